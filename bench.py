@@ -32,6 +32,7 @@ the library's per-kernel event hooks on); `roofline.traffic` comes from rocprofv
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import subprocess
@@ -82,7 +83,17 @@ def parse(argv=None):
                     help="train_step: untimed fitting steps before the warmup (BASELINE.md section 2: 200, so that opacities "
                          "and scales are no longer at their initial values; they also let the caching allocator see every "
                          "tensor size the varying visible set produces)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="headline / train_step on one GPU: after the timed steps, replay the same steps untimed from a fresh model "
+                         "under GSVC_DETERMINISTIC=1 and write the last one's outputs to DIR/<name>.npy (float32 / float64, at most "
+                         "64 MB in all: a larger output keeps a fixed seeded sample of its elements) — the same files in every run; "
+                         "the timed steps themselves run in the default mode as without the flag (line: dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and args.workload not in ("headline", "train_step"):
+        ap.error(f"--dump-outputs: the {args.workload} workload does not dump its outputs (headline / train_step do)")
+    if args.dump_outputs and (args.live_fit or args.gpus > 1):
+        ap.error("--dump-outputs: replays the frozen scene's steps on one GPU (no --live-fit, --gpus 1)")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -266,6 +277,57 @@ def reduce_sum_max(torch, dist, world, dev, total, elapsed):
     return float(t[0].item()), float(t[1].item())
 
 
+def result_line(res):
+    """The one JSON line: every number of ``res``, without the explanatory "note" / "*_note" strings (the same text in every run, and
+    the code beside each section says it).  With them the headline's line had grown past 20 kB; without them it is ~14 kB."""
+    def strip(v):
+        if isinstance(v, dict):
+            return {k: strip(x) for k, x in v.items() if not (k == "note" or k.endswith("_note"))}
+        return [strip(x) for x in v] if isinstance(v, list) else v
+    return json.dumps(strip(res), separators=(",", ":"))
+
+
+@contextlib.contextmanager
+def deterministic_mode():
+    """GSVC_DETERMINISTIC=1 inside (gsvc_amd.switches re-read); afterwards whatever the caller's environment said again."""
+    from gsvc_amd import switches
+    prev = os.environ.get("GSVC_DETERMINISTIC")
+    os.environ["GSVC_DETERMINISTIC"] = "1"
+    switches.reload()
+    try:
+        yield
+    finally:
+        if prev is None:
+            os.environ.pop("GSVC_DETERMINISTIC", None)
+        else:
+            os.environ["GSVC_DETERMINISTIC"] = prev
+        switches.reload()
+
+
+DUMP_BYTES = 64_000_000         # --dump-outputs: the whole directory, .npy headers included
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: ``arrays`` (name -> tensor / array / number) as ``path``/<name>.npy.  Floating point values are written as
+    float32 (float64 stays float64), integers and booleans as float64 (exact).  The files stay within DUMP_BYTES: smallest array
+    first, each takes at most an equal share of what is left; a larger one keeps that many of its flattened elements, at positions
+    drawn by numpy.random.default_rng(0) and sorted — the same positions in every run with the same shape."""
+    import numpy as np
+    import torch
+    host = {}
+    for name, v in arrays.items():
+        a = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
+        host[name] = a.astype(a.dtype if a.dtype == np.float64 else np.float32 if a.dtype.kind == "f" else np.float64)
+    os.makedirs(path, exist_ok=True)
+    left, n = DUMP_BYTES - 256 * len(host), len(host)          # (a .npy header is 128 bytes for these shapes)
+    for name, a in sorted(host.items(), key=lambda kv: kv[1].nbytes):
+        cap = left // n // a.itemsize
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left, n = left - a.nbytes, n - 1
+
+
 # ------------------------------------------------------------------------------------------------ stream_decode (cfg-5 shape)
 def run_stream_decode(args, dev, height=2160, width=3840, frames=300, gaussians_per_frame=2_000_000, n_render=24):
     """Entropy decode of a whole coded model + decoder render loop at the BASELINE.json configs[4] shape (reference
@@ -408,17 +470,13 @@ def _all_cores() -> int:
 
 
 # ------------------------------------------------------------------------------------------------ train_step
-def run_train_step(args, rank, world, dev):
-    """BASELINE.json configs[2]; frames shard over ranks with one gradient all-reduce per step."""
+def headline_model(args, dev):
+    """The headline's video, configuration and model, built from its seeds (run_train_step; dump_train_step builds the same again)."""
     import numpy as np
     import torch
-    import torch.distributed as dist
-    from gsvc_amd import _lib
-    from gsvc_amd import dist as gdist
     from gsvc_amd.arguments import cfg_20240919
     from gsvc_amd.frame import SyntheticFrameCube
     from gsvc_amd.model import GaussianModel
-    from gsvc_amd.train import Trainer
 
     if args.cfg3:
         args.anchors, args.train_frames = 100_000, 600
@@ -446,6 +504,20 @@ def run_train_step(args, rank, world, dev):
     pc.create_from_points(pts, spatial_lr_scale=1.0)
     pc.update_anchor_bound(cube.x_min, cube.y_min, cube.z_min)
     pc.training_setup(opt)
+    return cube, mp_, opt, pipe, pc, slab_frames
+
+
+def run_train_step(args, rank, world, dev):
+    """BASELINE.json configs[2]; frames shard over ranks with one gradient all-reduce per step."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    from gsvc_amd import _lib
+    from gsvc_amd import dist as gdist
+    from gsvc_amd.train import Trainer
+
+    cube, mp_, opt, pipe, pc, slab_frames = headline_model(args, dev)
+    H, W, T = args.height, args.width, args.train_frames
     if _dp_on(world):
         gdist.broadcast_parameters(pc)       # replicas start identical (they are built from the same seeds anyway)
     trainer = Trainer(pc, cube, opt, pipe, mp_, seed=args.scene_seed)
@@ -461,18 +533,10 @@ def run_train_step(args, rank, world, dev):
     # order, launch choices by row count only (gsvc_amd.switches GSVC_DETERMINISTIC) — so the model the timed steps start from is
     # the same bits in every run of this command (its checksum goes into the line), and `value` stops moving +-10 % with the
     # run's draw of active Gaussians.  The warm-up and the timed steps then run in the default (fast) mode.
-    from gsvc_amd import switches as _sw
     frozen = not args.live_fit and not _dp_on(world)
-    if frozen:
-        os.environ["GSVC_DETERMINISTIC"] = "1"
-        _sw.reload()
-    try:
+    with deterministic_mode() if frozen else contextlib.nullcontext():
         for _ in range(args.pretrain):
             step()
-    finally:
-        if frozen:
-            os.environ.pop("GSVC_DETERMINISTIC", None)
-            _sw.reload()
     scene_sum = 0
     with torch.no_grad():          # exact, order-free: the parameters' bit patterns added up as integers
         for _n, p_ in sorted(pc.named_parameters()):
@@ -487,6 +551,7 @@ def run_train_step(args, rank, world, dev):
         step()
     active = torch.zeros((), device=dev, dtype=torch.float64)
     submitted = [0]
+    it_timed0 = it[0]
 
     def counted():
         nonlocal active
@@ -502,6 +567,8 @@ def run_train_step(args, rank, world, dev):
                     "device_frees": int(mem1.get("num_device_free", 0) - mem0.get("num_device_free", 0)),
                     "alloc_retries": int(mem1.get("num_alloc_retries", 0) - mem0.get("num_alloc_retries", 0)),
                     "repeated_steps": int(getattr(trainer, "repeated_steps", 0) - rep0),
+                    "steps_run": it[0] - it_timed0, "last_iteration": it[0], "last_frame_idx": int(last[0].frame_idx),
+                    "last_loss": float(last[0].loss),
                     "reserved_GiB": round(mem1.get("reserved_bytes.all.current", 0) / 2 ** 30, 2)}
     elapsed_local = elapsed                    # this rank's own clock over the timed steps (the line's time is the MAX over the ranks)
     total_units, elapsed = reduce_sum_max(torch, dist, world, dev, active.item(), elapsed)
@@ -917,6 +984,33 @@ def run_train_step(args, rank, world, dev):
                                "seconds": round(tc, 3)}
         _gpu_cores()
     return res
+
+
+def dump_train_step(args, dev):
+    """--dump-outputs: the headline's steps once more, untimed, from a fresh model built from the same seeds — the frozen fit, then
+    ``args.warmup`` + ``args.steps`` steps at the timed steps' iterations and frames — with every one of them under GSVC_DETERMINISTIC=1,
+    and the last step's outputs written to ``args.dump_outputs``: its loss, averaged images, each render's image and radii, and the
+    model after its Adam update.  The timed steps run in the default mode, whose float atomics and wall-clock launch choices order
+    the sums differently run by run (Adam turns those last bits into whole learning-rate steps: 4e-3 of the loss after 25 steps);
+    this replay computes the same step in fixed order, so two runs of the command, or two builds, write the same files bit for bit
+    when they compute the same thing."""
+    import torch
+    from gsvc_amd.train import Trainer
+    cube, mp_, opt, pipe, pc, _ = headline_model(args, dev)
+    trainer = Trainer(pc, cube, opt, pipe, mp_, seed=args.scene_seed)
+    n = args.pretrain + args.warmup + args.steps
+    with deterministic_mode():
+        for i in range(1, n + 1):
+            o = trainer.step(i)
+        torch.cuda.synchronize()
+    arrays = {"loss": o.loss, "image1": o.image1, "image2": o.image2, "active_gaussians": o.active_gaussians, "frame_idx": o.frame_idx}
+    for i, r in enumerate(o.renders):
+        arrays[f"render{i}_image"], arrays[f"render{i}_radii"] = r.rendered_image, r.radii
+    for name, p_ in sorted(pc.named_parameters()):
+        arrays["param_" + name] = p_
+    dump_outputs(args.dump_outputs, arrays)
+    return {"dir": args.dump_outputs, "mode": "GSVC_DETERMINISTIC=1 (untimed replay of the headline's steps from a fresh model)",
+            "last_iteration": n, "frame_idx": int(o.frame_idx), "loss": float(o.loss), "files": len(arrays)}
 
 
 def run_train_step_late(args, dev, total=3000, stop_frac=0.6, anchors=100_000, steps=40):
@@ -1337,6 +1431,9 @@ def main():
     cpu = world == 1 and not args.no_cpu_baseline
     if args.workload in ("headline", "train_step"):
         res = run_train_step(args, rank, world, dev)
+        if args.dump_outputs:
+            torch.cuda.empty_cache()
+            res["dump_outputs"] = dump_train_step(args, dev)
         if args.workload == "headline" and not args.no_side and world == 1:
             # second term of the metric: render fps at 1080p on BASELINE.json configs[1]; a failure here must not take
             # the train-step line down
@@ -1405,9 +1502,9 @@ def main():
         # a line that claims N GPUs must come from N ranks of one process group (RCCL unless the test knob says otherwise)
         if res.get("n_gpus") != args.gpus or (world > 1 and res.get("rccl_ranks") != args.gpus):
             sys.stderr.write(f"bench.py: --gpus {args.gpus} but the line reports n_gpus={res.get('n_gpus')} rccl_ranks={res.get('rccl_ranks')}\n")
-            print(json.dumps(res), flush=True)
+            print(result_line(res), flush=True)
             sys.exit(3)
-        print(json.dumps(res), flush=True)
+        print(result_line(res), flush=True)
     if _dp_on(world):
         import torch.distributed as dist
         dist.destroy_process_group()

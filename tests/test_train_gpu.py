@@ -776,6 +776,41 @@ def test_bench_headline_scene_is_frozen():
 
 
 @pytest.mark.gpu
+def test_bench_dumps_its_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: the timed steps run in the default mode as without the flag (3 of them: the loop's own count); then the
+    same steps are replayed untimed from a fresh model under GSVC_DETERMINISTIC and the last one's loss, images, renders and the model
+    after its update written as .npy files (float32 / float64, 64 MB at most).  Two processes with the same arguments start from the
+    same scene (checksum) and write the same files bit for bit; the dump is the last timed step's iteration and frame, with its loss
+    within the default mode's spread."""
+    import json
+    import numpy as np
+    small = ["--workload", "train_step", "--steps", "3", "--warmup", "1", "--pretrain", "4", "--anchors", "20000", "--height", "272",
+             "--width", "480", "--no-cpu-baseline"]
+    runs, lines = [], []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        out = _run_bench({}, *small, "--dump-outputs", str(d))
+        assert out.returncode == 0, out.stderr[-2000:]
+        res = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
+        tr, du = res["timed_region"], res["dump_outputs"]
+        assert tr["steps_run"] == 3 and tr["last_iteration"] == 4 + 1 + 3 and res["ms_per_step"] > 0
+        assert du["last_iteration"] == tr["last_iteration"] and du["frame_idx"] == tr["last_frame_idx"]
+        assert sum(p.stat().st_size for p in d.iterdir()) <= 64_000_000
+        files = {p.name: np.load(p) for p in sorted(d.iterdir())}
+        assert float(files["loss.npy"]) == du["loss"] and files["frame_idx.npy"] == du["frame_idx"]
+        assert abs(du["loss"] - tr["last_loss"]) <= 1e-2 * abs(tr["last_loss"])
+        runs.append(files)
+        lines.append(res)
+    assert lines[0]["config"]["scene"]["checksum"] == lines[1]["config"]["scene"]["checksum"]
+    a, b = runs
+    assert a.keys() == b.keys() and {"loss.npy", "image1.npy", "image2.npy", "render3_radii.npy", "param__anchor.npy"} <= a.keys()
+    assert a["image1.npy"].shape == (3, 272, 480)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.isfinite(a[k]).all(), k
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+
+
+@pytest.mark.gpu
 def test_bench_gpus_flag_starts_that_many_ranks():
     """`python bench.py --gpus 2` (the driver's command form) must run TWO ranks or fail: with the single-GPU test knobs
     (both ranks on device 0, gloo) it starts torch.distributed.run as a child and relays rank 0's line with n_gpus = 2 —
