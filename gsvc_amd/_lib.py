@@ -37,6 +37,13 @@ class RasterSettingsC(C.Structure):
 RASTER_SLAB_ONE_SIDED, RASTER_PIXEL_CORNER, RASTER_DEPTH_DESCENDING = 1, 2, 4
 RASTER_MEANS2D_PIXEL_UNITS, RASTER_CLAMP_STOPS_GRADIENT, RASTER_NO_LOW_PASS = 8, 16, 32
 RASTER_TIGHT_BINNING = 64      # list a Gaussian only in the tiles its alpha >= 1/255 box touches (same results, shorter lists)
+RASTER_SH_VIEW_AXIS = 128      # SH colours at the view's constant axis instead of normalize(p - campos)
+
+
+class RasterSourcesC(C.Structure):
+    """gsvc_raster_sources: the optional SH colour / precomputed covariance inputs of the gsvc_raster_*_ex entry points."""
+    _fields_ = [("shs", C.c_void_p), ("sh_degree", C.c_int32), ("sh_coeffs", C.c_int32), ("campos", C.c_float * 3),
+                ("cov3D", C.c_void_p)]
 
 
 class AdamTensorC(C.Structure):
@@ -134,6 +141,10 @@ _SIGNATURES = {
     "gsvc_raster_forward_pair": (C.c_int, [C.POINTER(RasterSettingsC), _i64, _i64] + [_vp] * 11),
     "gsvc_raster_backward_scratch_bytes": (_i64, [_i64, _i64]),
     "gsvc_raster_backward": (C.c_int, [C.POINTER(RasterSettingsC), _i64, _i64] + [_vp] * 18),
+    "gsvc_raster_visible_filter_ex": (C.c_int, [C.POINTER(RasterSettingsC), _i64, _vp, _vp, _vp, C.POINTER(RasterSourcesC), _vp, _vp]),
+    "gsvc_raster_forward_ex": (C.c_int, [C.POINTER(RasterSettingsC), _i64, _i64] + [_vp] * 5 + [C.POINTER(RasterSourcesC)] + [_vp] * 6),
+    "gsvc_raster_backward_ex": (C.c_int, [C.POINTER(RasterSettingsC), _i64, _i64] + [_vp] * 5 + [C.POINTER(RasterSourcesC)]
+                                + [_vp] * 15),
     "gsvc_raster_binning_layout": (C.c_int, [C.POINTER(RasterSettingsC), _i64, _i64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gsvc_raster_image_layout": (C.c_int, [C.POINTER(RasterSettingsC), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gsvc_grid_forward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp]),

@@ -497,6 +497,11 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
 #endif
 constexpr int GBWD_COOP_MIN_ROWS = GSVC_GBWD_COOP_MIN_ROWS;      // rectangles from this many tiles are added up by the whole wave
 
+// SRC (SRC_SH | SRC_COV): the optional sources of gsvc_raster_backward_ex in ONE trailing RasterSrc argument (SRC = 0: none).
+//   SRC_COV  the covariance is read from cov3D; dL_dcov3D gets dL/dSigma per stored number, dL_dscales / dL_drotations zeros.
+//   SRC_SH   dL_dshs[k][c] = dL/dcolour[c] basis_k(dir) where channel c was not clamped (bits in GeomRec::pad), and, in the default
+//            direction convention, the gradient through dir = normalize(p - campos) is added to dL_dmeans3D.
+template <int SRC = 0, typename... Src>
 __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, const float *__restrict__ means3D,
                                                       const float *__restrict__ scales,
                                                       const float *__restrict__ rotations,
@@ -506,11 +511,14 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
                                                       const gsvc_raster_counters *__restrict__ counters,
                                                       float *__restrict__ dL_dmeans3D, float *__restrict__ dL_dmeans2D,
                                                       float *__restrict__ dL_dcolors, float *__restrict__ dL_dopacities,
-                                                      float *__restrict__ dL_dscales, float *__restrict__ dL_drotations)
+                                                      float *__restrict__ dL_dscales, float *__restrict__ dL_drotations,
+                                                      Src... src_arg)
 {
+    static_assert(SRC == 0 || sizeof...(Src) == 1, "one RasterSrc argument");
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const int lane = threadIdx.x & 63;
     float g3[3] = {0, 0, 0}, g2[3] = {0, 0, 0}, gc[3] = {0, 0, 0}, gs[3] = {0, 0, 0}, gq[4] = {0, 0, 0, 0}, go = 0.f;
+    float gcov[6] = {0, 0, 0, 0, 0, 0};     // SRC_COV
     const bool overflow = counters->overflow != 0;
     const bool act = i < P && !overflow && radii[i] > 0;
     // this Gaussian's rows of the partial-sum buffer: one per tile of its rectangle, contiguous, added in a FIXED order (tile order by
@@ -521,6 +529,7 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
     // latency for ~140 MB of rows).
     int n_rows = 0, tw = 1, rx0 = 0, ry0 = 0, goff = 0;
     uint32_t abx = 0u, aby = 0u;
+    uint32_t sh_clamp = 0u;     // SRC_SH: the clamp bits k_preprocess left in the record's pad word
     if (act) {
         const float4 w2 = reinterpret_cast<const float4 *>(geom + i)[2];
         const float4 w3 = reinterpret_cast<const float4 *>(geom + i)[3];
@@ -530,6 +539,7 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
         n_rows = tw * ((int)(ry >> 16) - ry0);
         goff = __float_as_int(w2.w);
         abx = __float_as_uint(w2.y); aby = __float_as_uint(w2.z);      // alpha bounding box
+        if constexpr ((SRC & SRC_SH) != 0) sh_clamp = __float_as_uint(w3.w);
     }
     float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
     float a2 = 0.f;
@@ -605,9 +615,15 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
     if (act) {
         float du, dv, dA, dB, dC;
         PreOut o;
+        if constexpr ((SRC & SRC_COV) != 0) {
+            const RasterSrc &src = (src_arg, ...);
+            preprocess_gaussian_src<true>(st, means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2], src.cov3D + 6 * (size_t)i,
+                                          0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, o);
+        } else {
         preprocess_gaussian(st, means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2], scales[3 * i], scales[3 * i + 1],
                             scales[3 * i + 2], rotations[4 * i], rotations[4 * i + 1], rotations[4 * i + 2],
                             rotations[4 * i + 3], o);
+        }
         // accumulator holds moments of h = G dL/dalpha: (sum h, h dx, h dy, h dx^2, h dx dy, h dy^2, colour grads)
         const float op = opacities[i];
         const float sh = a0.x, sx = a0.y, sy = a0.z, sxx = a0.w, sxy = a1.x, syy = a1.y;
@@ -622,8 +638,12 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
         const float *M = st.m;
         for (int j = 0; j < 3; j++) g3[j] = st.scale * (M[j] * du + M[4 + j] * dv);
 
-        const float s0 = scales[3 * i], s1 = scales[3 * i + 1], s2 = scales[3 * i + 2];
-        const float4 q = reinterpret_cast<const float4 *>(rotations)[i];
+        float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+        float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
+        if constexpr ((SRC & SRC_COV) == 0) {
+            s0 = scales[3 * i]; s1 = scales[3 * i + 1]; s2 = scales[3 * i + 2];
+            q = reinterpret_cast<const float4 *>(rotations)[i];
+        }
         const float ca = o.a, cb = o.b, cc = o.c;
         const float det = ca * cc - cb * cb;
         const float inv2 = 1.0f / (det * det + 1e-7f);
@@ -636,6 +656,11 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
         for (int r = 0; r < 3; r++)
             for (int c = 0; c < 3; c++)
                 G3[r][c] = T0[r] * dLa * T0[c] + 0.5f * dLb * (T0[r] * T1[c] + T1[r] * T0[c]) + T1[r] * dLc * T1[c];
+        if constexpr ((SRC & SRC_COV) != 0) {
+            // the six stored numbers: an off-diagonal one stands for both symmetric entries of Sigma
+            gcov[0] = G3[0][0]; gcov[1] = G3[0][1] + G3[1][0]; gcov[2] = G3[0][2] + G3[2][0];
+            gcov[3] = G3[1][1]; gcov[4] = G3[1][2] + G3[2][1]; gcov[5] = G3[2][2];
+        } else {
         const float qr = q.x, qx = q.y, qy = q.z, qz = q.w;
         const float R[3][3] = {{1.f - 2.f * (qy * qy + qz * qz), 2.f * (qx * qy - qr * qz), 2.f * (qx * qz + qr * qy)},
                                {2.f * (qx * qy + qr * qz), 1.f - 2.f * (qx * qx + qz * qz), 2.f * (qy * qz - qr * qx)},
@@ -660,6 +685,57 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
                        qz * dR[2][1] - 2.f * qy * dR[2][2]);
         gq[3] = 2.f * (-2.f * qz * dR[0][0] - qr * dR[0][1] + qx * dR[0][2] + qr * dR[1][0] - 2.f * qz * dR[1][1] +
                        qy * dR[1][2] + qx * dR[2][0] + qy * dR[2][1]);
+        }
+    }
+    if constexpr ((SRC & SRC_COV) != 0) {
+        const RasterSrc &src = (src_arg, ...);
+        if (src.dL_dcov3D != nullptr) {
+            float2 *dst = reinterpret_cast<float2 *>(src.dL_dcov3D + 6 * (size_t)i);
+            dst[0] = make_float2(gcov[0], gcov[1]); dst[1] = make_float2(gcov[2], gcov[3]); dst[2] = make_float2(gcov[4], gcov[5]);
+        }
+    }
+    if constexpr ((SRC & SRC_SH) != 0) {
+        // dL/dsh[k][c] = dL/dcolour[c] basis_k(dir) (0 where channel c was clamped), written row by row in 16-byte pieces, zeros
+        // beyond the active degree and for culled Gaussians; the gradient through dir is gathered in the same pass over the row
+        const RasterSrc &src = (src_arg, ...);
+        const bool vec = src.sh_vec != 0;
+        const bool dir_term = act && !(st.flags & GSVC_RASTER_SH_VIEW_AXIS);
+        const int n = 3 * (src.sh_degree + 1) * (src.sh_degree + 1), row_len = 3 * src.sh_coeffs;
+        const float gm[3] = {(sh_clamp & 1u) ? 0.f : gc[0], (sh_clamp & 2u) ? 0.f : gc[1], (sh_clamp & 4u) ? 0.f : gc[2]};
+        float len = 1.f;
+        const float3 dir = act ? sh_dir(st, src, means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2], len) : make_float3(0.f, 0.f, 0.f);
+        const float *row = src.shs + (size_t)i * row_len;
+        float *drow = src.dL_dshs != nullptr ? src.dL_dshs + (size_t)i * row_len : nullptr;
+        float gdx = 0.f, gdy = 0.f, gdz = 0.f;      // dL/d(unit direction)
+#pragma unroll
+        for (int j = 0; j < 12; j++) {
+            if (4 * j >= n) break;
+            const float4 v = dir_term ? sh_load4(row, 4 * j, n, vec) : make_float4(0.f, 0.f, 0.f, 0.f);
+            float out[4];
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                const int e = 4 * j + t, k = e / 3, c = e % 3;
+                out[t] = 0.f;
+                if (e < n && act) {
+                    out[t] = gm[c] * sh_basis(k, dir.x, dir.y, dir.z);
+                    if (dir_term) {
+                        const float3 g = sh_basis_grad(k, dir.x, dir.y, dir.z);
+                        const float w = gm[c] * f4_at(v, t);
+                        gdx += w * g.x; gdy += w * g.y; gdz += w * g.z;
+                    }
+                }
+            }
+            if (drow) sh_store4(drow, 4 * j, row_len, vec, make_float4(out[0], out[1], out[2], out[3]));
+        }
+        if (drow)
+            for (int e0 = (n + 3) & ~3; e0 < row_len; e0 += 4) sh_store4(drow, e0, row_len, vec, make_float4(0.f, 0.f, 0.f, 0.f));
+        if (dir_term) {
+            // dir = d / |d|, d = p - campos: dL/dd = (dL/ddir - dir (dir . dL/ddir)) / |d|
+            const float dd = dir.x * gdx + dir.y * gdy + dir.z * gdz, inv = 1.0f / len;
+            g3[0] += (gdx - dir.x * dd) * inv;
+            g3[1] += (gdy - dir.y * dd) * inv;
+            g3[2] += (gdz - dir.z * dd) * inv;
+        }
     }
     for (int j = 0; j < 3; j++) {
         dL_dmeans3D[3 * i + j] = g3[j];
@@ -681,18 +757,18 @@ extern "C" int64_t gsvc_raster_backward_scratch_bytes(int64_t P, int64_t max_ins
     return (max_instances > 0 ? max_instances : 1) * (int64_t)(ROW_FLOATS * sizeof(float));
 }
 
-extern "C" int gsvc_raster_backward(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
-                                    const float *means3D, const float *colors, const float *opacities,
-                                    const float *scales, const float *rotations, const int32_t *radii, const void *geom,
-                                    const void *binning, const void *image_state, const float *dL_dimage,
-                                    float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities,
-                                    float *dL_dscales, float *dL_drotations, void *scratch, void *stream)
+static int raster_backward_impl(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
+                                const float *means3D, const float *opacities, const float *scales, const float *rotations,
+                                const int32_t *radii, const void *geom, const void *binning, const void *image_state,
+                                const float *dL_dimage, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                                float *dL_dopacities, float *dL_dscales, float *dL_drotations, void *scratch, void *stream,
+                                int src_kind = 0, const RasterSrc *src = nullptr)
 {
-    (void)colors;
     GSVC_REQUIRE(settings != nullptr, "raster_backward: settings is NULL");
     GSVC_REQUIRE(P >= 0 && P < (int64_t)1 << 31 && max_instances >= 0, "raster_backward: bad sizes");
     if (P == 0) return GSVC_OK;
-    GSVC_REQUIRE(means3D && opacities && scales && rotations && radii && geom && binning && image_state && dL_dimage && scratch,
+    GSVC_REQUIRE(means3D && opacities && ((src_kind & SRC_COV) || (scales && rotations)) && radii && geom && binning &&
+                     image_state && dL_dimage && scratch,
                  "raster_backward: NULL input pointer");
     GSVC_REQUIRE(dL_dmeans3D && dL_dmeans2D && dL_dcolors && dL_dopacities && dL_dscales && dL_drotations,
                  "raster_backward: NULL output pointer");
@@ -722,9 +798,49 @@ extern "C" int gsvc_raster_backward(const gsvc_raster_settings *settings, int64_
     }
     {
         ProfScope _prof("k_gaussian_bwd", s);
-        hipLaunchKernelGGL(k_gaussian_bwd, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, p, (int)P, means3D,
-                           scales, rotations, opacities, radii, (const GeomRec *)geom, (const float *)scratch, counters,
-                           dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations);
+        auto launch = [&](auto kernel, auto... extra) {
+            hipLaunchKernelGGL(kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, p, (int)P, means3D,
+                               scales, rotations, opacities, radii, (const GeomRec *)geom, (const float *)scratch, counters,
+                               dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, extra...);
+        };
+        if (src_kind == SRC_SH) launch(&k_gaussian_bwd<SRC_SH, RasterSrc>, *src);
+        else if (src_kind == SRC_COV) launch(&k_gaussian_bwd<SRC_COV, RasterSrc>, *src);
+        else if (src_kind == (SRC_SH | SRC_COV)) launch(&k_gaussian_bwd<SRC_SH | SRC_COV, RasterSrc>, *src);
+        else launch(&k_gaussian_bwd<>);
     }
     return check_launch("raster_backward");
+}
+
+extern "C" int gsvc_raster_backward(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
+                                    const float *means3D, const float *colors, const float *opacities,
+                                    const float *scales, const float *rotations, const int32_t *radii, const void *geom,
+                                    const void *binning, const void *image_state, const float *dL_dimage,
+                                    float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities,
+                                    float *dL_dscales, float *dL_drotations, void *scratch, void *stream)
+{
+    (void)colors;
+    return raster_backward_impl(settings, P, max_instances, means3D, opacities, scales, rotations, radii, geom, binning,
+                                image_state, dL_dimage, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales,
+                                dL_drotations, scratch, stream);
+}
+
+extern "C" int gsvc_raster_backward_ex(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
+                                       const float *means3D, const float *colors, const float *opacities,
+                                       const float *scales, const float *rotations, const gsvc_raster_sources *sources,
+                                       const int32_t *radii, const void *geom, const void *binning, const void *image_state,
+                                       const float *dL_dimage, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                                       float *dL_dopacities, float *dL_dscales, float *dL_drotations, float *dL_dshs,
+                                       float *dL_dcov3D, void *scratch, void *stream)
+{
+    GSVC_REQUIRE(settings != nullptr, "raster_backward_ex: settings is NULL");
+    RasterSrc src;
+    int kind;
+    if (int rc = raster_sources_check("raster_backward_ex", colors, scales, rotations, sources, true, src, kind)) return rc;
+    src.dL_dshs = (kind & SRC_SH) ? dL_dshs : nullptr;
+    src.dL_dcov3D = (kind & SRC_COV) ? dL_dcov3D : nullptr;
+    GSVC_REQUIRE(!src.dL_dcov3D || ((uintptr_t)src.dL_dcov3D & 7u) == 0, "raster_backward_ex: dL_dcov3D must be 8-byte aligned");
+    src.sh_vec = (src.sh_coeffs % 4 == 0 && ((uintptr_t)src.shs & 15u) == 0 && ((uintptr_t)src.dL_dshs & 15u) == 0) ? 1 : 0;
+    return raster_backward_impl(settings, P, max_instances, means3D, opacities, scales, rotations, radii, geom, binning,
+                                image_state, dL_dimage, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales,
+                                dL_drotations, scratch, stream, kind, &src);
 }

@@ -95,6 +95,27 @@ struct RasterParams {
     float pix_off;      // 0.5 (pixel centres on integers) or 0
 };
 
+// Optional sources of the _ex entry points (gsvc_raster_sources + the backward's two extra outputs), as the kernels take them.
+// A kernel instantiated with SRC = 0 has no such argument at all (an empty trailing parameter pack): its argument block, and
+// so its code, is the one it had before the sources existed.
+constexpr int SRC_SH = 1;       // colours from shs[P, sh_coeffs, 3] instead of colors[P, 3]
+constexpr int SRC_COV = 2;      // 3-D covariance from cov3D[P, 6] instead of scales / rotations
+struct RasterSrc {
+    const float *shs;
+    const float *cov3D;
+    float *dL_dshs;             // backward only, may be NULL
+    float *dL_dcov3D;           // backward only, may be NULL
+    int sh_degree, sh_coeffs;
+    int sh_vec;                 // shs / dL_dshs rows are 16-byte aligned (sh_coeffs % 4 == 0, aligned bases): float4 access
+    float campos[3];
+};
+
+// Host-side checks of gsvc_raster_sources for the _ex entry points (raster_fwd.hip): -1 with gsvc_last_error() set on degree
+// outside 0..3, too small an sh_coeffs, both or neither colour sources (need_colour) and both or neither covariance sources.
+// Fills the kernels' RasterSrc (campos, degree, pointers) and the SRC_* bits of what was given.
+int raster_sources_check(const char *fn, const float *colors, const float *scales, const float *rotations,
+                         const gsvc_raster_sources *sources, bool need_colour, RasterSrc &src, int &kind);
+
 inline RasterParams make_params(const gsvc_raster_settings &s)
 {
     RasterParams p;
@@ -172,9 +193,13 @@ __device__ __forceinline__ bool ellipse_hits_quad(float u, float v, float A, flo
 // Steps 1-7 of the raster spec.  Every operation here decides an integer downstream (radius, tile
 // rectangle, depth key), so it is plain IEEE binary32 in a fixed order with no FMA contraction — the CPU
 // oracle repeats it bit for bit.  sqrt and division are the correctly rounded forms.
-__device__ __forceinline__ int preprocess_gaussian(const RasterParams &st, float px, float py, float pz,
-                                                   float s0, float s1, float s2, float qr, float qx, float qy,
-                                                   float qz, PreOut &o)
+// COV: the 3-D covariance c00..c22 is read from cov (one [6] row: xx, xy, xz, yy, yz, zz) instead of being built from
+// scale and rotation (s*, q* unused), and scale_modifier is not applied to it (the caller has, as in the 3DGS lineage).
+// Everything after the covariance is shared: a cov row computed in float32 in this function's order gives the same bits.
+template <bool COV>
+__device__ __forceinline__ int preprocess_gaussian_src(const RasterParams &st, float px, float py, float pz, const float *cov,
+                                                       float s0, float s1, float s2, float qr, float qx, float qy,
+                                                       float qz, PreOut &o)
 {
 #pragma clang fp contract(off)
     const float *M = st.m;
@@ -188,6 +213,12 @@ __device__ __forceinline__ int preprocess_gaussian(const RasterParams &st, float
         if (!(zv <= 0.0f && zv >= -st.threshold)) return 0;
     } else if (!(fabsf(zv) <= st.threshold)) return 0;
 
+    float c00, c01, c02, c11, c12, c22;
+    if constexpr (COV) {
+        const float2 w0 = reinterpret_cast<const float2 *>(cov)[0], w1 = reinterpret_cast<const float2 *>(cov)[1],
+                     w2 = reinterpret_cast<const float2 *>(cov)[2];
+        c00 = w0.x; c01 = w0.y; c02 = w1.x; c11 = w1.y; c12 = w2.x; c22 = w2.y;
+    } else {
     float R00 = 1.f - 2.f * (qy * qy + qz * qz);
     float R01 = 2.f * (qx * qy - qr * qz);
     float R02 = 2.f * (qx * qz + qr * qy);
@@ -201,12 +232,13 @@ __device__ __forceinline__ int preprocess_gaussian(const RasterParams &st, float
     float L00 = R00 * S0, L01 = R01 * S1, L02 = R02 * S2;
     float L10 = R10 * S0, L11 = R11 * S1, L12 = R12 * S2;
     float L20 = R20 * S0, L21 = R21 * S1, L22 = R22 * S2;
-    float c00 = L00 * L00 + L01 * L01 + L02 * L02;
-    float c01 = L00 * L10 + L01 * L11 + L02 * L12;
-    float c02 = L00 * L20 + L01 * L21 + L02 * L22;
-    float c11 = L10 * L10 + L11 * L11 + L12 * L12;
-    float c12 = L10 * L20 + L11 * L21 + L12 * L22;
-    float c22 = L20 * L20 + L21 * L21 + L22 * L22;
+    c00 = L00 * L00 + L01 * L01 + L02 * L02;
+    c01 = L00 * L10 + L01 * L11 + L02 * L12;
+    c02 = L00 * L20 + L01 * L21 + L02 * L22;
+    c11 = L10 * L10 + L11 * L11 + L12 * L12;
+    c12 = L10 * L20 + L11 * L21 + L12 * L22;
+    c22 = L20 * L20 + L21 * L21 + L22 * L22;
+    }
 
     float T00 = st.scale * M[0], T01 = st.scale * M[1], T02 = st.scale * M[2];
     float T10 = st.scale * M[4], T11 = st.scale * M[5], T12 = st.scale * M[6];
@@ -247,6 +279,138 @@ __device__ __forceinline__ int preprocess_gaussian(const RasterParams &st, float
     if ((x1 - x0) * (y1 - y0) <= 0) return 0;
     o.radius = radius;
     return radius;
+}
+
+__device__ __forceinline__ int preprocess_gaussian(const RasterParams &st, float px, float py, float pz,
+                                                   float s0, float s1, float s2, float qr, float qx, float qy,
+                                                   float qz, PreOut &o)
+{
+    return preprocess_gaussian_src<false>(st, px, py, pz, nullptr, s0, s1, s2, qr, qx, qy, qz, o);
+}
+
+// SH colour source.  The real spherical harmonics up to degree 3 in the 3DGS lineage's order and signs (Condon-Shortley phase),
+// as polynomials of the unit direction (x, y, z):
+//   l = 0   Y0  = 1/2 sqrt(1/pi)
+//   l = 1   -sqrt(3/(4 pi)) y,  sqrt(3/(4 pi)) z,  -sqrt(3/(4 pi)) x
+//   l = 2   1/2 sqrt(15/pi) xy,  -1/2 sqrt(15/pi) yz,  1/4 sqrt(5/pi) (2z^2 - x^2 - y^2),  -1/2 sqrt(15/pi) xz,
+//           1/4 sqrt(15/pi) (x^2 - y^2)
+//   l = 3   -1/4 sqrt(35/(2 pi)) y (3x^2 - y^2),  1/2 sqrt(105/pi) xyz,  -1/4 sqrt(21/(2 pi)) y (4z^2 - x^2 - y^2),
+//           1/4 sqrt(7/pi) z (2z^2 - 3x^2 - 3y^2),  -1/4 sqrt(21/(2 pi)) x (4z^2 - x^2 - y^2),  1/4 sqrt(105/pi) z (x^2 - y^2),
+//           -1/4 sqrt(35/(2 pi)) x (x^2 - 3y^2)
+constexpr float SH_Y0 = 0.28209479177387814f;
+constexpr float SH_Y1 = 0.48860251190291992f;
+constexpr float SH_Y2A = 1.0925484305920792f, SH_Y2B = 0.31539156525252005f, SH_Y2C = 0.54627421529603959f;
+constexpr float SH_Y3A = 0.59004358992664352f, SH_Y3B = 2.8906114426405538f, SH_Y3C = 0.45704579946446572f,
+                SH_Y3D = 0.3731763325901154f, SH_Y3E = 1.4453057213202769f;
+
+// basis function k (0..15) at unit direction (x, y, z); k is a compile-time constant wherever it is called (unrolled loops)
+__device__ __forceinline__ float sh_basis(int k, float x, float y, float z)
+{
+    switch (k) {
+    case 0: return SH_Y0;
+    case 1: return -SH_Y1 * y;
+    case 2: return SH_Y1 * z;
+    case 3: return -SH_Y1 * x;
+    case 4: return SH_Y2A * (x * y);
+    case 5: return -SH_Y2A * (y * z);
+    case 6: return SH_Y2B * (2.f * z * z - x * x - y * y);
+    case 7: return -SH_Y2A * (x * z);
+    case 8: return SH_Y2C * (x * x - y * y);
+    case 9: return -SH_Y3A * y * (3.f * x * x - y * y);
+    case 10: return SH_Y3B * (x * y * z);
+    case 11: return -SH_Y3C * y * (4.f * z * z - x * x - y * y);
+    case 12: return SH_Y3D * z * (2.f * z * z - 3.f * x * x - 3.f * y * y);
+    case 13: return -SH_Y3C * x * (4.f * z * z - x * x - y * y);
+    case 14: return SH_Y3E * z * (x * x - y * y);
+    default: return -SH_Y3A * x * (x * x - 3.f * y * y);
+    }
+}
+
+// gradient of basis function k with respect to (x, y, z), the polynomial above differentiated as it stands
+__device__ __forceinline__ float3 sh_basis_grad(int k, float x, float y, float z)
+{
+    switch (k) {
+    case 0: return make_float3(0.f, 0.f, 0.f);
+    case 1: return make_float3(0.f, -SH_Y1, 0.f);
+    case 2: return make_float3(0.f, 0.f, SH_Y1);
+    case 3: return make_float3(-SH_Y1, 0.f, 0.f);
+    case 4: return make_float3(SH_Y2A * y, SH_Y2A * x, 0.f);
+    case 5: return make_float3(0.f, -SH_Y2A * z, -SH_Y2A * y);
+    case 6: return make_float3(-2.f * SH_Y2B * x, -2.f * SH_Y2B * y, 4.f * SH_Y2B * z);
+    case 7: return make_float3(-SH_Y2A * z, 0.f, -SH_Y2A * x);
+    case 8: return make_float3(2.f * SH_Y2C * x, -2.f * SH_Y2C * y, 0.f);
+    case 9: return make_float3(-6.f * SH_Y3A * x * y, -SH_Y3A * (3.f * x * x - 3.f * y * y), 0.f);
+    case 10: return make_float3(SH_Y3B * y * z, SH_Y3B * x * z, SH_Y3B * x * y);
+    case 11: return make_float3(2.f * SH_Y3C * x * y, -SH_Y3C * (4.f * z * z - x * x - 3.f * y * y), -8.f * SH_Y3C * y * z);
+    case 12: return make_float3(-6.f * SH_Y3D * x * z, -6.f * SH_Y3D * y * z, SH_Y3D * (6.f * z * z - 3.f * x * x - 3.f * y * y));
+    case 13: return make_float3(-SH_Y3C * (4.f * z * z - 3.f * x * x - y * y), 2.f * SH_Y3C * x * y, -8.f * SH_Y3C * x * z);
+    case 14: return make_float3(2.f * SH_Y3E * x * z, -2.f * SH_Y3E * y * z, SH_Y3E * (x * x - y * y));
+    default: return make_float3(-SH_Y3A * (3.f * x * x - 3.f * y * y), 6.f * SH_Y3A * x * y, 0.f);
+    }
+}
+
+// The direction the SH colours of a Gaussian at world position p are evaluated at (unnormalised in d, its length in len):
+// p - campos, or the view's constant axis under GSVC_RASTER_SH_VIEW_AXIS.
+__device__ __forceinline__ float3 sh_dir(const RasterParams &st, const RasterSrc &src, float px, float py, float pz, float &len)
+{
+    float3 d;
+    if (st.flags & GSVC_RASTER_SH_VIEW_AXIS) d = make_float3(st.m[8], st.m[9], st.m[10]);
+    else d = make_float3(px - src.campos[0], py - src.campos[1], pz - src.campos[2]);
+    len = sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
+    const float inv = 1.0f / len;
+    return make_float3(d.x * inv, d.y * inv, d.z * inv);
+}
+
+// The 4 floats of an SH row (or of its gradient) starting at float e0: one 16-byte access when the rows are aligned, else
+// four scalar ones.  Floats at or beyond `len` are neither read (0 is returned) nor written.
+__device__ __forceinline__ float4 sh_load4(const float *row, int e0, int len, bool vec)
+{
+    if (vec) return *reinterpret_cast<const float4 *>(row + e0);
+    float4 v;
+    v.x = e0 < len ? row[e0] : 0.f;
+    v.y = e0 + 1 < len ? row[e0 + 1] : 0.f;
+    v.z = e0 + 2 < len ? row[e0 + 2] : 0.f;
+    v.w = e0 + 3 < len ? row[e0 + 3] : 0.f;
+    return v;
+}
+
+__device__ __forceinline__ void sh_store4(float *row, int e0, int len, bool vec, float4 v)
+{
+    if (vec) { *reinterpret_cast<float4 *>(row + e0) = v; return; }
+    if (e0 < len) row[e0] = v.x;
+    if (e0 + 1 < len) row[e0 + 1] = v.y;
+    if (e0 + 2 < len) row[e0 + 2] = v.z;
+    if (e0 + 3 < len) row[e0 + 3] = v.w;
+}
+
+__device__ __forceinline__ float f4_at(const float4 &v, int t) { return t == 0 ? v.x : t == 1 ? v.y : t == 2 ? v.z : v.w; }
+
+// SH colour of one Gaussian: rgb = max(sum_k basis_k(dir) sh[k] + 0.5, 0), accumulated coefficient by coefficient from 16-byte
+// loads of its row (only the 4 floats of one load and the 3 sums live: k_preprocess runs at 1024 lanes per workgroup).  Returns
+// the three clamp bits (bit c: channel c was clamped, it passes no gradient).
+__device__ __forceinline__ uint32_t sh_colour(const RasterSrc &src, const float *row, float x, float y, float z, float rgb[3])
+{
+    const int n = 3 * (src.sh_degree + 1) * (src.sh_degree + 1);      // floats of the active coefficients: 3, 12, 27, 48
+    const bool vec = src.sh_vec != 0;
+    float acc[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 12; j++) {
+        if (4 * j >= n) break;
+        const float4 v = sh_load4(row, 4 * j, n, vec);
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const int e = 4 * j + t;
+            if (e < n) acc[e % 3] += sh_basis(e / 3, x, y, z) * f4_at(v, t);
+        }
+    }
+    uint32_t clamp = 0u;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const float r = acc[c] + 0.5f;
+        if (r < 0.f) clamp |= 1u << c;
+        rgb[c] = fmaxf(r, 0.f);
+    }
+    return clamp;
 }
 
 #endif  // __HIPCC__

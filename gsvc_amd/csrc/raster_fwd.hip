@@ -69,6 +69,17 @@ __global__ void __launch_bounds__(256) k_visible_filter(RasterParams st, int P, 
                                    scales[3 * i + 1], scales[3 * i + 2], q.x, q.y, q.z, q.w, o);
 }
 
+// The same test with the 3-D covariance read from cov3D[P, 6] (gsvc_raster_visible_filter_ex).
+__global__ void __launch_bounds__(256) k_visible_filter_cov(RasterParams st, int P, const float *__restrict__ means3D,
+                                                            const float *__restrict__ cov3D, int32_t *__restrict__ radii)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    PreOut o;
+    radii[i] = preprocess_gaussian_src<true>(st, means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2], cov3D + 6 * (size_t)i,
+                                             0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, o);
+}
+
 // The visibility test of R views over the same anchors in one launch (a fitting step tests its four views): the anchor is read
 // once, masks[r][i] = radius under view r > 0.  The per-anchor scales / rotations may be given raw — scales as their logarithm
 // (``scale_exp``: scene/gaussian_model.py scaling_activation = exp), rows ``scale_stride`` floats apart (the first three of the
@@ -239,7 +250,9 @@ __device__ __forceinline__ void for_each_extra(int lane, int nt, int x0, int w, 
 // PAIR: bin for the two-view frame — a Gaussian is listed in the union of this view's tile rectangle and the
 // opposite view's rectangle mirrored into this view's tile grid (the 3-sigma rectangle formula is not mirror
 // symmetric, so the two differ by up to one tile column); K3 tags every instance with the views it belongs to.
-template <bool USE_LDS, bool PAIR>
+// SRC: the optional sources (SRC_SH | SRC_COV, single view only), given in ONE trailing RasterSrc argument; SRC = 0 has none.
+// With SRC_SH the record's pad word holds the three clamp bits of the SH colour for the backward.
+template <bool USE_LDS, bool PAIR, int SRC = 0, typename... Src>
 __global__ void __launch_bounds__(1024) k_preprocess(RasterParams st, int P, const float *__restrict__ means3D,
                                                      const float *__restrict__ colors,
                                                      const float *__restrict__ opacities,
@@ -249,8 +262,9 @@ __global__ void __launch_bounds__(1024) k_preprocess(RasterParams st, int P, con
                                                      int32_t *__restrict__ tile_count, int32_t *__restrict__ tile_extra,
                                                      gsvc_raster_counters *__restrict__ counters,
                                                      int32_t *__restrict__ tile_offsets, int32_t *__restrict__ big_list,
-                                                     int32_t *__restrict__ wg_extras, long long max_instances)
+                                                     int32_t *__restrict__ wg_extras, long long max_instances, Src... src_arg)
 {
+    static_assert(SRC == 0 || (!PAIR && sizeof...(Src) == 1), "the optional sources serve the single-view forward");
     extern __shared__ int hist[];
     __shared__ int s_wt[16];
     __shared__ int s_gbase;
@@ -278,15 +292,22 @@ __global__ void __launch_bounds__(1024) k_preprocess(RasterParams st, int P, con
     float rec2_b = 0.f;
     uint32_t rec2_bx = 0u, rec2_by = 0u;
     uint32_t ub_bits = 0u;     // pair mode: the opposite view's pixel x of this Gaussian (float bits), kept in GeomRec::pad
+    uint32_t sh_clamp = 0u;    // SRC_SH: the colour's clamp bits, kept in GeomRec::pad
     if (i < P) {
         // a Gaussian with opacity <= 0 can never reach alpha >= 1/255: culled here (radius 0), which lets callers
         // pass un-compacted Gaussian sets (GSVC's "opacity > 0" selection) without a host-side compaction
         const float op = opacities[i];
         o.radius_raw = 0;
         if (op > 0.0f) {
+            if constexpr ((SRC & SRC_COV) != 0) {
+                const RasterSrc &src = (src_arg, ...);
+                radius = preprocess_gaussian_src<true>(st, means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2],
+                                                       src.cov3D + 6 * (size_t)i, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, o);
+            } else {
             const float4 q = reinterpret_cast<const float4 *>(rotations)[i];
             radius = preprocess_gaussian(st, means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2], scales[3 * i],
                                          scales[3 * i + 1], scales[3 * i + 2], q.x, q.y, q.z, q.w, o);
+            }
         }
         radii[i] = radius;
         GeomRec rec;
@@ -360,7 +381,15 @@ __global__ void __launch_bounds__(1024) k_preprocess(RasterParams st, int P, con
         if (listed) {
             rec.u = o.u; rec.v = o.v; rec.A = o.A; rec.B = o.B;
             rec.C = o.C; rec.opacity = op;
+            if constexpr ((SRC & SRC_SH) != 0) {
+                const RasterSrc &src = (src_arg, ...);
+                float len, rgb[3];
+                const float3 dir = sh_dir(st, src, means3D[3 * i], means3D[3 * i + 1], means3D[3 * i + 2], len);
+                sh_clamp = sh_colour(src, src.shs + (size_t)i * (3 * src.sh_coeffs), dir.x, dir.y, dir.z, rgb);
+                rec.r = rgb[0]; rec.g = rgb[1]; rec.b = rgb[2];
+            } else {
             rec.r = colors[3 * i + 0]; rec.g = colors[3 * i + 1]; rec.b = colors[3 * i + 2];
+            }
             rec.depth = o.depth;
             if (PAIR && radius <= 0 && !tight) alpha_bbox(o.u, o.v, o.A, o.B, o.C, rec.opacity, abx, aby);      // listed for the opposite view only
             rec.bbox_x = abx; rec.bbox_y = aby;
@@ -389,7 +418,7 @@ __global__ void __launch_bounds__(1024) k_preprocess(RasterParams st, int P, con
             rec.rect_x = rec.rect_y = 0u;
             br.depth = 0.f; br.rect_x = br.rect_y = 0u;
         }
-        rec.goff = 0; rec.pad = PAIR ? ub_bits : 0u;
+        rec.goff = 0; rec.pad = PAIR ? ub_bits : sh_clamp;
         // the record of a Gaussian that is in no list is never read (the sort, the compositing kernels and the backward reach
         // records through list entries or behind radii > 0): a fitting render culls ~70 % of what it submits (opacity <= 0), and
         // their 64 + 16 bytes of zeros were a quarter of this kernel's stores
@@ -1358,7 +1387,7 @@ extern "C" int gsvc_raster_visible_masks(const gsvc_raster_settings *const *sett
 static int raster_forward_impl(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
                                const float *means3D, const float *colors, const float *opacities, const float *scales,
                                const float *rotations, float *image, int32_t *radii, void *geom, void *binning,
-                               void *image_state, void *stream, bool pair)
+                               void *image_state, void *stream, bool pair, int src_kind = 0, const RasterSrc *src = nullptr)
 {
     if (int rc = check_settings(settings, P)) return rc;
     GSVC_REQUIRE(max_instances >= 0 && max_instances < (int64_t)1 << 31, "raster_forward: max_instances out of range");
@@ -1373,7 +1402,8 @@ static int raster_forward_impl(const gsvc_raster_settings *settings, int64_t P, 
         set_error("raster_forward_pair: not defined under GSVC_RASTER_SLAB_ONE_SIDED / GSVC_RASTER_PIXEL_CORNER (render the two views)");
         return GSVC_E_UNSUPPORTED;
     }
-    GSVC_REQUIRE(P == 0 || (means3D && colors && opacities && scales && rotations && radii),
+    GSVC_REQUIRE(P == 0 || (means3D && opacities && radii && ((src_kind & SRC_SH) || colors) &&
+                            ((src_kind & SRC_COV) || (scales && rotations))),
                  "raster_forward: NULL input pointer");
     const RasterParams p = make_params(*settings);
     const RasterLayout L = raster_layout(*settings, P, max_instances);
@@ -1405,15 +1435,25 @@ static int raster_forward_impl(const gsvc_raster_settings *settings, int64_t P, 
         const bool use_lds = L.tiles <= LDS_HIST_MAX_TILES;
         // the fused scan stages SCAN_CHUNK tile counts in the same LDS
         const size_t lds = use_lds ? (size_t)(L.tiles > SCAN_CHUNK ? L.tiles : SCAN_CHUNK) * sizeof(int) : 0;
-        auto launch = [&](auto kernel) {
+        auto launch = [&](auto kernel, auto... extra) {
             if (lds > 48 * 1024)
                 (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                           LDS_HIST_MAX_TILES * 4);
             hipLaunchKernelGGL(kernel, dim3(blocks), dim3(1024), lds, s, p, (int)P, means3D, colors, opacities, scales,
                                rotations, radii, grec, brec, tile_count, tile_extra, counters, tile_offsets, big_list, wg_extras,
-                               (long long)max_instances);
+                               (long long)max_instances, extra...);
         };
-        if (use_lds && pair) launch(&k_preprocess<true, true>);
+        if (src_kind) {        // (single view: checked by gsvc_raster_forward_ex)
+            const RasterSrc a = *src;
+            switch (src_kind | (use_lds ? 4 : 0)) {
+            case SRC_SH | 4: launch(&k_preprocess<true, false, SRC_SH, RasterSrc>, a); break;
+            case SRC_COV | 4: launch(&k_preprocess<true, false, SRC_COV, RasterSrc>, a); break;
+            case SRC_SH | SRC_COV | 4: launch(&k_preprocess<true, false, SRC_SH | SRC_COV, RasterSrc>, a); break;
+            case SRC_SH: launch(&k_preprocess<false, false, SRC_SH, RasterSrc>, a); break;
+            case SRC_COV: launch(&k_preprocess<false, false, SRC_COV, RasterSrc>, a); break;
+            default: launch(&k_preprocess<false, false, SRC_SH | SRC_COV, RasterSrc>, a); break;
+            }
+        } else if (use_lds && pair) launch(&k_preprocess<true, true>);
         else if (use_lds) launch(&k_preprocess<true, false>);
         else if (pair) launch(&k_preprocess<false, true>);
         else launch(&k_preprocess<false, false>);
@@ -1471,6 +1511,75 @@ extern "C" int gsvc_raster_forward(const gsvc_raster_settings *settings, int64_t
 {
     return raster_forward_impl(settings, P, max_instances, means3D, colors, opacities, scales, rotations, image, radii, geom,
                                binning, image_state, stream, false);
+}
+
+int gsvc::raster_sources_check(const char *fn, const float *colors, const float *scales, const float *rotations,
+                         const gsvc_raster_sources *sources, bool need_colour, RasterSrc &src, int &kind)
+{
+    src = RasterSrc{};
+    kind = 0;
+    const float *shs = sources ? sources->shs : nullptr;
+    const float *cov = sources ? sources->cov3D : nullptr;
+    if (need_colour) {
+        GSVC_REQUIRE((shs != nullptr) != (colors != nullptr), "%s: give exactly one of shs and colors (got %s)", fn,
+                     shs ? "both" : "neither");
+        if (shs) {
+            GSVC_REQUIRE(sources->sh_degree >= 0 && sources->sh_degree <= 3, "%s: sh_degree must be 0..3 (got %d)", fn,
+                         (int)sources->sh_degree);
+            const int need = (sources->sh_degree + 1) * (sources->sh_degree + 1);
+            GSVC_REQUIRE(sources->sh_coeffs >= need && sources->sh_coeffs <= (1 << 20),
+                         "%s: sh_coeffs (%d) must be >= (sh_degree+1)^2 = %d", fn, (int)sources->sh_coeffs, need);
+            kind |= SRC_SH;
+            src.shs = shs;
+            src.sh_degree = sources->sh_degree;
+            src.sh_coeffs = sources->sh_coeffs;
+            for (int c = 0; c < 3; c++) src.campos[c] = sources->campos[c];
+        }
+    }
+    const bool sr = scales != nullptr && rotations != nullptr;
+    GSVC_REQUIRE((cov != nullptr) != sr, "%s: give exactly one of cov3D and scales + rotations (got %s)", fn,
+                 cov ? "both" : "neither");
+    if (cov) {
+        GSVC_REQUIRE(((uintptr_t)cov & 7u) == 0, "%s: cov3D must be 8-byte aligned", fn);
+        kind |= SRC_COV;
+        src.cov3D = cov;
+    }
+    return GSVC_OK;
+}
+
+extern "C" int gsvc_raster_visible_filter_ex(const gsvc_raster_settings *settings, int64_t P, const float *means3D,
+                                             const float *scales, const float *rotations, const gsvc_raster_sources *sources,
+                                             int32_t *radii, void *stream)
+{
+    if (int rc = check_settings(settings, P)) return rc;
+    RasterSrc src;
+    int kind;
+    if (int rc = raster_sources_check("visible_filter_ex", nullptr, scales, rotations, sources, false, src, kind)) return rc;
+    if (!kind) return gsvc_raster_visible_filter(settings, P, means3D, scales, rotations, radii, stream);
+    if (P == 0) return GSVC_OK;
+    GSVC_REQUIRE(means3D && radii, "visible_filter_ex: NULL pointer");
+    const RasterParams p = make_params(*settings);
+    hipStream_t s = (hipStream_t)stream;
+    {
+        ProfScope _prof("k_visible_filter", s);
+        hipLaunchKernelGGL(k_visible_filter_cov, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, p, (int)P, means3D,
+                           src.cov3D, radii);
+    }
+    return check_launch("visible_filter_ex");
+}
+
+extern "C" int gsvc_raster_forward_ex(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
+                                      const float *means3D, const float *colors, const float *opacities,
+                                      const float *scales, const float *rotations, const gsvc_raster_sources *sources,
+                                      float *image, int32_t *radii, void *geom, void *binning, void *image_state, void *stream)
+{
+    if (int rc = check_settings(settings, P)) return rc;
+    RasterSrc src;
+    int kind;
+    if (int rc = raster_sources_check("raster_forward_ex", colors, scales, rotations, sources, true, src, kind)) return rc;
+    src.sh_vec = (src.sh_coeffs % 4 == 0 && ((uintptr_t)src.shs & 15u) == 0) ? 1 : 0;
+    return raster_forward_impl(settings, P, max_instances, means3D, colors, opacities, scales, rotations, image, radii, geom,
+                               binning, image_state, stream, false, kind, &src);
 }
 
 extern "C" int gsvc_raster_forward_pair(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,

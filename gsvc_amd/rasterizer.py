@@ -12,9 +12,20 @@ Mirrors the surface GSVC uses:
   * an autograd node: ``means2D.grad`` receives the screen-space gradient (renderer.py:37-42,
     scene/gaussian_model.py:1311).
 
-Error behaviour follows the 3DGS lineage: missing scales/rotations, or both/neither of shs and
-colors_precomp, raise ``Exception``; shs and cov3D_precomp are not used by GSVC (it always passes
-colors_precomp / scales+rotations) and raise NotImplementedError here.
+Both colour sources and both covariance sources of the lineage are built:
+  * ``shs`` [P, K, 3] (with ``colors_precomp=None``): colours from the real spherical harmonics of degree
+    ``raster_settings.sh_degree`` (0..3, (degree+1)^2 <= K) evaluated in the kernel at
+    dir = normalize(means3D - raster_settings.campos), or at the view's constant axis under
+    ``flags & GSVC_RASTER_SH_VIEW_AXIS`` (DESIGN.md "Raster spec"); the backward returns dL/dshs and adds the
+    gradient through dir to dL/dmeans3D;
+  * ``cov3D_precomp`` [P, 6] = xx, xy, xz, yy, yz, zz (with ``scales``/``rotations`` None), used as given
+    (``scale_modifier`` is not applied, as in the lineage); the backward returns dL/dcov3D_precomp.
+GSVC itself always passes colors_precomp + scales/rotations: that call keeps the original entry points
+(gsvc_raster_forward / _backward); only a call with shs or cov3D_precomp takes the gsvc_raster_*_ex ones.
+
+Error behaviour follows the 3DGS lineage: both/neither of shs and colors_precomp, or of scales/rotations
+and cov3D_precomp, raise ``Exception``.  SH colours are single-view only (not in raster_forward(pair=True) /
+rasterize_many).
 """
 from __future__ import annotations
 
@@ -134,12 +145,14 @@ _capacity_hint = {}
 
 
 def raster_forward(cs: _lib.RasterSettingsC, means3D, colors, opacities, scales, rotations, max_instances=None,
-                   sync=True, pair=False, readback=False, radii_out=None, side_stream=None):
+                   sync=True, pair=False, readback=False, radii_out=None, side_stream=None, sources=None):
     """Launch the forward pipeline.  Returns (image, radii, state).  With ``sync`` the instance counters
     are read back (16 B) and the call is repeated with a larger instance capacity if it overflowed; without
     it the caller must check ``state.counters()[1]`` itself (``readback``: the counters' copy to the host is queued right
     behind the forward, for resolve_deferred()).  ``pair=True`` returns the two-view frame
-    (render(view) + flip(render(opposite view))) / 2 from one pass (inference only, see gsvc_raster_forward_pair)."""
+    (render(view) + flip(render(opposite view))) / 2 from one pass (inference only, see gsvc_raster_forward_pair).
+    ``sources`` (a RasterSourcesC: SH colours and / or a precomputed covariance, single view only) selects
+    gsvc_raster_forward_ex; ``colors`` / ``scales`` + ``rotations`` are then None where it replaces them."""
     L = _lib.lib()
     P = int(means3D.shape[0])
     dev = means3D.device
@@ -158,11 +171,19 @@ def raster_forward(cs: _lib.RasterSettingsC, means3D, colors, opacities, scales,
         image_state = torch.empty(sizes.image_bytes, dtype=torch.uint8, device=dev)
         image = torch.empty(3, H, W, dtype=torch.float32, device=dev)
         radii = radii_out if radii_out is not None else torch.empty(P, dtype=torch.int32, device=dev)
-        fn = L.gsvc_raster_forward_pair if pair else L.gsvc_raster_forward
-        _lib.check(fn(C.byref(cs), P, max_instances, _lib.ptr(means3D), _lib.ptr(colors),
-                                         _lib.ptr(opacities), _lib.ptr(scales), _lib.ptr(rotations), _lib.ptr(image),
-                                         _lib.ptr(radii), _lib.ptr(geom), _lib.ptr(binning), _lib.ptr(image_state), stream),
-                   "gsvc_raster_forward")
+        if sources is not None:
+            if pair:
+                raise ValueError("raster_forward: SH colours / cov3D_precomp serve the single-view forward only")
+            _lib.check(L.gsvc_raster_forward_ex(C.byref(cs), P, max_instances, _lib.ptr(means3D), _lib.ptr(colors),
+                                                _lib.ptr(opacities), _lib.ptr(scales), _lib.ptr(rotations), C.byref(sources),
+                                                _lib.ptr(image), _lib.ptr(radii), _lib.ptr(geom), _lib.ptr(binning),
+                                                _lib.ptr(image_state), stream), "gsvc_raster_forward_ex")
+        else:
+            fn = L.gsvc_raster_forward_pair if pair else L.gsvc_raster_forward
+            _lib.check(fn(C.byref(cs), P, max_instances, _lib.ptr(means3D), _lib.ptr(colors),
+                                             _lib.ptr(opacities), _lib.ptr(scales), _lib.ptr(rotations), _lib.ptr(image),
+                                             _lib.ptr(radii), _lib.ptr(geom), _lib.ptr(binning), _lib.ptr(image_state), stream),
+                       "gsvc_raster_forward")
         state = RasterState(cs, P, max_instances, geom, binning, image_state, radii)
         if not sync and readback:
             # the counters are final once the forward kernels have run: their 16 bytes start travelling to the host
@@ -243,6 +264,59 @@ class _RasterizeGaussians(torch.autograd.Function):
             _lib.ptr(st.image_state), _lib.ptr(g), _lib.ptr(d3), _lib.ptr(d2), _lib.ptr(dc), _lib.ptr(do), _lib.ptr(ds),
             _lib.ptr(dq), _lib.ptr(scratch), _lib.current_stream(dev)), "gsvc_raster_backward")
         return d3, d2, dc, do, ds, dq, None, None, None
+
+
+def _sources_c(shs, sh_degree, campos, cov3D):
+    """gsvc_raster_sources for the tensors given (None: that source is not used)."""
+    src = _lib.RasterSourcesC()
+    src.shs, src.cov3D = _lib.ptr(shs), _lib.ptr(cov3D)
+    if shs is not None:
+        src.sh_degree, src.sh_coeffs = int(sh_degree), int(shs.shape[1])
+        src.campos[:] = list(campos)
+    return src
+
+
+class _RasterizeGaussiansEx(torch.autograd.Function):
+    """The rasterization with SH colours and / or a precomputed 3-D covariance (gsvc_raster_forward_ex / _backward_ex).  The
+    plain call (colors_precomp + scales / rotations) stays on _RasterizeGaussians."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, colors, opacities, scales, rotations, shs, cov3D, cs, sh_degree, campos, holder, sync=True):
+        f32 = lambda t, name: None if t is None else _as_f32(t, name)
+        means3D, colors, opacities = _as_f32(means3D, "means3D"), f32(colors, "colors_precomp"), _as_f32(opacities, "opacities")
+        scales, rotations, shs, cov3D = f32(scales, "scales"), f32(rotations, "rotations"), f32(shs, "shs"), f32(cov3D, "cov3D_precomp")
+        if shs is not None and (shs.dim() != 3 or shs.shape[0] != means3D.shape[0] or shs.shape[2] != 3):
+            raise ValueError(f"shs must be [P, coefficients, 3], got {tuple(shs.shape)}")
+        if cov3D is not None and tuple(cov3D.shape) != (means3D.shape[0], 6):
+            raise ValueError(f"cov3D_precomp must be [P, 6], got {tuple(cov3D.shape)}")
+        src = _sources_c(shs, sh_degree, campos, cov3D)
+        image, radii, state = raster_forward(cs, means3D, colors, opacities, scales, rotations, sync=sync, readback=not sync,
+                                             sources=src)
+        ctx.state, ctx.src = state, src
+        ctx.save_for_backward(means3D, colors, opacities, scales, rotations, shs, cov3D)
+        ctx.mark_non_differentiable(radii)
+        holder["state"] = state
+        return image, radii
+
+    @staticmethod
+    def backward(ctx, grad_image, _grad_radii):
+        means3D, colors, opacities, scales, rotations, shs, cov3D = ctx.saved_tensors
+        st = ctx.state
+        P = st.P
+        dev = means3D.device
+        g = _as_f32(grad_image, "grad_image")
+        d3, d2, dc = torch.empty(P, 3, device=dev), torch.empty(P, 3, device=dev), torch.empty(P, 3, device=dev)
+        do, ds, dq = torch.empty(P, 1, device=dev), torch.empty(P, 3, device=dev), torch.empty(P, 4, device=dev)
+        dsh = torch.empty_like(shs) if shs is not None else None
+        dcov = torch.empty(P, 6, device=dev) if cov3D is not None else None
+        scratch = torch.empty(backward_scratch_floats(P, st.max_instances), device=dev)
+        _lib.check(_lib.lib().gsvc_raster_backward_ex(
+            C.byref(st.cs), P, st.max_instances, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(opacities), _lib.ptr(scales),
+            _lib.ptr(rotations), C.byref(ctx.src), _lib.ptr(st.radii), _lib.ptr(st.geom), _lib.ptr(st.binning),
+            _lib.ptr(st.image_state), _lib.ptr(g), _lib.ptr(d3), _lib.ptr(d2), _lib.ptr(dc), _lib.ptr(do), _lib.ptr(ds),
+            _lib.ptr(dq), _lib.ptr(dsh), _lib.ptr(dcov), _lib.ptr(scratch), _lib.current_stream(dev)), "gsvc_raster_backward_ex")
+        return (d3, d2, dc if colors is not None else None, do, ds if scales is not None else None,
+                dq if rotations is not None else None, dsh, dcov, None, None, None, None, None)
 
 
 _SIDE = {}
@@ -352,17 +426,41 @@ class GaussianRasterizer(nn.Module):
         self._cs = None
         self.last_state: Optional[RasterState] = None
         self.deferred = False   # True: forward() does not read the counters back (third return value = RasterState)
+        self._campos_host = None
 
     def _c_settings(self):
         if self._cs is None:
             self._cs = settings_to_c(self.raster_settings)
         return self._cs
 
+    def _campos(self):
+        """settings.campos as three host floats (read once: a tensor on the GPU costs a synchronising copy)."""
+        if self._campos_host is None:
+            rs = self.raster_settings
+            if rs.campos is None:
+                if not (int(getattr(rs, "flags", 0)) & _lib.RASTER_SH_VIEW_AXIS):
+                    raise ValueError("SH colours need raster_settings.campos (or flags & GSVC_RASTER_SH_VIEW_AXIS)")
+                self._campos_host = (0.0, 0.0, 0.0)
+            else:
+                self._campos_host = tuple(float(v) for v in _host_floats(rs.campos, 3))
+        return self._campos_host
+
     def visible_filter(self, means3D, scales=None, rotations=None, cov3D_precomp=None):
-        if cov3D_precomp is not None:
-            raise NotImplementedError("cov3D_precomp is not used by GSVC (pipe.compute_cov3D_python is False)")
-        if scales is None or rotations is None:
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
+        if cov3D_precomp is not None:
+            with torch.no_grad():
+                m, cov = _as_f32(means3D, "means3D"), _as_f32(cov3D_precomp, "cov3D_precomp")
+                P = int(m.shape[0])
+                if tuple(cov.shape) != (P, 6):
+                    raise ValueError(f"cov3D_precomp must be [P, 6], got {tuple(cov.shape)}")
+                radii = torch.empty(P, dtype=torch.int32, device=m.device)
+                src = _sources_c(None, 0, None, cov)
+                _lib.check(_lib.lib().gsvc_raster_visible_filter_ex(C.byref(self._c_settings()), P, _lib.ptr(m), None, None,
+                                                                    C.byref(src), _lib.ptr(radii), _lib.current_stream(m.device)),
+                           "gsvc_raster_visible_filter_ex")
+            return radii
         with torch.no_grad():
             m, s, q = _as_f32(means3D, "means3D"), _as_f32(scales, "scales"), _as_f32(rotations, "rotations")
             P = int(m.shape[0])
@@ -376,15 +474,18 @@ class GaussianRasterizer(nn.Module):
                 cov3D_precomp=None):
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
-        if shs is not None:
-            raise NotImplementedError("SH colours are not used by GSVC (sh_degree=0, colors_precomp always given)")
-        if cov3D_precomp is not None:
-            raise NotImplementedError("cov3D_precomp is not used by GSVC")
-        if scales is None or rotations is None:
+        if ((scales is None or rotations is None) and cov3D_precomp is None) or \
+                ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         holder = {}
-        image, radii = _RasterizeGaussians.apply(means3D, means2D, colors_precomp, opacities, scales, rotations,
-                                                 self._c_settings(), holder, not self.deferred)
+        if shs is None and cov3D_precomp is None:
+            image, radii = _RasterizeGaussians.apply(means3D, means2D, colors_precomp, opacities, scales, rotations,
+                                                     self._c_settings(), holder, not self.deferred)
+        else:
+            campos = self._campos() if shs is not None else None
+            image, radii = _RasterizeGaussiansEx.apply(means3D, means2D, colors_precomp, opacities, scales, rotations, shs,
+                                                       cov3D_precomp, self._c_settings(), int(self.raster_settings.sh_degree),
+                                                       campos, holder, not self.deferred)
         self.last_state = holder["state"]
         if self.deferred:      # counters stay on the device: the caller resolves them with resolve_deferred()
             return image, radii, self.last_state

@@ -13,11 +13,12 @@
  *                                                    call sites reference utils/encodings.py:529-553,582-610
  *   utils/entropy_models.py EntropyGaussian (+Low_bound)           reference utils/entropy_models.py:32-68,159-175
  *
- * TWO KINDS OF ENTRY POINTS.  A maintainer who swaps GSVC's native extensions for this library binds the FIFTEEN marked
+ * TWO KINDS OF ENTRY POINTS.  A maintainer who swaps GSVC's native extensions for this library binds the EIGHTEEN marked
  * [BOUNDARY] — they have the shape of the calls GSVC makes today — and can ignore the rest:
  *
  *   rasterizer   gsvc_raster_sizes_query, gsvc_raster_visible_filter, gsvc_raster_forward, gsvc_raster_backward_scratch_bytes,
  *                gsvc_raster_backward   (+ gsvc_raster_forward_pair: the decoder's two-view frame of report_utils.py:297-319 in one pass)
+ *                (+ gsvc_raster_{visible_filter,forward,backward}_ex: SH colours / precomputed 3-D covariances)
  *   hash grid    gsvc_grid_forward, gsvc_grid_backward                      (= grid_encode_forward / grid_encode_backward)
  *   rate         gsvc_rate_forward, gsvc_rate_backward                      (= EntropyGaussian.forward + Low_bound's backward)
  *   codec        gsvc_ans_segments, gsvc_ans_scratch_bytes, gsvc_ans_encode, gsvc_ans_decode_scratch_bytes, gsvc_ans_decode
@@ -75,8 +76,8 @@ int gsvc_profile_collect(char *names_out_host, int32_t *launches_out_host, float
  * ---------------------------------------------------------------------------------------------------- */
 
 /* Fields of GaussianRasterizationSettings the extension reads (reference renderer.py:63-83).
- * sh_degree / campos / prefiltered / debug carry no information for the colours_precomp path and are
- * not part of the ABI.  viewmatrix is the LOGICAL 4x4 the reference passes (`frame.view_matrix.permute(1,0)`),
+ * sh_degree / campos are read only when SH colours are given: they travel in gsvc_raster_sources, the argument of the
+ * *_ex entry points, and are not part of this struct; prefiltered / debug carry no information and are not part of the ABI.  viewmatrix is the LOGICAL 4x4 the reference passes (`frame.view_matrix.permute(1,0)`),
  * row-major: p_view = M[:3,:3] p + M[:3,3]. */
 typedef struct gsvc_raster_settings {
     int32_t image_height;
@@ -108,6 +109,9 @@ typedef struct gsvc_raster_settings {
                                                anyway): same image, radii, num_rendered (still the 3-sigma count) and gradients (up to
                                                the order large rectangles' rows are added in), shorter lists — late in a fit 40 % of the
                                                3-sigma instances are such.  The pair forward clamps both views' rectangles by the (shared) box */
+#define GSVC_RASTER_SH_VIEW_AXIS 128u       /* SH colours (gsvc_raster_sources.shs) are evaluated at the view's constant axis
+                                               dir = normalize(viewmatrix[2][0..2]) (world direction of view-space +z) instead of
+                                               dir = normalize(p_world - campos); no gradient reaches means3D through dir then */
 
 /* Byte sizes of the three opaque state blobs of one forward call (the 3DGS-lineage "geomBuffer /
  * binningBuffer / imgBuffer" the reference extension hands back to autograd). */
@@ -177,6 +181,40 @@ int gsvc_raster_backward(const gsvc_raster_settings *settings, int64_t P, int64_
                          const void *image_state, const float *dL_dimage, float *dL_dmeans3D, float *dL_dmeans2D,
                          float *dL_dcolors, float *dL_dopacities, float *dL_dscales, float *dL_drotations,
                          void *scratch, void *stream);
+
+/* Optional inputs of the 3DGS-lineage rasterizer call the _ex entry points below complete: GaussianRasterizer(shs=...,
+ * cov3D_precomp=...) and visible_filter(cov3D_precomp=...) of diff_gaussian_rasterization (reference
+ * ortho_gaussian_renderer/renderer.py:85-98, preprocess.py:99-104, arguments/__init__.py:130-131). */
+typedef struct gsvc_raster_sources {
+    const float *shs;        /* [P, sh_coeffs, 3] or NULL (then `colors` is read) */
+    int32_t sh_degree;       /* active degree 0..3; (sh_degree+1)^2 <= sh_coeffs */
+    int32_t sh_coeffs;       /* row stride of shs in coefficients (the lineage passes shs.shape[1]) */
+    float campos[3];
+    const float *cov3D;      /* [P, 6] = xx, xy, xz, yy, yz, zz, or NULL (then scales/rotations are read) */
+} gsvc_raster_sources;
+
+/* [BOUNDARY] The forms of gsvc_raster_visible_filter / _forward / _backward that take gsvc_raster_sources.  Exactly one colour
+ * source (colors or sources->shs) and exactly one covariance source (scales + rotations, or sources->cov3D) must be given; the
+ * unused pointers are NULL.  SH colours: colour = max(sum_k basis_k(dir) sh[k] + 0.5, 0) per channel over the (sh_degree+1)^2
+ * real spherical-harmonic functions of the 3DGS lineage, dir as GSVC_RASTER_SH_VIEW_AXIS says.  A precomputed covariance is
+ * used as given (scale_modifier is not applied to it, as in the lineage).  Single view only (no _pair form). */
+int gsvc_raster_visible_filter_ex(const gsvc_raster_settings *settings, int64_t P, const float *means3D,
+                                  const float *scales, const float *rotations, const gsvc_raster_sources *sources,
+                                  int32_t *radii, void *stream);
+int gsvc_raster_forward_ex(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
+                           const float *means3D, const float *colors, const float *opacities, const float *scales,
+                           const float *rotations, const gsvc_raster_sources *sources, float *image, int32_t *radii,
+                           void *geom, void *binning, void *image_state, void *stream);
+/* As gsvc_raster_backward, plus dL_dshs[P, sh_coeffs, 3] (coefficients beyond the active degree get 0) and dL_dcov3D[P, 6] (the
+ * gradient with respect to the six stored numbers: an off-diagonal one carries both symmetric entries), each may be NULL.
+ * With cov3D, dL_dscales / dL_drotations are zero; with shs, dL_dmeans3D includes the term through dir (default convention). */
+int gsvc_raster_backward_ex(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
+                            const float *means3D, const float *colors, const float *opacities, const float *scales,
+                            const float *rotations, const gsvc_raster_sources *sources, const int32_t *radii,
+                            const void *geom, const void *binning, const void *image_state, const float *dL_dimage,
+                            float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities,
+                            float *dL_dscales, float *dL_drotations, float *dL_dshs, float *dL_dcov3D, void *scratch,
+                            void *stream);
 
 /* Test/inspection helpers: locate the sorted per-tile lists inside the binning blob.
  * tile_offsets_host_out: byte offset of int32 tile_offsets[T+1]; point_list: byte offset of int32 ids. */

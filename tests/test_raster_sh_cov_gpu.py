@@ -1,0 +1,355 @@
+"""GPU tests of the rasterizer's optional sources: SH colours (``shs``) and precomputed 3-D covariances (``cov3D_precomp``),
+forward and backward, through GaussianRasterizer and the gsvc_raster_*_ex entry points.
+
+Bars: a cov3D computed in float32 in the kernel's order gives bit-identical radii / tile lists / num_rendered; pixels within
+1e-4; gradients within test_raster_gpu's relative-to-scale bar against the CPU oracle fed with the same colours, pulled back
+through an independent torch statement of the SH basis (or of the covariance construction) by autograd."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+from gsvc_amd import _lib, synthetic
+from tests._dense_raster import dense_render
+from tests.test_raster_gpu import PIX_TOL, _grad_close, _oracle_settings, _to_dev
+
+pytestmark = pytest.mark.gpu
+
+TIGHT, ONE_SIDED, CORNER, VIEW_AXIS = 64, 1, 2, 128
+
+
+def _rasterizer(s, view="viewmatrix", flags=0, sh_degree=0, campos=None, bg=None):
+    from gsvc_amd.rasterizer import GaussianRasterizationSettings, GaussianRasterizer
+    rs = GaussianRasterizationSettings(
+        image_height=s["H"], image_width=s["W"], x_min=s["x_min"], y_min=s["y_min"], scale=s["scale"],
+        threshold=s["threshold"], bg=torch.tensor(bg if bg is not None else s["bg"], dtype=torch.float32),
+        scale_modifier=s["scale_modifier"], viewmatrix=torch.tensor(s[view]), sh_degree=sh_degree,
+        campos=None if campos is None else torch.tensor(campos, dtype=torch.float32), prefiltered=False, debug=False,
+        flags=flags)
+    return GaussianRasterizer(raster_settings=rs)
+
+
+def _scene(P, H, W, seed, scale_modifier=1.0):
+    sc = synthetic.raster_scene(P, H=H, W=W, T=64, seed=seed, window_frames=8, sigma_px=(0.5, 6.0))
+    sc["settings"]["scale_modifier"] = scale_modifier
+    return sc
+
+
+# ------------------------------------------------------------------ independent statements of the two new inputs
+def cov3d_kernel_order_np(scales, rotations, scale_modifier):
+    """[P, 6] float32 covariance in preprocess_gaussian's operation order (no FMA: numpy rounds every operation)."""
+    f = np.float32
+    s = scales.astype(f) * f(scale_modifier)
+    q = rotations.astype(f)
+    qr, qx, qy, qz = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    one, two = f(1), f(2)
+    R = [[one - two * (qy * qy + qz * qz), two * (qx * qy - qr * qz), two * (qx * qz + qr * qy)],
+         [two * (qx * qy + qr * qz), one - two * (qx * qx + qz * qz), two * (qy * qz - qr * qx)],
+         [two * (qx * qz - qr * qy), two * (qy * qz + qr * qx), one - two * (qx * qx + qy * qy)]]
+    L = [[R[r][c] * s[:, c] for c in range(3)] for r in range(3)]
+
+    def dot(a, b):
+        return L[a][0] * L[b][0] + L[a][1] * L[b][1] + L[a][2] * L[b][2]
+    return np.stack([dot(0, 0), dot(0, 1), dot(0, 2), dot(1, 1), dot(1, 2), dot(2, 2)], axis=1).astype(f)
+
+
+def cov3d_torch(scales, rotations, scale_modifier):
+    """[P, 6] from (scales, quaternions) with torch ops (differentiable), Sigma = R S S^T R^T."""
+    r, x, y, z = rotations.unbind(1)
+    R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - r * z), 2 * (x * z + r * y),
+                     2 * (x * y + r * z), 1 - 2 * (x * x + z * z), 2 * (y * z - r * x),
+                     2 * (x * z - r * y), 2 * (y * z + r * x), 1 - 2 * (x * x + y * y)], dim=1).view(-1, 3, 3)
+    Lm = R * (scales * scale_modifier)[:, None, :]
+    S = Lm @ Lm.transpose(1, 2)
+    return torch.stack([S[:, 0, 0], S[:, 0, 1], S[:, 0, 2], S[:, 1, 1], S[:, 1, 2], S[:, 2, 2]], dim=1)
+
+
+def sh_basis_torch(d):
+    """The 16 real spherical harmonics of degree <= 3 (3DGS-lineage order and signs) at unit directions d [P, 3]."""
+    x, y, z = d.unbind(1)
+    pi = math.pi
+    k1 = math.sqrt(3 / (4 * pi))
+    return torch.stack([
+        torch.full_like(x, 0.5 * math.sqrt(1 / pi)),
+        -k1 * y, k1 * z, -k1 * x,
+        0.5 * math.sqrt(15 / pi) * x * y,
+        -0.5 * math.sqrt(15 / pi) * y * z,
+        0.25 * math.sqrt(5 / pi) * (2 * z * z - x * x - y * y),
+        -0.5 * math.sqrt(15 / pi) * x * z,
+        0.25 * math.sqrt(15 / pi) * (x * x - y * y),
+        -0.25 * math.sqrt(35 / (2 * pi)) * y * (3 * x * x - y * y),
+        0.5 * math.sqrt(105 / pi) * x * y * z,
+        -0.25 * math.sqrt(21 / (2 * pi)) * y * (4 * z * z - x * x - y * y),
+        0.25 * math.sqrt(7 / pi) * z * (2 * z * z - 3 * x * x - 3 * y * y),
+        -0.25 * math.sqrt(21 / (2 * pi)) * x * (4 * z * z - x * x - y * y),
+        0.25 * math.sqrt(105 / pi) * z * (x * x - y * y),
+        -0.25 * math.sqrt(35 / (2 * pi)) * x * (x * x - 3 * y * y)], dim=1)
+
+
+def sh_dirs_torch(means, campos, viewmatrix, flags):
+    if flags & VIEW_AXIS:
+        a = torch.as_tensor(np.asarray(viewmatrix)[2, :3], dtype=means.dtype, device=means.device)
+        return (a / a.norm()).expand(means.shape[0], 3)
+    d = means - torch.as_tensor(campos, dtype=means.dtype, device=means.device)
+    return d / d.norm(dim=1, keepdim=True)
+
+
+def sh_colours_torch(shs, dirs, degree):
+    """(clamped colours [P, 3], raw sums + 0.5 [P, 3])."""
+    n = (degree + 1) ** 2
+    raw = (sh_basis_torch(dirs)[:, :n, None] * shs[:, :n, :]).sum(1) + 0.5
+    return torch.clamp_min(raw, 0.0), raw
+
+
+def _campos(sc):
+    m = sc["means3D"]
+    s = sc["settings"]
+    return (float(m[:, 0].mean() + 0.3 * m[:, 0].std()), float(m[:, 1].mean() - 0.2 * m[:, 1].std()),
+            float(s["z_cam"] - 3.0 * s["threshold"]))
+
+
+def _shs(P, coeffs, seed):
+    rng = np.random.default_rng(seed)
+    shs = (rng.standard_normal((P, coeffs, 3)) * 0.6).astype(np.float32)
+    shs[:, 0, :] = rng.normal(0.0, 2.0, (P, 3))         # DC spread so that a good share of the channels clamp
+    return shs
+
+
+# ------------------------------------------------------------------ 1. covariance forward
+@pytest.mark.parametrize("flags", [0, TIGHT, ONE_SIDED | CORNER])
+@pytest.mark.parametrize("view", ["viewmatrix", "viewmatrix_s"])
+def test_cov3d_forward_is_bit_exact_with_scale_rotation(flags, view):
+    sc = _scene(4000, 256, 256, seed=11, scale_modifier=1.3)
+    s = sc["settings"]
+    d = _to_dev(sc)
+    cov = torch.tensor(cov3d_kernel_order_np(sc["scales"], sc["rotations"], s["scale_modifier"]), device="cuda")
+    r = _rasterizer(s, view, flags)
+    m2 = torch.zeros_like(d["means3D"])
+    img_a, radii_a, n_a = r(means3D=d["means3D"], means2D=m2, colors_precomp=d["colors"], opacities=d["opacities"],
+                            scales=d["scales"], rotations=d["rotations"])
+    off_a, pl_a = (t.clone() for t in r.last_state.tile_lists())
+    img_b, radii_b, n_b = r(means3D=d["means3D"], means2D=m2, colors_precomp=d["colors"], opacities=d["opacities"],
+                            cov3D_precomp=cov)
+    off_b, pl_b = r.last_state.tile_lists()
+    assert (radii_a > 0).sum() > 100
+    assert n_a == n_b
+    assert torch.equal(radii_a, radii_b)
+    assert torch.equal(off_a, off_b) and torch.equal(pl_a, pl_b)
+    assert (img_a - img_b).abs().max().item() < PIX_TOL
+    vf_a = r.visible_filter(means3D=d["means3D"], scales=d["scales"], rotations=d["rotations"])
+    vf_b = r.visible_filter(means3D=d["means3D"], cov3D_precomp=cov)
+    assert torch.equal(vf_a, vf_b)
+
+
+# ------------------------------------------------------------------ 2. covariance backward
+@pytest.mark.parametrize("P,H,W,seed,view", [(400, 64, 96, 0, "viewmatrix"), (5000, 256, 256, 1, "viewmatrix_s")])
+def test_cov3d_backward_matches_the_oracle_through_the_construction(oracle_lib, P, H, W, seed, view):
+    sc = _scene(P, H, W, seed, scale_modifier=0.9)
+    sc["opacities"][::9] = 0.0                      # some culled Gaussians whatever the scene
+    s = sc["settings"]
+    bg = (0.3, 0.1, 0.6)
+    os_ = _oracle_settings(oracle_lib, s, view, bg)
+    ref = oracle_lib.raster_forward(os_, sc["means3D"], sc["colors"], sc["opacities"], sc["scales"], sc["rotations"])
+    rng = np.random.default_rng(200 + seed)
+    dL = rng.standard_normal((3, H, W)).astype(np.float32)
+    dL[:, ref.borderline != 0] = 0
+    rb = oracle_lib.raster_backward(os_, sc["means3D"], sc["colors"], sc["opacities"], sc["scales"], sc["rotations"], ref, dL)
+    d = {k: v.requires_grad_(True) for k, v in _to_dev(sc).items()}
+    means2D = torch.zeros_like(d["means3D"], requires_grad=True)
+    cov = cov3d_torch(d["scales"], d["rotations"], s["scale_modifier"])
+    cov.retain_grad()
+    r = _rasterizer(s, view, bg=bg)
+    image, radii, _ = r(means3D=d["means3D"], means2D=means2D, colors_precomp=d["colors"], opacities=d["opacities"],
+                        cov3D_precomp=cov)
+    assert np.array_equal(radii.cpu().numpy(), ref.radii)
+    (image * torch.tensor(dL, device="cuda")).sum().backward()
+    _grad_close(d["scales"].grad.cpu().numpy(), rb.scales, "scales via cov3D")
+    _grad_close(d["rotations"].grad.cpu().numpy(), rb.rotations, "rotations via cov3D")
+    _grad_close(d["means3D"].grad.cpu().numpy(), rb.means3D, "means3D")
+    _grad_close(d["opacities"].grad.cpu().numpy(), rb.opacities, "opacities")
+    _grad_close(d["colors"].grad.cpu().numpy(), rb.colors, "colors")
+    _grad_close(means2D.grad.cpu().numpy(), rb.means2D, "means2D")
+    culled = torch.tensor(ref.radii == 0, device="cuda")
+    assert culled.any() and torch.all(cov.grad[culled] == 0)
+
+
+# ------------------------------------------------------------------ 3. SH forward
+SH_CASES = [(0, 1), (1, 4), (1, 5), (2, 9), (2, 16), (3, 16), (3, 20)]
+
+
+@pytest.mark.parametrize("degree,coeffs", SH_CASES)
+@pytest.mark.parametrize("flags", [0, VIEW_AXIS])
+def test_sh_forward_equals_precomputed_colours(degree, coeffs, flags):
+    sc = _scene(3000, 128, 192, seed=5 + degree)
+    s = sc["settings"]
+    d = _to_dev(sc)
+    P = sc["means3D"].shape[0]
+    campos = _campos(sc)
+    shs = torch.tensor(_shs(P, coeffs, seed=degree * 10 + coeffs), device="cuda")
+    col, raw = sh_colours_torch(shs, sh_dirs_torch(d["means3D"], campos, s["viewmatrix"], flags), degree)
+    assert (raw < 0).any() and (raw > 0).any()      # some channels clamp, others do not
+    r = _rasterizer(s, "viewmatrix", flags, sh_degree=degree, campos=campos)
+    m2 = torch.zeros_like(d["means3D"])
+    img_a, radii_a, n_a = r(means3D=d["means3D"], means2D=m2, colors_precomp=col.contiguous(), opacities=d["opacities"],
+                            scales=d["scales"], rotations=d["rotations"])
+    img_b, radii_b, n_b = r(means3D=d["means3D"], means2D=m2, shs=shs, opacities=d["opacities"], scales=d["scales"],
+                            rotations=d["rotations"])
+    assert (radii_a > 0).sum() > 100
+    assert n_a == n_b and torch.equal(radii_a, radii_b)
+    assert (img_a - img_b).abs().max().item() < PIX_TOL
+
+
+# ------------------------------------------------------------------ 4. SH backward
+@pytest.mark.parametrize("degree,coeffs", [(0, 1), (1, 5), (2, 9), (3, 16), (3, 20)])
+@pytest.mark.parametrize("flags", [0, VIEW_AXIS])
+def test_sh_backward_matches_the_oracle_through_the_basis(oracle_lib, degree, coeffs, flags):
+    sc = _scene(3000, 128, 192, seed=20 + degree)
+    s = sc["settings"]
+    P, H, W = sc["means3D"].shape[0], s["H"], s["W"]
+    bg = (0.2, 0.4, 0.1)
+    campos = _campos(sc)
+    shs_np = _shs(P, coeffs, seed=31 + degree)
+    # the independent statement, on the host in float64: colours, and the map (shs, means3D) -> colours for autograd
+    m64 = torch.tensor(sc["means3D"], dtype=torch.float64, requires_grad=True)
+    sh64 = torch.tensor(shs_np, dtype=torch.float64, requires_grad=True)
+    col64, raw64 = sh_colours_torch(sh64, sh_dirs_torch(m64, campos, s["viewmatrix"], flags), degree)
+    colours = col64.detach().numpy().astype(np.float32)
+    os_ = _oracle_settings(oracle_lib, s, "viewmatrix", bg)      # (the oracle has no SH: it is fed the colours)
+    ref = oracle_lib.raster_forward(os_, sc["means3D"], colours, sc["opacities"], sc["scales"], sc["rotations"])
+    rng = np.random.default_rng(300 + degree)
+    dL = rng.standard_normal((3, H, W)).astype(np.float32)
+    dL[:, ref.borderline != 0] = 0
+    rb = oracle_lib.raster_backward(os_, sc["means3D"], colours, sc["opacities"], sc["scales"], sc["rotations"], ref, dL)
+    g_sh, g_m = torch.autograd.grad(col64, [sh64, m64], grad_outputs=torch.tensor(rb.colors, dtype=torch.float64).view(P, 3),
+                                    allow_unused=True)
+    g_m = torch.zeros_like(m64) if g_m is None else g_m
+
+    d = {k: v.requires_grad_(True) for k, v in _to_dev(sc).items()}
+    shs = torch.tensor(shs_np, device="cuda", requires_grad=True)
+    means2D = torch.zeros_like(d["means3D"], requires_grad=True)
+    r = _rasterizer(s, "viewmatrix", flags, sh_degree=degree, campos=campos, bg=bg)
+    image, radii, _ = r(means3D=d["means3D"], means2D=means2D, shs=shs, opacities=d["opacities"], scales=d["scales"],
+                        rotations=d["rotations"])
+    assert np.array_equal(radii.cpu().numpy(), ref.radii)
+    assert np.abs(image.detach().cpu().numpy() - ref.image)[:, ref.borderline == 0].max() < PIX_TOL
+    (image * torch.tensor(dL, device="cuda")).sum().backward()
+    _grad_close(shs.grad.cpu().numpy(), g_sh.numpy(), f"shs d{degree}")
+    want_m = rb.means3D.reshape(P, 3) + g_m.numpy()
+    _grad_close(d["means3D"].grad.cpu().numpy(), want_m, "means3D (+ SH direction)")
+    if flags & VIEW_AXIS or degree == 0:             # (degree 0 is constant over the sphere)
+        assert not g_m.any()
+    else:
+        assert np.abs(g_m.numpy()).max() > 1e-3 * np.abs(rb.means3D).max()     # the direction term is really there
+    _grad_close(d["opacities"].grad.cpu().numpy(), rb.opacities, "opacities")
+    _grad_close(d["scales"].grad.cpu().numpy(), rb.scales, "scales")
+    _grad_close(d["rotations"].grad.cpu().numpy(), rb.rotations, "rotations")
+    _grad_close(means2D.grad.cpu().numpy(), rb.means2D, "means2D")
+    gs = shs.grad.cpu().numpy()
+    n = (degree + 1) ** 2
+    assert not gs[:, n:, :].any()                              # coefficients beyond the active degree
+    clamped = raw64.detach().numpy() < -1e-4                   # clamped channels pass nothing back
+    assert clamped.any()
+    for c in range(3):
+        assert not gs[clamped[:, c], :, c].any()
+    assert not gs[ref.radii == 0].any()
+
+
+def test_sh_backward_matches_dense_float64_autograd(oracle_lib):
+    sc = synthetic.raster_scene(30, H=40, W=56, T=32, seed=3, window_frames=8, sigma_px=(1.0, 5.0))
+    s = sc["settings"]
+    s["bg"] = (0.3, 0.1, 0.6)
+    P, degree = sc["means3D"].shape[0], 3
+    campos = _campos(sc)
+    shs_np = _shs(P, 16, seed=7)
+    m64 = torch.tensor(sc["means3D"], dtype=torch.float64, requires_grad=True)
+    sh64 = torch.tensor(shs_np, dtype=torch.float64, requires_grad=True)
+    col64, _ = sh_colours_torch(sh64, sh_dirs_torch(m64, campos, s["viewmatrix"], 0), degree)
+    os_ = _oracle_settings(oracle_lib, s)
+    fwd = oracle_lib.raster_forward(os_, sc["means3D"], col64.detach().numpy().astype(np.float32), sc["opacities"],
+                                    sc["scales"], sc["rotations"])
+    assert (fwd.radii > 0).sum() > 10
+    rng = np.random.default_rng(5)
+    dL = rng.standard_normal((3, s["H"], s["W"])).astype(np.float32)
+    dL[:, fwd.borderline != 0] = 0
+    t = {k: torch.tensor(sc[k].astype(np.float64)) for k in ("opacities", "scales", "rotations")}
+    img = dense_render(s, m64, col64, t["opacities"].view(-1), t["scales"], t["rotations"], fwd.radii)
+    (img * torch.tensor(dL.astype(np.float64))).sum().backward()
+
+    d = {k: v.requires_grad_(True) for k, v in _to_dev(sc).items()}
+    shs = torch.tensor(shs_np, device="cuda", requires_grad=True)
+    r = _rasterizer(s, sh_degree=degree, campos=campos)
+    image, radii, _ = r(means3D=d["means3D"], means2D=torch.zeros_like(d["means3D"]), shs=shs, opacities=d["opacities"],
+                        scales=d["scales"], rotations=d["rotations"])
+    assert np.abs(image.detach().cpu().numpy() - img.detach().numpy())[:, fwd.borderline == 0].max() < 1e-4
+    (image * torch.tensor(dL, device="cuda")).sum().backward()
+
+    def close(a, b, name):
+        a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+        assert np.allclose(a, b, rtol=2e-3, atol=2e-4 * max(1e-12, np.abs(b).max())), (name, np.abs(a - b).max(), np.abs(b).max())
+    close(shs.grad.cpu().numpy(), sh64.grad.numpy(), "shs")
+    close(d["means3D"].grad.cpu().numpy(), m64.grad.numpy(), "means3D")
+
+
+# ------------------------------------------------------------------ 5. repeatability and culling
+def test_sh_and_cov3d_gradients_repeat_bit_for_bit_and_culled_get_zeros():
+    sc = _scene(6000, 256, 256, seed=9)
+    s = sc["settings"]
+    sc["opacities"][::7] = 0.0                      # culled by opacity, besides those outside slab / screen
+    d = {k: v.requires_grad_(True) for k, v in _to_dev(sc).items()}
+    P = sc["means3D"].shape[0]
+    shs = torch.tensor(_shs(P, 16, seed=2), device="cuda", requires_grad=True)
+    cov = torch.tensor(cov3d_kernel_order_np(sc["scales"], sc["rotations"], 1.0), device="cuda", requires_grad=True)
+    r = _rasterizer(s, sh_degree=3, campos=_campos(sc))
+    dL = torch.randn(3, s["H"], s["W"], device="cuda", generator=torch.Generator("cuda").manual_seed(1))
+    grads = []
+    for _ in range(2):
+        for t in (shs, cov, d["means3D"]):
+            t.grad = None
+        image, radii, _ = r(means3D=d["means3D"], means2D=torch.zeros_like(d["means3D"]), shs=shs, opacities=d["opacities"],
+                            cov3D_precomp=cov)
+        (image * dL).sum().backward()
+        grads.append((shs.grad.clone(), cov.grad.clone(), d["means3D"].grad.clone()))
+    for a, b in zip(*grads):
+        assert torch.equal(a, b)
+    culled = radii == 0
+    assert culled.sum() > P // 7 and (~culled).sum() > 100
+    assert torch.all(grads[0][0][culled] == 0) and torch.all(grads[0][1][culled] == 0)
+    assert torch.all(grads[0][2][culled] == 0)
+    assert grads[0][0][~culled].abs().max() > 0 and grads[0][1][~culled].abs().max() > 0
+
+
+# ------------------------------------------------------------------ 6. the default path keeps its entry points
+def test_default_call_takes_the_existing_entry_points(monkeypatch):
+    sc = _scene(2000, 128, 128, seed=4)
+    s = sc["settings"]
+    d = {k: v.requires_grad_(True) for k, v in _to_dev(sc).items()}
+    L = _lib.lib()
+    calls = []
+
+    def spy(name):
+        fn = getattr(L, name)
+
+        def wrapped(*a):
+            calls.append(name)
+            return fn(*a)
+        monkeypatch.setattr(L, name, wrapped)
+    for name in ("gsvc_raster_forward", "gsvc_raster_backward", "gsvc_raster_forward_ex", "gsvc_raster_backward_ex",
+                 "gsvc_raster_visible_filter", "gsvc_raster_visible_filter_ex"):
+        spy(name)
+    r = _rasterizer(s, sh_degree=1, campos=_campos(sc))
+    image, _, _ = r(means3D=d["means3D"], means2D=torch.zeros_like(d["means3D"]), colors_precomp=d["colors"],
+                    opacities=d["opacities"], scales=d["scales"], rotations=d["rotations"])
+    image.sum().backward()
+    r.visible_filter(means3D=d["means3D"], scales=d["scales"], rotations=d["rotations"])
+    assert calls == ["gsvc_raster_forward", "gsvc_raster_backward", "gsvc_raster_visible_filter"]
+    calls.clear()
+    shs = torch.zeros(d["means3D"].shape[0], 4, 3, device="cuda", requires_grad=True)
+    image, _, _ = r(means3D=d["means3D"], means2D=torch.zeros_like(d["means3D"]), shs=shs, opacities=d["opacities"],
+                    scales=d["scales"], rotations=d["rotations"])
+    image.sum().backward()
+    assert calls == ["gsvc_raster_forward_ex", "gsvc_raster_backward_ex"]
+    # a zero SH row is the colour 0.5 in every channel
+    img_c, _, _ = r(means3D=d["means3D"], means2D=torch.zeros_like(d["means3D"]), opacities=d["opacities"],
+                    colors_precomp=torch.full_like(d["colors"], 0.5), scales=d["scales"], rotations=d["rotations"])
+    assert (image - img_c).abs().max().item() < PIX_TOL
