@@ -1295,9 +1295,15 @@ hipStream_t wgrad_stream_behind(hipStream_t s)
     constexpr int POOL = 32;
     static hipEvent_t pool[POOL];
     static int at = -1;
+    static bool disabled = false;      // the pool could not be made: the caller's stream from then on
+    if (disabled) return s;
     if (at < 0) {
         for (int i = 0; i < POOL; i++)
-            if (hipEventCreateWithFlags(&pool[i], hipEventDisableTiming) != hipSuccess) return s;
+            if (hipEventCreateWithFlags(&pool[i], hipEventDisableTiming) != hipSuccess) {
+                while (i-- > 0) hipEventDestroy(pool[i]);
+                disabled = true;
+                return s;
+            }
         at = 0;
     }
     hipEvent_t e = pool[at];

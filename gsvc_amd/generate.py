@@ -19,7 +19,7 @@ from enum import Enum
 
 import torch
 
-from . import switches
+from . import schedule, switches
 from .encodings import STE_multistep
 
 
@@ -394,7 +394,7 @@ class StepPlan:
     def resolve(self):
         """The one wait: cut the padded lists to their lengths."""
         if self.vis_list is None:
-            _blocked_wait(self._event)
+            schedule.blocked_wait(self._event)
             n = self._host.tolist()
             R, A = self.R, self._A
             if self._ends:                   # the fused scans report the scan at each view's end: counts are the differences
@@ -1004,102 +1004,6 @@ def _rate_many(pc, seg, feat, grid_scaling, grid_offsets, offset_masks, Q_feat, 
                      bit_per_offsets_param=per[r, 2]) for r in range(R)]
 
 
-_RATE_STREAM = {}
-SMALL_WORK_MIN_ROWS = 150_000      # visible anchor rows of a step from which the small-work stream is used: below, the step is
-                                   # host-bound (configs[3]: 58 k rows) and the extra events / stream switches only cost host time
-# ... unless the Trainer has MEASURED which side bounds its steps (round 5): the row count says nothing about the rasterizer's load, and
-# late in a fit a 100 k-anchor model (80 k rows) spends 7 ms per step on the GPU — its Gaussians cover 57 tiles each — while the host
-# needs 5.  The host only ever blocks at the step's two waits (the plan's counts, the renders' counters): what it blocks there per step
-# is the GPU's lead over it.  None = no measurement yet (the row count decides); set by gsvc_amd.train.Trainer.
-class StepContext:
-    """The measurement belongs to the Trainer that made it (as module globals two Trainers of one process clobbered
-    each other's): ``gpu_bound_hint`` (None = no measurement yet: the row count decides) and the seconds the host spent blocked in the
-    step's waits since its Trainer last read them.  A Trainer makes its own context current for the duration of each of its steps
-    (``step_context``); callers without a Trainer (render loops, tests) see the neutral default."""
-    __slots__ = ("gpu_bound_hint", "host_blocked_s", "flips")
-
-    def __init__(self):
-        self.gpu_bound_hint, self.host_blocked_s, self.flips = None, 0.0, 0
-
-
-_DEFAULT_CONTEXT = StepContext()
-step_context = _DEFAULT_CONTEXT
-
-
-def gpu_bound(rows) -> bool:
-    """Should this step spend host time (events, stream switches, separate launches) to save GPU time?"""
-    # (the measurement only ever ADDS steps to the GPU-bound side: a caller that synchronises every step — float(loss) — never lets the
-    # host block in the step's own waits, and must not lose what the row count alone already grants)
-    return rows >= SMALL_WORK_MIN_ROWS or bool(step_context.gpu_bound_hint)
-
-
-def _blocked_wait(event):
-    import time
-    t0 = time.perf_counter()
-    event.synchronize()
-    step_context.host_blocked_s += time.perf_counter() - t0
-
-
-def small_work_stream(dev):
-    """The stream on which a fitting step issues the small launch-bound pieces that do not read the rasterizer's output (the sampled
-    rate here, the regularisers / optical-flow term / table bits in gsvc_amd/train.py), so that they run under the compositing
-    kernels instead of in front of or behind them."""
-    rs = _RATE_STREAM.get(dev.index)
-    if rs is None:
-        rs = _RATE_STREAM[dev.index] = torch.cuda.Stream(device=dev)
-    return rs
-
-
-class two_stream_backward:
-    """Scope of a backward whose graph has nodes on the small-work stream: a parameter that both that stream's nodes and the step's
-    stream's nodes use gets its gradient from two streams — intended (the engine orders them), so the engine's warning about it
-    is switched off for the duration of THIS backward only (it was switched off process-wide at first use)."""
-
-    _depth = 0          # nested scopes (a backward inside a backward's hook): only the outermost one switches the warning back on
-
-    def __enter__(self):
-        self._set = getattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch", None)
-        if self._set is not None:
-            two_stream_backward._depth += 1
-            self._set(False)
-
-    def __exit__(self, *exc):
-        if self._set is not None:
-            two_stream_backward._depth -= 1
-            # torch offers a setter only (no getter to save the caller's choice): a caller who has switched the warning off for the
-            # whole process says so once with GSVC_KEEP_STREAM_WARNING_OFF=1 and this scope then leaves it off
-            if two_stream_backward._depth == 0 and not os.environ.get("GSVC_KEEP_STREAM_WARNING_OFF"):
-                self._set(True)
-
-
-def record_on(stream, *objs):
-    """``record_stream(stream)`` on every CUDA tensor in ``objs`` (tensors, lists / tuples of them, objects whose attributes hold
-    them; None is skipped).  A tensor allocated on the step's stream and READ on the small-work stream must tell the caching
-    allocator so: autograd releases saved tensors as soon as a node's backward is enqueued, and a block returned to the step's
-    pool while the other stream's kernel is still queued could be handed to — and overwritten by — the next main-stream kernel
-    (ADVICE round 4).  The allocator then holds the block back until the work queued on ``stream`` at the time of the free is done."""
-    seen = set()
-
-    def walk(o, depth):
-        if o is None or id(o) in seen:
-            return
-        seen.add(id(o))
-        if isinstance(o, torch.Tensor):
-            if o.is_cuda:
-                o.record_stream(stream)
-        elif isinstance(o, (list, tuple)):
-            for v in o:
-                walk(v, depth)
-        elif isinstance(o, dict):
-            for v in o.values():
-                walk(v, depth)
-        elif depth > 0 and hasattr(o, "__dict__") and not isinstance(o, torch.nn.Module):
-            for v in vars(o).values():
-                walk(v, depth - 1)
-    for o in objs:
-        walk(o, 1)
-
-
 def finish_deferred_rate(gss_list):
     """The sampled rate of a batched TRAINING_ENTROPY generation pass whose caller asked for it late (``defer_rate``): issued now —
     the caller has queued the rasterizer's launches — on a stream of its own that waits only for what the rate reads (the event
@@ -1114,9 +1018,9 @@ def finish_deferred_rate(gss_list):
     batch.deferred_rate = None
     dev = gss_list[0].xyz.device
     main = torch.cuda.current_stream(dev)
-    rs = small_work_stream(dev)
+    rs = schedule.small_work_stream(dev)
     rs.wait_event(ready)
-    record_on(rs, *reads)                    # allocated on this stream, read (and saved for a backward that runs) on that one
+    schedule.record_on(rs, *reads)           # allocated on this stream, read (and saved for a backward that runs) on that one
     with torch.cuda.stream(rs):
         packs = rate()
     main.wait_stream(rs)
@@ -1303,8 +1207,9 @@ def generate_neural_gaussians_many(frames, pc, visible_masks, mode=GenerateMode.
                 and plan is not None and plan.distinct is not None and plan.distinct.shape[0] != vis.shape[0] and not switches.NO_VIEW_SHARE):
             share = _film_rows(pc, frames, plan, vis, seg, anchor_all)
     from . import mlp as _mlp
-    # few rows: the step's time is the host's (SMALL_WORK_MIN_ROWS) -> the MLP layer launches prefer fewer, multi-product launches
-    _mlp.host_bound_step = bool(vis.is_cuda and torch.is_grad_enabled() and not gpu_bound(seg.rows) and "GSVC_MANY_MIN_ROWS" not in os.environ)
+    # the step's one "is the GPU the bound" decision: the rate deferral, the batch's small-work stream and the MLP launch forms follow it
+    bound = schedule.gpu_bound(seg.rows)
+    schedule.host_bound_step = bool(vis.is_cuda and torch.is_grad_enabled() and not bound and "GSVC_MANY_MIN_ROWS" not in os.environ)
     gens = [getattr(pc, n) for n in ("get_opacity_mlp", "get_color_mlp", "get_cov_mlp")]
     deform_mods = list(pc.get_deform_mlp) if isinstance(pc.get_deform_mlp, torch.nn.Sequential) else []
     deform_linears = deform_mods[0::2]
@@ -1423,23 +1328,12 @@ def generate_neural_gaussians_many(frames, pc, visible_masks, mode=GenerateMode.
                 return _rate_many(pc, seg, feat, grid_scaling, grid_offsets, offset_masks, Q_feat, Q_scaling, Q_offsets, ec, ec_row,
                                   sel=plan.sel if plan is not None else None)
         if (defer_rate and dense and late_rows and plan is not None and plan.sel is not None and vis.is_cuda
-                and gpu_bound(seg.rows) and not switches.NO_RATE_OVERLAP):
+                and bound and not switches.NO_RATE_OVERLAP):
             # the sampled rate — three small networks on ~10 k rows and a dozen reductions, launch-bound — is issued by the caller
             # BEHIND the rasterizer's launches, on its own stream (finish_deferred_rate): it runs under the compositing kernels
             # forward and, its autograd nodes living on that stream, under the rasterizer's backward
             reads = [feat, grid_scaling, grid_offsets, offset_masks, Q_feat, Q_scaling, Q_offsets, ec_row, plan.sel, ec]
             ready = torch.cuda.current_stream(vis.device).record_event()
-            if switches.RATE_EARLY:
-                # issued NOW (still on its own stream, so it runs beside whatever follows): the rate's autograd nodes are then
-                # OLDER than the rasterizer's, and the engine — which runs younger nodes first — launches the rasterizer's backward
-                # before the rate's ~40 small launches instead of behind them
-                rs = small_work_stream(vis.device)
-                rs.wait_event(ready)
-                record_on(rs, *reads)
-                with torch.cuda.stream(rs):
-                    packs = rate()
-                deferred.append((lambda: packs, ready, ()))
-                return rates
             deferred.append((rate, ready, reads))
             return rates
         return rate()
@@ -1491,7 +1385,7 @@ def generate_neural_gaussians_many(frames, pc, visible_masks, mode=GenerateMode.
                                 xyz=xyz, color=color, rot=rot, world=world,      # the un-split tensors: rasterize_many works on their row ranges
                                 bit_per_param_sum=getattr(rates[0], "bit_per_param_sum", None),
                                 deferred_rate=deferred[0] if deferred else None,
-                                small_work=bool(vis.is_cuda and gpu_bound(seg.rows) and not switches.NO_RATE_OVERLAP))
+                                gpu_bound=bound, small_work=bool(vis.is_cuda and bound and not switches.NO_RATE_OVERLAP))
         out = []
         for r, gs in enumerate(seg.slices(K)):
             out.append(GeneratedGaussians(

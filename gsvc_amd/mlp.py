@@ -24,7 +24,7 @@ import os
 
 import torch
 
-from . import _lib, switches
+from . import _lib, schedule, switches
 
 MFMA_MAX_DIM = 192
 MIN_ROWS = 4096
@@ -32,13 +32,10 @@ MIN_ROWS = 4096
 # wave's row fragments / accumulators across the products but re-stage every product's weight image per workgroup — a fixed cost
 # that a few thousand rows do not amortise (the rate sample's ~10 k rows: 124 us against 3 x 16 us as layer launches; same-process
 # A/B of the fitting step 7.36 -> 7.28 ms): switches.MANY_MIN_ROWS, default 24 576.  A HOST-bound step (few visible rows: the host,
-# not the GPU, sets its time — gsvc_amd.generate sets ``host_bound_step`` per generation pass) takes them at any size: there a
+# not the GPU, sets its time — gsvc_amd.schedule.host_bound_step, set per generation pass) takes them at any size: there a
 # launch saved is worth more than the microseconds its kernel loses (configs[3]: 4.86 -> 4.66 ms per step, round 5)
-host_bound_step = False
-
-
 def _many_min_rows():
-    return 0 if host_bound_step else switches.MANY_MIN_ROWS
+    return 0 if schedule.host_bound_step else switches.MANY_MIN_ROWS
 
 
 # epilogue codes of gsvc_linear_forward_ex (include/gsvc_hip.h)
@@ -574,41 +571,6 @@ def _film_desc(film):
     return C.byref(d)
 
 
-# ---- the weight gradients' own stream (gsvc_set_wgrad_stream) ----------------------------------------------------------------
-# Trainer.step opens ``wgrad_overlap`` around its backward: inside it _GenerateAll.backward's dW products run on a side stream
-# behind the chain kernels while the step's stream carries the feature gradient on; leaving it, the step's stream waits for them.
-_WGRAD_STREAM = {}
-_wgrad_active = None      # the side stream while a ``wgrad_overlap`` block is open
-_wgrad_calls = 0          # _GenerateAll.backward calls inside the open block: only the FIRST one's products leave the step's stream — a
-                          # second call's gradients are ADDED to the first's by autograd, on the step's stream, before the block's end
-
-
-class wgrad_overlap:
-    def __init__(self, dev):
-        self.dev = dev
-
-    def __enter__(self):
-        global _wgrad_active
-        if self.dev.type != "cuda" or switches.NO_WGRAD_OVERLAP or _wgrad_active is not None:
-            self.on = False
-            return self
-        st = _WGRAD_STREAM.get(self.dev.index)
-        if st is None:
-            st = _WGRAD_STREAM[self.dev.index] = torch.cuda.Stream(device=self.dev)
-        _lib.check(_lib.lib().gsvc_set_wgrad_stream(st.cuda_stream), "gsvc_set_wgrad_stream")
-        global _wgrad_calls
-        _wgrad_active, _wgrad_calls, self.on = st, 0, True
-        return self
-
-    def __exit__(self, *exc):
-        global _wgrad_active
-        if self.on:
-            _lib.check(_lib.lib().gsvc_set_wgrad_stream(None), "gsvc_set_wgrad_stream")
-            torch.cuda.current_stream(self.dev).wait_stream(_wgrad_active)      # the optimizer, the reducer: behind the last product
-            _wgrad_active = None
-        return False
-
-
 def _ptr_array(tensors):
     import ctypes as C
     return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
@@ -676,17 +638,9 @@ class _GenerateAll(torch.autograd.Function):
                 setattr(gds[g], name, v.data_ptr())
             total += (int(L.gsvc_generator_scratch_floats(C.byref(d), M, int(ctx.film[0].shape[0]) if ctx.film is not None else 0)) + 3) // 4 * 4
         dd = _deform_desc(params[42:52])
-        side = _wgrad_active if (_wgrad_active is not None and dev.type == "cuda") else None
-        later_call = False
-        if side is not None:
-            global _wgrad_calls
-            _wgrad_calls += 1
-            if _wgrad_calls > 1:
-                # (the per-render form of a step: several generation passes) the sum of this call's and the first call's weight gradients
-                # is formed on this stream: wait for the first call's products, keep this call's here
-                torch.cuda.current_stream(dev).wait_stream(side)
-                _lib.check(L.gsvc_set_wgrad_stream(None), "gsvc_set_wgrad_stream")
-                later_call, later_side, side = True, side, None
+        # a GPU-bound step's backward offers the weight gradients a stream of their own (gsvc_amd.schedule.backward_streams): the dW
+        # products run there behind the chain kernels while the step's stream carries the feature gradient on
+        side = schedule.take_wgrad_stream() if dev.type == "cuda" else None
         if side is None:
             total = max(total, int(L.gsvc_deform_scratch_floats(C.byref(dd), M)))      # the deformation network reuses the generators' scratch
             scratch = scratch_d = torch.empty(total, device=dev, dtype=torch.float32)
@@ -697,10 +651,9 @@ class _GenerateAll(torch.autograd.Function):
             scratch_d = torch.empty(int(L.gsvc_deform_scratch_floats(C.byref(dd), M)), device=dev, dtype=torch.float32)
             for x in (feat, cond, *saved, scratch, scratch_d, flat, gys[3], *((ctx.film[0],) if ctx.film is not None else ())):
                 x.record_stream(side)
-        hold = side is not None
-        if hold:
             # both networks' chain kernels first, then every product beside what follows: a chain workgroup needs its whole CU, and the
             # generators' products queued ahead of mlp_deform's chain kernels made those wait for them (6.81 -> 6.78 ms per step)
+            _lib.check(L.gsvc_set_wgrad_stream(side.cuda_stream), "gsvc_set_wgrad_stream")
             _lib.check(L.gsvc_wgrad_hold(1), "gsvc_wgrad_hold")
         F_ = feat.shape[1]
         per = (M * F_ + 3) // 4 * 4                                                      # every buffer starts 16-byte aligned
@@ -720,12 +673,11 @@ class _GenerateAll(torch.autograd.Function):
                                               _lib.ptr(scratch_d), _lib.ptr(gfeats[3]), 0, _ptr_array(gen_gf), 3, C.byref(gd), st),
                        "gsvc_deform_backward")
         finally:
-            if hold:      # (also after an error: nothing stays held, the library leaves the hold)
+            if side is not None:      # (also after an error: nothing stays held or set)
                 rc = L.gsvc_wgrad_flush(st)
                 L.gsvc_wgrad_hold(0)
-            if later_call:
-                L.gsvc_set_wgrad_stream(later_side.cuda_stream)
-        if hold:
+                L.gsvc_set_wgrad_stream(None)
+        if side is not None:
             _lib.check(rc, "gsvc_wgrad_flush")
         return (gfeats[3] if need[0] else None, None, None, None, *grads)
 

@@ -201,7 +201,7 @@ def render_frames(frames, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0
         if int(f.image_width) % 16 != 0 or (int(getattr(pipe, "raster_flags", 0) or 0) & 3):
             raise ValueError("render_frames: the two-view pass needs an image width that is a multiple of 16 and the symmetric-slab / "
                              "pixel-centre conventions (use render_pair)")
-    from ..rasterizer import _side_streams
+    from ..schedule import raster_streams
     dev = pc._anchor.device
 
     def launch(chunk, trunks):
@@ -210,9 +210,9 @@ def render_frames(frames, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0
         visible = prefilter_voxels_many(chunk, pc, pipe, bg_color, geometry=geometry)
         gss_list = generate_neural_gaussians_many(chunk, pc, visible, mode, dense=True, anchors=geometry[0], trunks=trunks)
         images, states = [], []
-        # the frames of a batch are independent pipelines: dealt to two side streams (rasterizer._side_streams), one frame's
+        # the frames of a batch are independent pipelines: dealt to two side streams (schedule.raster_streams), one frame's
         # kernel boundaries and tails are filled by the next frame's kernels
-        side = _side_streams(dev, len(chunk))
+        side = raster_streams(dev, len(chunk))
         main = torch.cuda.current_stream(dev) if side else None
         args = [(gss.xyz.contiguous(), gss.color.contiguous(), gss.opacity.contiguous(), gss.scaling.contiguous(), gss.rot.contiguous())
                 for gss in gss_list]

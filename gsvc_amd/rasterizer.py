@@ -37,7 +37,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, switches
+from . import _lib, schedule
 
 
 class GaussianRasterizationSettings(NamedTuple):
@@ -212,9 +212,8 @@ def resolve_deferred(states):
     if not states:
         return [], False
     if all(getattr(st, "_event", None) is not None for st in states):
-        from .generate import _blocked_wait      # (what the host blocks here is the GPU's lead over it: Trainer's bound detector)
         for st in states:
-            _blocked_wait(st._event)
+            schedule.blocked_wait(st._event)      # (what the host blocks here is the GPU's lead over it: Trainer's bound detector)
         host = [st._host.tolist() for st in states]
     else:
         host = torch.stack([st.binning[:32].view(torch.int32) for st in states]).tolist()
@@ -319,21 +318,6 @@ class _RasterizeGaussiansEx(torch.autograd.Function):
                 dq if rotations is not None else None, dsh, dcov, None, None, None, None, None)
 
 
-_SIDE = {}
-
-
-def _side_streams(device, renders):
-    """Two side streams per device for the independent renders of a step (GSVC_RASTER_STREAMS=1: everything on the current
-    stream)."""
-    n = switches.RASTER_STREAMS
-    if n <= 1 or renders < 2 or torch.device(device).type != "cuda":
-        return []
-    key = (torch.device(device).index, n)
-    if key not in _SIDE:
-        _SIDE[key] = [torch.cuda.Stream(device=device) for _ in range(n)]
-    return _SIDE[key]
-
-
 class _RasterizeMany(torch.autograd.Function):
     """R rasterizations of consecutive row ranges of ONE set of Gaussian tensors (the un-compacted renders of a fitting step are
     slices of the batch the generation pass produced): the forward launches the R pipelines on the ranges in place, the backward
@@ -350,7 +334,7 @@ class _RasterizeMany(torch.autograd.Function):
         images, states = [], []
         # the renders are independent pipelines of dependent kernels (bin, scatter, sort, composite): dealt to two side streams,
         # one render's kernel boundaries and tails are filled by the other's kernels
-        side = _side_streams(means3D.device, len(cs_list))
+        side = schedule.raster_streams(means3D.device, len(cs_list))
         main = torch.cuda.current_stream(means3D.device)
         for sd in side:
             sd.wait_stream(main)
@@ -376,7 +360,7 @@ class _RasterizeMany(torch.autograd.Function):
         d3, d2, dc = torch.empty(N, 3, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, 3, device=dev)
         do, ds, dq = torch.empty(N, 1, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, 4, device=dev)
         L = _lib.lib()
-        side = _side_streams(dev, len(ctx.states))
+        side = schedule.raster_streams(dev, len(ctx.states))
         main = torch.cuda.current_stream(dev)
         # everything the side streams read is produced / allocated on the main stream BEFORE the fork: an image gradient that is
         # not contiguous fp32 (an expanded gradient of images[r].sum(), autocast) is converted by a copy kernel on main, and the

@@ -18,16 +18,13 @@ import contextlib
 import torch
 
 from . import dist as gdist
-from . import switches
+from . import schedule, switches
 from .generate import GenerateMode, region
 from .loss_utils import calc_optical_loss, render_regs, ssim_l1, ssim_l1_pair
 from .optim import FusedAdam
 from .ortho_gaussian_renderer import plan_views, render, render_many
 from .rasterizer import resolve_deferred
 from .train_util import TrainingController
-
-
-EARLY_PLAN_MIN_ROWS = 150_000      # visible anchor rows of a step's views from which Trainer._early_tail is used
 
 
 @dataclass
@@ -170,10 +167,12 @@ class Trainer:
         gaussians._zown = self._zown      # gsvc_amd.generate._param_means reads the owners' means from it
         self._mask_reg_weight = 0.0
         self._ovf_handle = None
-        # which side bounds the steps, measured (gsvc_amd.generate.StepContext.gpu_bound_hint): the host's blocked time per step, smoothed
+        # which side bounds the steps, measured (gsvc_amd.schedule.StepContext.gpu_bound_hint): the host's blocked time per step, smoothed
         self._blocked_ema = None
-        from . import generate as _gen
-        self._ctx = _gen.StepContext()      # this trainer's own measurement (made current for the duration of each of its steps)
+        self._ctx = schedule.StepContext()      # this trainer's own measurement (made current for the duration of each of its steps)
+        # the generators' and mlp_deform's parameters: the networks whose weight gradients may take a stream of their own
+        self._chain_params = [p for m in (gaussians.get_opacity_mlp, gaussians.get_color_mlp, gaussians.get_cov_mlp, gaussians.get_deform_mlp)
+                              for p in m.parameters()]
 
     def close(self):
         """Give the calling thread its CPU affinity back (``__init__`` narrowed it to the GPU's NUMA node: gsvc_amd/hostbind.py;
@@ -181,9 +180,6 @@ class Trainer:
         if self.pc._anchor.is_cuda:
             from .hostbind import unbind
             unbind(self.pc._anchor.device)
-        from . import generate as _gen
-        if _gen.step_context is self._ctx:
-            _gen.step_context = _gen._DEFAULT_CONTEXT
 
     def __enter__(self):
         return self
@@ -203,9 +199,7 @@ class Trainer:
         step the GPU bounds the step and host-side work that shortens the GPU's (the small-work stream, the early plan, separate
         layer launches) pays; under ~0.1 ms the host does and it does not.  In between the last decision stands (the measures
         themselves move the balance).  The first steps (allocator growth, first launches) are not counted."""
-        from . import generate as _gen
         ctx = self._ctx
-        _gen.step_context = ctx          # whatever this step's generation / waits read and add to is this trainer's
         b = ctx.host_blocked_s
         ctx.host_blocked_s = 0.0
         self._steps_seen = getattr(self, "_steps_seen", 0) + 1
@@ -234,50 +228,52 @@ class Trainer:
             self.bound_log = getattr(self, "bound_log", [])[-31:] + [(self._steps_seen, bool(ctx.gpu_bound_hint), 1e3 * self._blocked_ema)]
 
     def step(self, iteration: int, frame_idx: int | None = None) -> StepOutput:
-        self._update_bound()
-        if frame_idx is None and self._plan_idx is not None:
-            frame_idx = self._plan_idx              # drawn (from the same generator, in the same order) at the end of the last step
-        self._early = None
-        out = self._step(iteration, frame_idx)
-        if out is None:      # a rasterizer instance buffer overflowed (capacity now raised): repeat the step
-            self.repeated_steps = getattr(self, "repeated_steps", 0) + 1
-            dropped = None
-            if self._early is not None:
-                # the guarded early update saw the overflow word and wrote nothing: only its step counts moved.  The plan it
-                # queued is for the NEXT frame pair; the repeat draws its own lists.
-                self.pc.optimizer.rewind(self._early[0])
-                dropped = self._early[3]          # its count exchange is in flight: the tensors stay alive until the repeat is done
-                self._early = None
-            elif self.prefetch and self.pc._anchor.is_cuda and gdist.active():
-                # Whether the early tail ran is a rank-LOCAL fact (its row threshold and reducer.complete() depend on the rank's
-                # own views), and it queued a plan = one collective on the plan group.  A rank that did not run it answers with a
-                # matching no-op exchange, so that every rank has issued exactly ONE plan-group collective per attempted step:
-                # otherwise the repeat's end-of-step plan on this rank would pair with the other rank's dropped one and every
-                # later distinct_cap would be one step out of phase between the ranks.
-                dropped = gdist.plan_group_noop(self.pc._anchor.device)
-            # the repeat draws its own index lists on EVERY rank (no plan -> dense gradient exchange everywhere): a rank that kept
-            # its plan would exchange rows while a rank that dropped its early plan all-reduces
-            self._plan = None
-            self.pc.optimizer.zero_grad(set_to_none=True)
-            out = self._step(iteration, frame_idx if frame_idx is not None else self._last_idx, early=False)     # the same frame pair again
-            if out is None:
-                raise RuntimeError("rasterizer instance buffer overflowed twice in a row")
-            if dropped is not None and getattr(dropped, "_gmax_work", None) is not None:
-                dropped._gmax_work.wait()
-            del dropped
-        self.controller.step()
-        if self._early is not None:          # the next step's plan was queued from inside the backward (_early_tail)
-            _, self._plan_idx, self._plan_mode, self._plan = self._early
+        # whatever this step's generation, waits and backward read and add to is this trainer's; outside a step, the default context
+        with schedule.using(self._ctx):
+            self._update_bound()
+            if frame_idx is None and self._plan_idx is not None:
+                frame_idx = self._plan_idx              # drawn (from the same generator, in the same order) at the end of the last step
             self._early = None
+            out = self._step(iteration, frame_idx)
+            if out is None:      # a rasterizer instance buffer overflowed (capacity now raised): repeat the step
+                self.repeated_steps = getattr(self, "repeated_steps", 0) + 1
+                dropped = None
+                if self._early is not None:
+                    # the guarded early update saw the overflow word and wrote nothing: only its step counts moved.  The plan it
+                    # queued is for the NEXT frame pair; the repeat draws its own lists.
+                    self.pc.optimizer.rewind(self._early[0])
+                    dropped = self._early[3]          # its count exchange is in flight: the tensors stay alive until the repeat is done
+                    self._early = None
+                elif self.prefetch and self.pc._anchor.is_cuda and gdist.active():
+                    # Whether the early tail ran is a rank-LOCAL fact (its row threshold and reducer.complete() depend on the rank's
+                    # own views), and it queued a plan = one collective on the plan group.  A rank that did not run it answers with a
+                    # matching no-op exchange, so that every rank has issued exactly ONE plan-group collective per attempted step:
+                    # otherwise the repeat's end-of-step plan on this rank would pair with the other rank's dropped one and every
+                    # later distinct_cap would be one step out of phase between the ranks.
+                    dropped = gdist.plan_group_noop(self.pc._anchor.device)
+                # the repeat draws its own index lists on EVERY rank (no plan -> dense gradient exchange everywhere): a rank that kept
+                # its plan would exchange rows while a rank that dropped its early plan all-reduces
+                self._plan = None
+                self.pc.optimizer.zero_grad(set_to_none=True)
+                out = self._step(iteration, frame_idx if frame_idx is not None else self._last_idx, early=False)     # the same frame pair again
+                if out is None:
+                    raise RuntimeError("rasterizer instance buffer overflowed twice in a row")
+                if dropped is not None and getattr(dropped, "_gmax_work", None) is not None:
+                    dropped._gmax_work.wait()
+                del dropped
+            self.controller.step()
+            if self._early is not None:          # the next step's plan was queued from inside the backward (_early_tail)
+                _, self._plan_idx, self._plan_mode, self._plan = self._early
+                self._early = None
+                return out
+            self._plan = self._plan_idx = None
+            if self.prefetch and self.pc._anchor.is_cuda:
+                with torch.no_grad(), region('step.plan'):
+                    self._plan_idx = self.rng.randint(self.lo, max(self.lo, self.hi - 1))
+                    self._prefetch_frames(self._plan_idx)
+                    self._plan_mode = self.controller.render_mode
+                    self._plan = plan_views(self._views(self._plan_idx), self.pc, self.pipe, self.background, self._plan_mode)
             return out
-        self._plan = self._plan_idx = None
-        if self.prefetch and self.pc._anchor.is_cuda:
-            with torch.no_grad(), region('step.plan'):
-                self._plan_idx = self.rng.randint(self.lo, max(self.lo, self.hi - 1))
-                self._prefetch_frames(self._plan_idx)
-                self._plan_mode = self.controller.render_mode
-                self._plan = plan_views(self._views(self._plan_idx), self.pc, self.pipe, self.background, self._plan_mode)
-        return out
 
     def sync_replicas(self, moments: bool = True):
         """Under z-range ownership (GSVC_DP_ZOWN=1) a replica is only fresh inside its own block + halo: call this (on every rank)
@@ -352,11 +348,6 @@ class Trainer:
         # only when a rank sees less than a quarter of the anchors.  The same decision on every rank (cap is their maximum).
         return switches.DP_SPARSE == "1" or gdist.sparse_rows_pay(gdist.world_size(), int(self.pc._anchor.shape[0]),
                                                                                   plan.distinct_cap)
-
-    @staticmethod
-    def _gpu_bound(rows):
-        from . import generate as _gen
-        return rows >= EARLY_PLAN_MIN_ROWS or bool(_gen.step_context.gpu_bound_hint)
 
     def _views(self, frame_idx):
         """The step's four views: (frame, frame seen from the opposite side) of the two adjacent frames."""
@@ -441,9 +432,8 @@ class Trainer:
         # on the small-work stream behind the generation pass's event so that they run under the compositing kernels (their backward
         # too: autograd runs a node on its forward's stream) instead of behind the image losses
         side = None
-        if batch is not None and getattr(batch, "generated_event", None) is not None and not switches.NO_RATE_OVERLAP:
-            from .generate import small_work_stream
-            side = small_work_stream(dev)
+        if getattr(batch, "generated_event", None) is not None:      # (recorded only when the batch's small_work is set)
+            side = schedule.small_work_stream(dev)
             side.wait_event(batch.generated_event)
         n_image_terms = len(terms)
         with (torch.cuda.stream(side) if side is not None else contextlib.nullcontext()):
@@ -473,9 +463,8 @@ class Trainer:
                 weights += [opt.lmbda] * (1 if rate_sum is not None else 4) + [opt.lmbda / denom, 5e-4]
         if side is not None:
             # what the terms above read of the step's stream's allocations (and saved for their backward on the small-work stream)
-            from .generate import record_on
-            record_on(side, batch.scaling, batch.neural_opacity, batch.mask, getattr(batch, "world", None), getattr(batch, "vis", None),
-                      [g.step_cache for g in grid_tables(pc)], flow if opt.optical_lambda != 0 else None)
+            schedule.record_on(side, batch.scaling, batch.neural_opacity, batch.mask, getattr(batch, "world", None), getattr(batch, "vis", None),
+                               [g.step_cache for g in grid_tables(pc)], flow if opt.optical_lambda != 0 else None)
             main_stream = torch.cuda.current_stream(dev)
             main_stream.wait_stream(side)
             for t in terms[n_image_terms:]:
@@ -516,8 +505,7 @@ class Trainer:
                 and pc._scaling.requires_grad and pc._mask.requires_grad
                 # it pays when the GPU, not the host, bounds the step (the hook's work costs ~1 ms of host time more on the
                 # autograd thread than at the end of the step: a 6 k-row step went 8.3 -> 9.7 ms, the 200 k-row step 11.95 -> 11.3)
-                and (switches.EARLY_PLAN or self._gpu_bound(sum(int(r.visible_index.shape[0]) for r in
-                                                                                (x.generated_gaussians for x in renders))))):
+                and (switches.EARLY_PLAN or batch.gpu_bound)):
             # STE_ENTROPY renders from detached attributes (reference guassian.py:205-207): _scaling receives no gradient there,
             # is not changed by the step, and its hook would never run
             waited = [pc._mask] if mode == GenerateMode.TRAININ_STE_ENTROPY else [pc._scaling, pc._mask]
@@ -529,24 +517,15 @@ class Trainer:
                     self._early_tail(renders, waited)
             handles = [p.register_post_accumulate_grad_hook(arrived) for p in waited]
         try:
-            from .generate import two_stream_backward
-            from .mlp import wgrad_overlap
             # a GPU-bound step (the one that uses the small-work stream) also sends the chain networks' weight gradients to their own
-            # stream; a host-bound one only pays for the events and the allocator's stream records (configs[3]: +0.2 ms of host time)
-            gpu_bound_step = side is not None or getattr(batch, "small_work", False)
-            with region('step.backward'), (two_stream_backward() if gpu_bound_step else contextlib.nullcontext()), \
-                    (wgrad_overlap(dev) if gpu_bound_step else contextlib.nullcontext()):
+            # stream, and waits for both streams behind the backward; a host-bound one would only pay for the events and the allocator's
+            # stream records (configs[3]: +0.2 ms of host time)
+            with region('step.backward'), (schedule.backward_streams(dev, self._chain_params) if getattr(batch, "small_work", False)
+                                           else contextlib.nullcontext()):
                 loss.backward()
         finally:
             for h in handles:
                 h.remove()
-        if dev.type == "cuda" and (side is not None or getattr(batch, "small_work", False)):
-            # backward() returns with every node's kernels queued on the node's forward stream.  A parameter that only the small-work
-            # stream touched (the priors' networks: used by the deferred rate alone) has its gradient accumulated THERE, and nothing in
-            # the engine orders that before what this stream does next — the optimizer, the reducer, the statistics.  Without this
-            # wait Adam occasionally read those gradients half written (seen as run-to-run drift of the rate model, not as a crash).
-            from .generate import small_work_stream
-            torch.cuda.current_stream(dev).wait_stream(small_work_stream(dev))
         done = getattr(self.dataset, "step_done", None)
         if done is not None:
             done()      # every reader of the ground-truth slots (image losses, optical term — forward and backward, this stream and the

@@ -8,7 +8,7 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
-MODULES = ["_lib", "generate", "mlp", "train", "rasterizer", "loss_utils", "optim", "model", "encodings", "entropy_models", "dist",
+MODULES = ["_lib", "generate", "mlp", "train", "rasterizer", "schedule", "loss_utils", "optim", "model", "encodings", "entropy_models", "dist",
            "ortho_gaussian_renderer/renderer", "ortho_gaussian_renderer/preprocess"]
 
 

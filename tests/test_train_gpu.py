@@ -343,7 +343,7 @@ def test_early_plan_steps_equal_plain_steps(monkeypatch, phase):
         assert off < 5e-3, (n, off)
 
 
-def test_rate_on_its_own_stream_equals_the_rate_inside_the_generation_pass(monkeypatch):
+def test_rate_on_the_small_work_stream_equals_the_rate_inside_the_generation_pass(monkeypatch):
     """TRAINING_ENTROPY steps with the sampled rate issued behind the rasterizer's launches on a stream of its own
     (gsvc_amd/generate.py finish_deferred_rate: its kernels run under the compositing kernels, forward and backward) against
     GSVC_NO_RATE_OVERLAP=1 (inside the generation pass, on the step's stream): the same draws, losses and parameters after four
@@ -356,7 +356,8 @@ def test_rate_on_its_own_stream_equals_the_rate_inside_the_generation_pass(monke
             monkeypatch.setenv("GSVC_NO_RATE_OVERLAP", "1")
         monkeypatch.setenv("GSVC_EARLY_PLAN", "1")
         import gsvc_amd.generate as G
-        monkeypatch.setattr(G, "SMALL_WORK_MIN_ROWS", 0)      # a step this small does not use the third stream by itself
+        import gsvc_amd.schedule as S
+        monkeypatch.setattr(S, "GPU_BOUND_MIN_ROWS", 0)      # a step this small does not use the third stream by itself
         pc, cube, opt, pipe, mp, Trainer = _setup(anchors=6000, seed=4)
         opt.full_precision_training_total = opt.quantized_training_total = 0
         opt.entropy_constrained_train_total = 1000
@@ -1359,15 +1360,31 @@ def test_deterministic_mode_computes_the_default_modes_gradients(monkeypatch):
 @pytest.mark.gpu
 @pytest.mark.parametrize("batched", [True, False])
 def test_weight_gradients_on_their_own_stream_are_the_same_gradients(monkeypatch, batched):
-    """Inside a step's backward the generators' / mlp_deform's weight-gradient products run on a side stream behind the chain kernels
-    (gsvc_set_wgrad_stream; mlp.wgrad_overlap) while the step's stream carries the feature gradient on.  The same kernels on the same
-    operands: under GSVC_DETERMINISTIC=1 every parameter's gradient has the SAME BITS with and without the side stream — in the
-    production form (one generation pass per step) and in the per-render form (four passes: only the first one's products leave the
-    step's stream, the others' are added to them by autograd on it), in the entropy and the straight-through phase, step after step."""
+    """In a GPU-bound step's backward (gsvc_amd.schedule.backward_streams) the generators' / mlp_deform's weight-gradient products run
+    on a side stream behind the chain kernels (gsvc_set_wgrad_stream, taken by mlp._GenerateAll.backward) while the step's stream
+    carries the feature gradient on.  The same kernels on the same operands: under GSVC_DETERMINISTIC=1 every parameter's gradient
+    has the SAME BITS with and without the side stream, in every phase, step after step.  The steps are made GPU-bound by the row
+    threshold (0), the model has the production widths (the chain kernels exist for those only), and a spy on the library's
+    gsvc_set_wgrad_stream shows the stream taken once in every batched step — and never in the per-render form, which has no batch
+    and so no side stream at all."""
     import os
-    from gsvc_amd import switches
+    from gsvc_amd import _lib, schedule, switches
+    from gsvc_amd.arguments import cfg_20240919
+    from gsvc_amd.frame import SyntheticFrameCube
+    from gsvc_amd.model import GaussianModel
+    from gsvc_amd.train import Trainer
+    monkeypatch.setattr(schedule, "GPU_BOUND_MIN_ROWS", 0)
     monkeypatch.setenv("GSVC_DETERMINISTIC", "1")
     switches.reload()
+    L = _lib.lib()
+    real_set = L.gsvc_set_wgrad_stream
+    taken = []
+
+    def spy(stream):
+        if stream is not None:
+            taken.append(stream)
+        return real_set(stream)
+    monkeypatch.setattr(L, "gsvc_set_wgrad_stream", spy)
     try:
         res = {}
         for off in (False, True):
@@ -1376,13 +1393,24 @@ def test_weight_gradients_on_their_own_stream_are_the_same_gradients(monkeypatch
             else:
                 monkeypatch.delenv("GSVC_NO_WGRAD_OVERLAP", raising=False)
             switches.reload()
-            pc, cube, opt, pipe, mp, Trainer = _setup(anchors=5000, H=96, W=160, T=12, seed=7)
+            mp_, opt, pipe = cfg_20240919()
+            cube = SyntheticFrameCube(96, 160, 12, device="cuda")
+            mp_.threshold = 3.0 / cube.scale
+            torch.manual_seed(7)
+            np.random.seed(7)
+            pc = GaussianModel(mp_, mp_.anchor_feature_dim, mp_.n_offsets, mp_.voxel_size, mp_.update_depth, mp_.update_init_factor,
+                               mp_.update_hierarchy_factor, mp_.use_feat_bank, n_features_per_level=mp_.grid_feature_dim,
+                               log2_hashmap_size=mp_.log2, log2_hashmap_size_2D=mp_.log2_2D, device="cuda")
+            rng = np.random.default_rng(7)
+            lim = np.array([cube.x_min, cube.y_min, cube.z_min]) * 1.1
+            pc.create_from_points(rng.uniform(lim, -lim, (20_000, 3)), spatial_lr_scale=1.0)
+            pc.update_anchor_bound(cube.x_min, cube.y_min, cube.z_min)
             opt.full_precision_training_total, opt.quantized_training_total = 2, 2
             opt.entropy_constrained_train_total, opt.ste_entropy_constrained_train_total = 3, 3
             opt.start_stat, opt.update_until, opt.pause_densification = 10 ** 9, 10 ** 9, 0
             pc.training_setup(opt)
-            tr = Trainer(pc, cube, opt, pipe, mp, seed=4, batched=batched)
-            grads = []
+            tr = Trainer(pc, cube, opt, pipe, mp_, seed=4, batched=batched)
+            grads, took = [], []
             real_step = pc.optimizer.step
 
             def step(*a, **k):
@@ -1391,10 +1419,15 @@ def test_weight_gradients_on_their_own_stream_are_the_same_gradients(monkeypatch
                 return real_step(*a, **k)
             pc.optimizer.step = step
             for it in range(1, 11):
+                n0 = len(taken)
                 tr.step(it, frame_idx=3 + it % 4)
+                took.append(len(taken) - n0)
             torch.cuda.synchronize()
             res[off] = (grads, {n: p.detach().clone() for n, p in pc.named_parameters()})
             tr.close()
+            # the armed form took the side stream in every step (once: one generation pass per step); nothing else ever does
+            assert took == [1 if (batched and not off) else 0] * 10, (off, took)
+            assert all(t == schedule.wgrad_stream(pc.device).cuda_stream for t in taken)
         (g_on, p_on), (g_off, p_off) = res[False], res[True]
         assert len(g_on) == len(g_off) == 10
         for i, (a, b) in enumerate(zip(g_on, g_off)):
