@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the GSVC hot path on MI355X (contract: see the task statement).
 
-    python bench.py --gpus N --steps K --warmup W [--workload headline|train_step|raster_fwd|raster_fwdbwd]
+    python bench.py --gpus N --steps K --warmup W [--workload headline|train_step|raster_fwd|raster_fwdbwd] [--full]
+
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if given and prints the line: the headline figure
+(`value`, `ms_per_step`), the configuration it was measured on, the timed region's counters and the steps' measured bound.
+Everything else the benchmark measures takes runs of its own and comes with --full: per-kernel and roofline passes, cold-frame
+and exchange-off passes, the decoder loop, stream codec and adjust_anchor timings, CPU baselines, and the headline's side runs.
 
 Workloads (a "step" is one pass of the hot path over synthetic UVG-shaped 1080p input resident in HBM):
   train_step     BASELINE.json configs[2] (the largest single-GPU configuration of the metric): 1080p, 16-frame z-slab,
@@ -14,8 +19,9 @@ Workloads (a "step" is one pass of the hot path over synthetic UVG-shaped 1080p 
                  (16-frame slab of a 300-frame cube), attributes drawn from the model's own entropy context; the whole model is
                  entropy-coded, decoded (masks, hash tables, three attribute streams per z-slab) and 24 two-view frames are
                  rendered from the decoded model: stream_decode fps = frames / (decode + render)
-  headline       (default) train_step as the top-level value / ms_per_step / roofline / cpu_baseline, plus a short
-                 raster_fwd run reported under the side key "raster_fwd" (render fps, single and two-view)
+  headline       (default) train_step as the top-level value / ms_per_step; with --full also its roofline / cpu_baseline and
+                 the side runs: a short raster_fwd run under the side key "raster_fwd" (render fps, single and two-view), the live
+                 fit, the 500 k-active and late-in-a-fit steps, the schedule's phases and the 4K stream decode
 
 --gpus N > 1: when not already under torch.distributed.run (no WORLD_SIZE in the environment) this process starts
 `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a CHILD before anything touches the GPU,
@@ -23,11 +29,11 @@ relays its JSON line and exits with its return code.  One rank per GPU over RCCL
 (rank r samples its pairs from its own block of frames), gradients are all-reduced once per step -> weak scaling.
 
 One JSON line on rank 0.  `value` = Gaussians rasterized per second, whole job (sum over ranks and over the 4
-renders of Gaussians with radius > 0, x steps, / max-over-ranks wall time).  `roofline` is for the dominant
+renders of Gaussians with radius > 0, x steps, / max-over-ranks wall time).  `roofline` (--full) is for the dominant
 rasterizer kernel, timed with HIP events on its launch stream inside this process (a second pass of K steps with
 the library's per-kernel event hooks on); `roofline.traffic` comes from rocprofv3 PMC passes of this same command
 (they cannot run inside this process): the file and binary version they were taken from are named beside it.
-`cpu_baseline` = the CPU oracle (a port, not the product) on a bounded sample of the same workload.
+`cpu_baseline` (--full) = the CPU oracle (a port, not the product) on a bounded sample of the same workload.
 """
 from __future__ import annotations
 
@@ -64,8 +70,12 @@ def parse(argv=None):
     ap.add_argument("--sigma-px", type=float, nargs=2, default=(0.5, 4.0),
                     help="raster workloads: range of the Gaussians' per-axis sigma in pixels (log-uniform); BASELINE.md section 2 "
                          "uses 0.5 .. 4; a fitting render has footprints of ~13 tiles per Gaussian (try 2 .. 12)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side", action="store_true", help="headline: skip the raster_fwd side run")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure, everything else the benchmark measures: per-kernel / roofline passes, the "
+                         "cold-frame and exchange-off passes, decoder loop, stream codec, adjust_anchor, CPU baselines, the "
+                         "headline's side runs, and the raster workloads' two-view / two-stream / graph-replay fps")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle's timed sample (cpu_baseline)")
+    ap.add_argument("--no-side", action="store_true", help="headline --full: skip the side runs")
     ap.add_argument("--anchors", type=int, default=245_000,
                     help="train_step: anchors in the cube (245k in 64 frames x 1.1 bleed -> ~50k in a 16-frame slab)")
     ap.add_argument("--train-frames", type=int, default=64, help="train_step: frames of the synthetic video")
@@ -470,6 +480,17 @@ def _all_cores() -> int:
 
 
 # ------------------------------------------------------------------------------------------------ train_step
+def bound_entries(trainer, res):
+    """Which side bounds the step, measured, into ``res``: what the host blocks per step at the step's two waits (the plan's counts,
+    the renders' counters) is the GPU's lead over it (gsvc_amd.train.Trainer._update_bound); ~0 = the host is the bound."""
+    if getattr(trainer, "_blocked_ema", None) is not None:
+        res["host_blocked_ms_per_step"] = 1e3 * trainer._blocked_ema
+        hint = trainer._ctx.gpu_bound_hint
+        res["gpu_bound_measured"] = bool(hint) if hint is not None else None
+        res["gpu_bound_flips"] = [{"step": s_, "gpu_bound": g_, "blocked_ms_ema": round(m_, 3)} for s_, g_, m_ in getattr(trainer, "bound_log", [])]
+    return res
+
+
 def headline_model(args, dev):
     """The headline's video, configuration and model, built from its seeds (run_train_step; dump_train_step builds the same again)."""
     import numpy as np
@@ -585,6 +606,32 @@ def run_train_step(args, rank, world, dev):
                 sys.stderr.write(f"AB {var}={val}: {1e3 * e / 30:.3f} ms/step\n")
         os.environ.pop(var, None)
         switches.reload()
+
+    P = submitted[0] / (4.0 * args.steps)                 # Gaussians submitted per render, mean over the timed steps
+    n_vis = total_units / (4 * args.steps * world)
+    res = {
+        "metric": METRIC, "value": total_units / elapsed, "unit": "Gaussians/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"train_step ({'BASELINE.json configs[3] per-GPU workload, cfg_20240919.yaml as is' if args.cfg3 else 'BASELINE.json configs[2]'}): "
+                               f"{H}x{W}, {T}-frame synthetic video, {pc._anchor.shape[0]} "
+                               f"anchors x K=10, {slab_frames:.0f}-frame z-slab (threshold {mp_.threshold:.5f}); 4 renders/step fwd+bwd + hash grid + entropy loss "
+                               f"(lambda={opt.lmbda}, TRAINING_ENTROPY) + L1/SSIM/optical + Adam; one frame pair per rank; "
+                               f"{args.pretrain} untimed fitting steps before the warmup ({'frozen scene: deterministic fit, seed ' + str(args.scene_seed) + ' / video 1234, checksum ' + scene['checksum'] if scene['frozen'] else 'live fit'})",
+                   "scene": scene,
+                   "gaussians_per_render": P, "active_per_render": n_vis, "active_fraction": n_vis / max(P, 1.0),
+                   "visible_anchors_per_render": P / pc.n_offsets,
+                   "value_counts": "Gaussians with radius > 0 (active_per_render x 4 renders x steps / s); gaussians_per_render are "
+                                   "submitted un-compacted (K per visible anchor), both means over the timed steps",
+                   "parallelism": f"frame-shard x{world} + gradient all-reduce" if world > 1 else "single GPU"},
+        "effective_batch": world,      # frame pairs per optimizer step: loss = mean over ranks (the reference steps on one pair)
+        "dp_anchor_optimizer": ("row-sparse / all-reduce exchange + replicated Adam" if world > 1 else None),
+        "rccl_ranks": (dist.get_world_size() if _dp_on(world) else 1),
+        "dist_backend": (dist.get_backend() if _dp_on(world) else None),
+        "timed_region": timed_region,
+    }
+    if not args.full:
+        return bound_entries(trainer, res) if rank == 0 else None
 
     # cold ground truth: the same K steps with the video in pinned HOST memory and the step's two frames + flow uploaded per step
     # (what the reference's own step timer includes: pipeline/train.py:332,407-408,464), one step ahead on a copy stream
@@ -810,8 +857,6 @@ def run_train_step(args, rank, world, dev):
     HW = H * W
     n_inst = inst / (4 * args.steps)                      # instances per render (listed: what the roofline's bytes are counted on)
     n_inst_api = inst_api / (4 * args.steps)              # num_rendered per render (tiles of the 3-sigma rectangles)
-    P = submitted[0] / (4.0 * args.steps)                 # Gaussians submitted per render, mean over the timed steps
-    n_vis = total_units / (4 * args.steps * world)
     kern = {k: {"launches": n, "avg_us": 1e3 * ms / max(n, 1)} for k, (n, ms) in prof.items()}
     alg = {"k_blend": 40 * n_inst + 20 * HW, "k_blend_bwd": 40 * n_inst + 20 * HW, "k_preprocess": 60 * P + 44 * n_vis,
            "k_gaussian_bwd": 88 * n_vis + 124 * P}
@@ -829,28 +874,11 @@ def run_train_step(args, rank, world, dev):
         # for any other workload until it has its own pass
         traffic, traffic_src = None, {"measured_live": False, "file": None,
                                       "refused": "profiles/pmc_latest.json holds counters of the default train_step shape only"}
-    res = {
-        "metric": METRIC, "value": total_units / elapsed, "unit": "Gaussians/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"train_step ({'BASELINE.json configs[3] per-GPU workload, cfg_20240919.yaml as is' if args.cfg3 else 'BASELINE.json configs[2]'}): "
-                               f"{H}x{W}, {T}-frame synthetic video, {pc._anchor.shape[0]} "
-                               f"anchors x K=10, {slab_frames:.0f}-frame z-slab (threshold {mp_.threshold:.5f}); 4 renders/step fwd+bwd + hash grid + entropy loss "
-                               f"(lambda={opt.lmbda}, TRAINING_ENTROPY) + L1/SSIM/optical + Adam; one frame pair per rank; "
-                               f"{args.pretrain} untimed fitting steps before the warmup ({'frozen scene: deterministic fit, seed ' + str(args.scene_seed) + ' / video 1234, checksum ' + scene['checksum'] if scene['frozen'] else 'live fit'})",
-                   "scene": scene,
-                   "gaussians_per_render": P, "active_per_render": n_vis, "active_fraction": n_vis / max(P, 1.0),
-                   "instances_per_render": n_inst, "num_rendered_per_render": n_inst_api, "tiles_per_active_gaussian": n_inst / max(n_vis, 1.0),
-                   "instances_note": "instances_per_render = entries of the tile lists (a Gaussian is listed in the tiles its alpha >= 1/255 box "
-                                     "touches: GSVC_RASTER_TIGHT_BINNING); num_rendered_per_render = the API's count over the 3-sigma rectangles",
-                   "visible_anchors_per_render": P / pc.n_offsets,
-                   "value_counts": "Gaussians with radius > 0 (active_per_render x 4 renders x steps / s); gaussians_per_render are "
-                                   "submitted un-compacted (K per visible anchor), both means over the timed steps",
-                   "parallelism": f"frame-shard x{world} + gradient all-reduce" if world > 1 else "single GPU"},
-        "effective_batch": world,      # frame pairs per optimizer step: loss = mean over ranks (the reference steps on one pair)
-        "dp_anchor_optimizer": ("row-sparse / all-reduce exchange + replicated Adam" if world > 1 else None),
-        "rccl_ranks": (dist.get_world_size() if _dp_on(world) else 1),
-        "dist_backend": (dist.get_backend() if _dp_on(world) else None),
+    res["config"].update({
+        "instances_per_render": n_inst, "num_rendered_per_render": n_inst_api, "tiles_per_active_gaussian": n_inst / max(n_vis, 1.0),
+        "instances_note": "instances_per_render = entries of the tile lists (a Gaussian is listed in the tiles its alpha >= 1/255 box "
+                          "touches: GSVC_RASTER_TIGHT_BINNING); num_rendered_per_render = the API's count over the 3-sigma rectangles"})
+    res.update({
         "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
                      "note": "this kernel's binding unit is the vector ALU, not HBM: traffic_source.valu holds the SQ counters of the "
@@ -865,25 +893,17 @@ def run_train_step(args, rank, world, dev):
                                              "(GSVC_RASTER_STREAMS=1): its exclusive duration"})},
         "roofline_valu": roofline_valu(probe, kern.get("k_blend_bwd"), one_stream.get("k_blend_bwd"), traffic_src),
         "gsvc_kernel_us_per_step": kernel_us,
-        "timed_region": timed_region,
         "kernels": {k: {"avg_us": round(v["avg_us"], 2), "launches_per_step": v["launches"] / args.steps} for k, v in kern.items()},
         "render_pair_fps_end_to_end": pair_fps,
         "render_frames_fps_end_to_end": frames_fps,
         "decoder_loop": decoder_loop,
         "render_fps_note": PAIR_NOTE,
-    }
+    })
     if cold is not None:
         res["cold_ground_truth"] = cold
         if "ms_per_step_cold" in cold:
             res["ms_per_step_cold"] = cold["ms_per_step_cold"]
-    # which side bounds the step, measured: what the host blocks per step at the step's two waits (the plan's counts, the renders'
-    # counters) is the GPU's lead over it (gsvc_amd.train.Trainer._update_bound); ~0 = the host is the bound
-    if getattr(trainer, "_blocked_ema", None) is not None:
-        from gsvc_amd import generate as _gen
-        res["host_blocked_ms_per_step"] = 1e3 * trainer._blocked_ema
-        hint = trainer._ctx.gpu_bound_hint
-        res["gpu_bound_measured"] = bool(hint) if hint is not None else None
-        res["gpu_bound_flips"] = [{"step": s_, "gpu_bound": g_, "blocked_ms_ema": round(m_, 3)} for s_, g_, m_ in getattr(trainer, "bound_log", [])]
+    bound_entries(trainer, res)
     if comm is not None:
         res["gradient_exchange"] = comm
     if world == 1:
@@ -1274,6 +1294,21 @@ def run_raster(args, rank, world, dev, workload, cpu_baseline):
         step()
     elapsed = timed(torch, dist, world, step, args.steps)
     total_units, elapsed = reduce_sum_max(torch, dist, world, dev, float(n_vis) * args.steps, elapsed)
+    cfg_name = ("BASELINE.json configs[1]" if (H, W, P, tuple(args.sigma_px)) == (1080, 1920, 200_000, (0.5, 4.0))
+                else f"raster set of BASELINE.md section 2, sigma {args.sigma_px[0]}..{args.sigma_px[1]} px")
+    out = {
+        "metric": METRIC, "value": total_units / elapsed, "unit": "Gaussians/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{workload} ({cfg_name}): {H}x{W} single frame of a {T}-frame cube, {P} Gaussians in a "
+                               f"16-frame z-slab; frames sharded 1 per rank",
+                   "gaussians": P, "visible": n_vis, "instances": n_inst, "max_tile_list": max_tile,
+                   "parallelism": f"frame-shard x{world}"},
+        "rccl_ranks": (dist.get_world_size() if world > 1 else 1),
+        "render_fps": args.steps * world / elapsed,
+    }
+    if not args.full:
+        return out if rank == 0 else None
 
     # two-view frames (the reference's fps definition: view + opposite view + flip + average) from the fused pass
     for _ in range(3):
@@ -1355,18 +1390,7 @@ def run_raster(args, rank, world, dev, workload, cpu_baseline):
         pipe_bytes += 40 * n_inst + 20 * HW + 88 * n_vis + 124 * P
     kernel_us = sum(v["avg_us"] * v["launches"] for v in kern.values()) / args.steps
     traffic, traffic_src = pmc_traffic(workload, dom)
-    cfg_name = ("BASELINE.json configs[1]" if (H, W, P, tuple(args.sigma_px)) == (1080, 1920, 200_000, (0.5, 4.0))
-                else f"raster set of BASELINE.md section 2, sigma {args.sigma_px[0]}..{args.sigma_px[1]} px")
-    out = {
-        "metric": METRIC, "value": total_units / elapsed, "unit": "Gaussians/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-        "config": {"workload": f"{workload} ({cfg_name}): {H}x{W} single frame of a {T}-frame cube, {P} Gaussians in a "
-                               f"16-frame z-slab; frames sharded 1 per rank",
-                   "gaussians": P, "visible": n_vis, "instances": n_inst, "max_tile_list": max_tile,
-                   "parallelism": f"frame-shard x{world}"},
-        "rccl_ranks": (dist.get_world_size() if world > 1 else 1),
-        "render_fps": args.steps * world / elapsed,
+    out.update({
         "graph_replay": (None if graph_ms is None else
                          {"ms_per_step": graph_ms, "render_fps": 1e3 * world / graph_ms,
                           "note": "the same step captured once into a HIP graph and replayed (image bit-identical to the eager step)"}),
@@ -1384,7 +1408,7 @@ def run_raster(args, rank, world, dev, workload, cpu_baseline):
                               "achieved_on_wall_ms_per_step": pipe_bytes / (elapsed / args.steps) / 1e9},
         "kernels": {k: {"avg_us": round(v["avg_us"], 2), "launches_per_step": v["launches"] / args.steps}
                     for k, v in kern.items()},
-    }
+    })
     if cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_raster(sc, workload)
     del d, dL, grads, scratch
@@ -1434,7 +1458,7 @@ def main():
         if args.dump_outputs:
             torch.cuda.empty_cache()
             res["dump_outputs"] = dump_train_step(args, dev)
-        if args.workload == "headline" and not args.no_side and world == 1:
+        if args.workload == "headline" and args.full and not args.no_side and world == 1:
             # second term of the metric: render fps at 1080p on BASELINE.json configs[1]; a failure here must not take
             # the train-step line down
             try:

@@ -1,4 +1,4 @@
-"""bench.py's host-side pieces: the result line (bench.result_line) and the --dump-outputs writer (bench.dump_outputs)."""
+"""bench.py's host-side pieces: the result line (bench.result_line), the --dump-outputs writer (bench.dump_outputs) and its options."""
 import json
 import os
 
@@ -38,3 +38,8 @@ def test_result_line_is_one_line_with_every_number_and_no_notes():
     assert "\n" not in line and "note" not in line
     assert json.loads(line) == {"metric": "m", "value": 1.5, "ms_per_step": 6.5, "steps": 20, "config": {"workload": "w", "active_per_render": 3.0},
                                 "flips": [{"step": 8}], "side": {"error": "E: e", "kernels": {"k_blend": {"avg_us": 2.0}}}}
+
+
+def test_a_plain_run_is_lean_and_full_is_an_option():
+    assert not bench.parse(["--gpus", "1", "--steps", "20", "--warmup", "5"]).full
+    assert bench.parse(["--full"]).full

@@ -770,6 +770,7 @@ def test_bench_headline_scene_is_frozen():
         assert out.returncode == 0, out.stderr[-2000:]
         lines.append(json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0]))
     a, b, other, live = [l["config"]["scene"] for l in lines]
+    assert not {"roofline", "kernels", "decoder_loop", "cpu_baseline"} & lines[0].keys()       # a plain run: the headline figure only
     assert a["frozen"] and b["frozen"] and a["checksum"] == b["checksum"] and a["fit_steps"] == 24
     assert abs(lines[0]["config"]["active_per_render"] - lines[1]["config"]["active_per_render"]) <= 1e-3 * lines[0]["config"]["active_per_render"]
     assert other["frozen"] and other["checksum"] != a["checksum"] and other["seeds"]["trainer"] == 3
@@ -816,11 +817,11 @@ def test_bench_gpus_flag_starts_that_many_ranks():
     """`python bench.py --gpus 2` (the driver's command form) must run TWO ranks or fail: with the single-GPU test knobs
     (both ranks on device 0, gloo) it starts torch.distributed.run as a child and relays rank 0's line with n_gpus = 2 —
     the whole multi-rank fitting step on GPU tensors: parameter broadcast, gradient all-reduce from the backward hooks, the
-    early overflow decision, per-rank frame shards; without the knobs on a box with fewer than 2 GPUs it exits non-zero
-    and prints no JSON line (it used to run one rank and report n_gpus 1)."""
+    early overflow decision, per-rank frame shards, and with --full the exchange-off pass; without the knobs on a box with
+    fewer than 2 GPUs it exits non-zero and prints no JSON line (it used to run one rank and report n_gpus 1)."""
     import json
     small = ["--workload", "train_step", "--steps", "3", "--warmup", "1", "--pretrain", "2", "--anchors", "20000",
-             "--height", "272", "--width", "480", "--no-cpu-baseline"]
+             "--height", "272", "--width", "480", "--no-cpu-baseline", "--full"]
     out = _run_bench({"GSVC_DIST_BACKEND": "gloo", "GSVC_SHARE_GPU": "1"}, "--gpus", "2", *small)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -845,11 +846,11 @@ def test_bench_gpus_flag_starts_that_many_ranks():
 def test_bench_runs_its_data_parallel_path_on_a_one_rank_rccl_group():
     """bench.py's own multi-rank code — process-group setup as the driver's command form does it (backend "nccl", device_id), the
     parameter broadcast, the barriers around the timed region, the float64 SUM / MAX reductions of the line's numbers, the
-    exchange-off pass with the re-broadcast — on a real RCCL communicator of ONE rank (GSVC_DP_FORCE=1), replicated exchange and
+    exchange-off pass of --full with the re-broadcast — on a real RCCL communicator of ONE rank (GSVC_DP_FORCE=1), replicated exchange and
     z-range ownership: the line must say backend nccl and carry the gradient_exchange block."""
     import json
     small = ["--workload", "train_step", "--steps", "3", "--warmup", "1", "--pretrain", "2", "--anchors", "20000",
-             "--height", "272", "--width", "480", "--no-cpu-baseline"]
+             "--height", "272", "--width", "480", "--no-cpu-baseline", "--full"]
     for extra, word in (({}, "dense"), ({"GSVC_DP_ZOWN": "1"}, "z-range")):
         out = _run_bench({"GSVC_DP_FORCE": "1", **extra}, "--gpus", "1", *small)
         assert out.returncode == 0, out.stderr[-2000:]

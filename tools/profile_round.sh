@@ -11,7 +11,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
 for w in $WL; do
-  if [ $w = train_step ]; then ARGS="--workload train_step --steps 6 --warmup 2 --pretrain 30 --no-cpu-baseline"; else ARGS="--workload $w --steps 20 --warmup 5 --no-cpu-baseline"; fi
+  if [ $w = train_step ]; then ARGS="--workload train_step --steps 6 --warmup 2 --pretrain 30 --no-cpu-baseline --full"; else ARGS="--workload $w --steps 20 --warmup 5 --no-cpu-baseline --full"; fi
   timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_$w -- python3 $REPO/bench.py $ARGS > $OUT/kt_$w.log 2>&1
   f=$(find $OUT/kt_$w -name "*kernel_stats.csv" | head -1)
   [ -n "$f" ] && python3 $REPO/tools/pmc_extract.py --stats $f 70 > $OUT/${w}_${TAG}_kernel_stats.csv
