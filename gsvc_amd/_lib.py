@@ -145,6 +145,9 @@ _SIGNATURES = {
     "gsvc_raster_forward_ex": (C.c_int, [C.POINTER(RasterSettingsC), _i64, _i64] + [_vp] * 5 + [C.POINTER(RasterSourcesC)] + [_vp] * 6),
     "gsvc_raster_backward_ex": (C.c_int, [C.POINTER(RasterSettingsC), _i64, _i64] + [_vp] * 5 + [C.POINTER(RasterSourcesC)]
                                 + [_vp] * 15),
+    "gsvc_raster_forward_aux": (C.c_int, [C.POINTER(RasterSettingsC), _i64, _i64] + [_vp] * 5 + [C.POINTER(RasterSourcesC)] + [_vp] * 8),
+    "gsvc_raster_backward_aux": (C.c_int, [C.POINTER(RasterSettingsC), _i64, _i64] + [_vp] * 5 + [C.POINTER(RasterSourcesC)]
+                                 + [_vp] * 17),
     "gsvc_raster_binning_layout": (C.c_int, [C.POINTER(RasterSettingsC), _i64, _i64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gsvc_raster_image_layout": (C.c_int, [C.POINTER(RasterSettingsC), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "gsvc_grid_forward": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp]),

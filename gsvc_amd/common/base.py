@@ -28,3 +28,6 @@ class RenderResults:
     dense: bool = False                      # Gaussians = all K slots of every visible anchor; selection_mask marks opacity > 0
     visible_index: typing.Union[torch.Tensor, None] = None    # int64 indices of the visible anchors
     raster_state: typing.Any = None          # rasterizer state whose instance counters have not been read back yet
+    # render(return_depth=, return_alpha=): the rasterizer's per-pixel maps [1, H, W] (sum_i w_i z_i, 1 - T_final); None otherwise
+    rendered_depth: typing.Union[torch.Tensor, None] = None
+    rendered_alpha: typing.Union[torch.Tensor, None] = None

@@ -15,6 +15,7 @@
 #include "raster_common.h"
 
 #include <cstdlib>
+#include <type_traits>
 
 namespace gsvc {
 
@@ -40,9 +41,15 @@ struct PixState {
     float T, tb, d0, d1, d2, bd;  // tb = final_T * (bg . dL/dpixel)
     int last;                     // n_contrib; 0 for a pixel outside the image (no list position is <= 0)
 };
+struct PixStateAux : PixState {
+    float gD, gA;                 // dL/ddepth, dL/dalpha: two more channels of value z_i and 1 on a zero background
+};
 
 struct Sums9 {
     float h, x, y, xx, xy, yy, r, g, b;
+};
+struct Sums10 : Sums9 {
+    float z;                      // the tenth sum, w dL/ddepth (-> dL/dz of the entry)
 };
 
 // Nine sums of FOUR list entries in one pass: 74 cross-lane instructions per four entries (18.5 per entry; rounds 1-3 reduced
@@ -133,14 +140,48 @@ __device__ __forceinline__ void r4_tail(Sums9 &q)
                  : "+v"(q.h), "+v"(q.x), "+v"(q.y), "+v"(q.xx), "+v"(q.xy), "+v"(q.yy), "+v"(q.r), "+v"(q.g), "+v"(q.b));
 }
 
+// The tenth sum (AUX) through the same stages, one register: r1_pair is r4_pair's swap + add for it, r1_tail adds a 16-lane row
+// the way r4_tail adds the ninth (afterwards every lane of row r holds the total of row r's entry).  Each DPP add reads the
+// register the previous one wrote: two wait states apart.
+__device__ __forceinline__ void r1_pair(float &a, float &b, const bool rows16)
+{
+    if (!rows16)
+        asm volatile("s_nop 1\n"
+                     "v_permlane32_swap_b32 %0, %1\n"
+                     "s_nop 1\n"
+                     "v_add_f32 %0, %0, %1\n"
+                     : "+v"(a), "+v"(b));
+    else
+        asm volatile("s_nop 1\n"
+                     "v_permlane16_swap_b32 %0, %1\n"
+                     "s_nop 1\n"
+                     "v_add_f32 %0, %0, %1\n"
+                     : "+v"(a), "+v"(b));
+}
+
+__device__ __forceinline__ void r1_tail(float &q)
+{
+    asm volatile("s_nop 1\n"
+                 "v_add_f32_dpp %0, %0, %0 row_ror:8 row_mask:0xf bank_mask:0xf\n"
+                 "s_nop 1\n"
+                 "v_add_f32_dpp %0, %0, %0 row_half_mirror row_mask:0xf bank_mask:0xf\n"
+                 "s_nop 1\n"
+                 "v_add_f32_dpp %0, %0, %0 quad_perm:[2,3,0,1] row_mask:0xf bank_mask:0xf\n"
+                 "s_nop 1\n"
+                 "v_add_f32_dpp %0, %0, %0 quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n"
+                 : "+v"(q));
+}
+
 
 // One list entry at one pixel, straight-line: a pixel the entry did not contribute to (behind the pixel's last
 // contributor, alpha < 1/255, power > 0, outside the image) runs the same instructions with alpha = 0 and G = 0, which
 // leaves T and bd unchanged (rcp(1) = 1, 0 * cd + 1 * bd = bd) and adds zeros.  No EXEC-mask branches: the compiler's
 // branchy form spent a third of its instructions on zero-filling the nine sums on every path.
-template <bool CLAMP_STOP, bool ZERO_BG>
-__device__ __forceinline__ bool bwd_pixel(PixState &p, float dx, float dy, const float4 &a, const float4 &b, float cb,
-                                          int contributor, Sums9 &s)
+// AUX: the entry's "colour" also has the channels z (depth map) and 1 (alpha map), both on a zero background: they add
+// z gD + gA to cd, and w gD to the tenth sum.
+template <bool CLAMP_STOP, bool ZERO_BG, bool AUX = false, typename PS = PixState, typename S = Sums9>
+__device__ __forceinline__ bool bwd_pixel(PS &p, float dx, float dy, const float4 &a, const float4 &b, float cb,
+                                          int contributor, S &s, float z = 0.f)
 {
     float t1 = a.z * dx;                        // -power*log2(e) = A' dx^2 + C' dy^2 + B' dx dy, conic pre-scaled
     t1 = fmaf(a.w, dy, t1);
@@ -152,12 +193,14 @@ __device__ __forceinline__ bool bwd_pixel(PixState &p, float dx, float dy, const
     const float alpha = valid ? araw : 0.0f;
     // CLAMP_STOP (GSVC_RASTER_CLAMP_STOPS_GRADIENT): where min(0.99, .) is active alpha does not depend on the Gaussian
     const float G = (CLAMP_STOP ? (valid & !(b.y * Graw > ALPHA_MAX)) : valid) ? Graw : 0.0f;
-    const float cd = fmaf(cb, p.d2, fmaf(b.w, p.d1, b.z * p.d0));   // colour . dL/dpixel
+    float cd = fmaf(cb, p.d2, fmaf(b.w, p.d1, b.z * p.d0));   // colour . dL/dpixel
+    if constexpr (AUX) cd = fmaf(z, p.gD, cd + p.gA);
     const float oma = 1.0f - alpha;
     const float inv = __builtin_amdgcn_rcpf(oma);
     p.T *= inv;
     const float w = alpha * p.T;
     s.r = fmaf(w, p.d0, s.r); s.g = fmaf(w, p.d1, s.g); s.b = fmaf(w, p.d2, s.b);
+    if constexpr (AUX) s.z = fmaf(w, p.gD, s.z);
     // ZERO_BG (black background, the reference's default): the background's share T_final (bg . d) / (1 - alpha) is zero
     const float dLda = ZERO_BG ? (cd - p.bd) * p.T : fmaf(cd - p.bd, p.T, -(p.tb * inv));
     p.bd = fmaf(alpha, cd, oma * p.bd);
@@ -177,9 +220,9 @@ __device__ __forceinline__ bool bwd_pixel(PixState &p, float dx, float dy, const
 // h' y^2 with h' = o G dL/dalpha — moments about the TILE centre, which the row's writer shifts to the Gaussian's centre and
 // divides by o once per (tile, Gaussian) (k_blend_bwd_tile's flush).  33 vector instructions per (entry, quadrant), was 39.
 // Only for conics that are positive definite with a margin (the forward's rule): "power > 0" cannot occur there.
-template <bool CLAMP_STOP, bool ZERO_BG>
-__device__ __forceinline__ bool bwd_pixel_poly(PixState &p, float x, float y, float x2, float y2, float xy, const float4 &a,
-                                               const float4 &b, float cb, int contributor, Sums9 &s)
+template <bool CLAMP_STOP, bool ZERO_BG, bool AUX = false, typename PS = PixState, typename S = Sums9>
+__device__ __forceinline__ bool bwd_pixel_poly(PS &p, float x, float y, float x2, float y2, float xy, const float4 &a,
+                                               const float4 &b, float cb, int contributor, S &s, float z = 0.f)
 {
     float t = fmaf(b.y, xy, a.x);
     t = fmaf(a.y, x, t);
@@ -191,12 +234,14 @@ __device__ __forceinline__ bool bwd_pixel_poly(PixState &p, float x, float y, fl
     const bool valid = (contributor <= p.last) & !(araw < ALPHA_MIN);
     const float alpha = valid ? araw : 0.0f;
     const float Gh = (CLAMP_STOP ? (valid & !(oG > ALPHA_MAX)) : valid) ? oG : 0.0f;
-    const float cd = fmaf(cb, p.d2, fmaf(b.w, p.d1, b.z * p.d0));   // colour . dL/dpixel
+    float cd = fmaf(cb, p.d2, fmaf(b.w, p.d1, b.z * p.d0));   // colour . dL/dpixel
+    if constexpr (AUX) cd = fmaf(z, p.gD, cd + p.gA);
     const float oma = 1.0f - alpha;
     const float inv = __builtin_amdgcn_rcpf(oma);
     p.T *= inv;
     const float w = alpha * p.T;
     s.r = fmaf(w, p.d0, s.r); s.g = fmaf(w, p.d1, s.g); s.b = fmaf(w, p.d2, s.b);
+    if constexpr (AUX) s.z = fmaf(w, p.gD, s.z);
     // ZERO_BG (black background, the reference's default): the background's share T_final (bg . d) / (1 - alpha) is zero
     const float dLda = ZERO_BG ? (cd - p.bd) * p.T : fmaf(cd - p.bd, p.T, -(p.tb * inv));
     p.bd = fmaf(alpha, cd, oma * p.bd);
@@ -217,10 +262,16 @@ __device__ __forceinline__ bool bwd_pixel_poly(PixState &p, float x, float y, fl
 #define GSVC_BWD_WAVES 4      // 115-120 VGPRs (27 live sums of the four-entry reduction + 28 of pixel state + the 12 per-lane
                               // polynomial constants); at 5 waves (96) the spills cost more than the fifth wave gives (measured)
 #endif
+#ifndef GSVC_BWD_AUX_WAVES
+#define GSVC_BWD_AUX_WAVES 4
+#endif
 // DBG: the timing experiments / lane-efficiency probe selected by the run-time word `dbg` (GSVC_BWD_DEBUG); the production
 // instantiation (DBG = false) carries none of their code or registers
-template <bool CLAMP_STOP, bool DBG, bool ZERO_BG>
-__global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterParams st, const int32_t *__restrict__ tile_offsets,
+// AUX (gsvc_raster_backward_aux): dL/ddepth and dL/dalpha from ONE trailing RasterAuxGrad argument enter cd (bwd_pixel), z of every
+// staged entry rides in LDS next to it, and a tenth sum w dL/ddepth goes through the reduction into float 9 of the row.  AUX = false
+// has no such argument, LDS or code.
+template <bool CLAMP_STOP, bool DBG, bool ZERO_BG, bool AUX = false, typename... Aux>
+__global__ void __launch_bounds__(64, AUX ? GSVC_BWD_AUX_WAVES : GSVC_BWD_WAVES) k_blend_bwd_tile(RasterParams st, const int32_t *__restrict__ tile_offsets,
                                                        const int32_t *__restrict__ point_list,
                                                        const uint2 *__restrict__ inst_bbox,
                                                        const int32_t *__restrict__ gslot,
@@ -228,20 +279,25 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
                                                        const float *__restrict__ final_T,
                                                        const int32_t *__restrict__ n_contrib,
                                                        const float *__restrict__ dL_dimage, float *__restrict__ rows,
-                                                       const gsvc_raster_counters *__restrict__ counters, int dbg_word)
+                                                       const gsvc_raster_counters *__restrict__ counters, int dbg_word,
+                                                       Aux... aux_arg)
 {
+    static_assert(!AUX || (!DBG && sizeof...(Aux) == 1), "one RasterAuxGrad argument, no timing experiments");
+    constexpr int NS = AUX ? 10 : 9;  // sums per entry
     const int dbg = DBG ? dbg_word : 0;
     __shared__ float4 s_f0[64];     // u v A' B'
     __shared__ float4 s_f1[64];     // C' opacity r g
     __shared__ float2 s_f2[64];     // b, tag = chunk entry | quadrant mask << 8 | list position << 12
-    __shared__ float s_out[64][9];  // per chunk entry: sum h, h dx, h dy, h dx^2, h dx dy, h dy^2, w d0, w d1, w d2
+    __shared__ float s_out[64][NS]; // per chunk entry: sum h, h dx, h dy, h dx^2, h dx dy, h dy^2, w d0, w d1, w d2 (AUX: w dL/ddepth)
     __shared__ float s_park[5][64]; // per lane, across the replay loop: what the flush needs of the lane's own entry (registers
                                     // are what bounds the waves per SIMD here; these six would be live through the whole loop)
     const int lane = threadIdx.x;
     const int tx0 = blockIdx.x * TILE, ty0 = blockIdx.y * TILE;
     const int tile = blockIdx.y * st.gx + blockIdx.x;
     const int HW = st.H * st.W;
-    PixState ps[4];
+    using PS = std::conditional_t<AUX, PixStateAux, PixState>;
+    using Sums = std::conditional_t<AUX, Sums10, Sums9>;
+    PS ps[4];
     // the lane's pixel of quadrant q relative to the tile centre: x = (q & 1 ? xb : xa), y = (q >> 1 ? yb : ya), and the products
     const float xa = (float)(lane & 7) - 7.5f, xb = xa + 8.0f, ya = (float)(lane >> 3) - 7.5f, yb = ya + 8.0f;
     const float px_[4] = {xa, xb, xa, xb}, py_[4] = {ya, ya, yb, yb};
@@ -249,6 +305,16 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
     const float pxy_[4] = {xa * ya, xb * ya, xa * yb, xb * yb};
     const float tcx = (float)tx0 + 7.5f, tcy = (float)ty0 + 7.5f;
     int wl[4];
+    float *s_fz = nullptr;          // AUX: z of the staged entries
+    float4 *s_gda = nullptr;        // AUX: dL/ddepth, dL/dalpha on their way to the quadrant layout (the wide prologue)
+    RasterAuxGrad ax{};
+    if constexpr (AUX) {
+        __shared__ float s_z[64];
+        __shared__ float4 s_g2[2][64];
+        s_fz = s_z;
+        s_gda = &s_g2[0][0];
+        ax = (aux_arg, ...);
+    }
     // every load of the prologue is issued before anything is waited for (one memory round trip): the tile's list bounds,
     // the forward's per-pixel state (tile-major: coalesced) and dL/dpixel — the latter as one 16-byte load per lane and
     // channel (lane l: row l / 4 of the tile, pixels 4 (l % 4) .. + 3), handed to the quadrant layout through LDS
@@ -258,7 +324,7 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
         Tf[q] = final_T[(tile * 4 + q) * 64 + lane];
         ps[q].last = n_contrib[(tile * 4 + q) * 64 + lane];
     }
-    const bool wide = (st.W & 3) == 0;
+    const bool wide = (st.W & 3) == 0 && (!AUX || ax.vec);
     if (wide) {
         const int py = ty0 + (lane >> 2), px = tx0 + 4 * (lane & 3);
         const bool in = py < st.H && px < st.W;
@@ -267,8 +333,15 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
         for (int c = 0; c < 3; c++)
             g[c] = in ? *reinterpret_cast<const float4 *>(dL_dimage + (size_t)c * HW + (size_t)py * st.W + px)
                       : make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 ga[2];
+        if constexpr (AUX) {
+            const size_t o = (size_t)py * st.W + px;
+            ga[0] = in && ax.dL_ddepth ? *reinterpret_cast<const float4 *>(ax.dL_ddepth + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+            ga[1] = in && ax.dL_dalpha ? *reinterpret_cast<const float4 *>(ax.dL_dalpha + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+        }
         float4 *t0 = s_f0, *t1 = s_f1, *t2 = reinterpret_cast<float4 *>(&s_out[0][0]);
         t0[lane] = g[0]; t1[lane] = g[1]; t2[lane] = g[2];
+        if constexpr (AUX) { s_gda[lane] = ga[0]; s_gda[64 + lane] = ga[1]; }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -278,6 +351,10 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
             ps[q].d0 = reinterpret_cast<const float *>(t0)[o];
             ps[q].d1 = reinterpret_cast<const float *>(t1)[o];
             ps[q].d2 = reinterpret_cast<const float *>(t2)[o];
+            if constexpr (AUX) {
+                ps[q].gD = reinterpret_cast<const float *>(s_gda)[o];
+                ps[q].gA = reinterpret_cast<const float *>(s_gda + 64)[o];
+            }
         }
         __builtin_amdgcn_wave_barrier();
     } else {
@@ -289,13 +366,17 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
             ps[q].d0 = inq ? dL_dimage[pix] : 0.f;
             ps[q].d1 = inq ? dL_dimage[HW + pix] : 0.f;
             ps[q].d2 = inq ? dL_dimage[2 * HW + pix] : 0.f;
+            if constexpr (AUX) {
+                ps[q].gD = inq && ax.dL_ddepth ? ax.dL_ddepth[pix] : 0.f;
+                ps[q].gA = inq && ax.dL_dalpha ? ax.dL_dalpha[pix] : 0.f;
+            }
         }
     }
     const int beg = tile_offsets[tile], end = tile_offsets[tile + 1];
     if (counters->overflow || beg == end) return;
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-        PixState &p = ps[q];
+        PS &p = ps[q];
         p.tb = ZERO_BG ? 0.f : Tf[q] * (st.bg0 * p.d0 + st.bg1 * p.d1 + st.bg2 * p.d2);
         p.T = Tf[q];
         p.bd = 0.f;
@@ -338,12 +419,13 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
         }
         // exact ellipse-vs-quadrant test on the bbox survivors (same rule as the forward: raster_common.h)
         float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0;
-        float r2x = 0.f;
+        float r2x = 0.f, r3z = 0.f;
         const float4 *rec = reinterpret_cast<const float4 *>(geom + (id < 0 ? 0 : id));
         if (qm != 0 && !(dbg & 64)) {
             r0 = rec[0];
             r1 = rec[1];
             r2x = rec[2].x;
+            if constexpr (AUX) r3z = rec[3].z;
         }
         {
             const int kn = c1 - 64 - 1 - lane;      // behind the gathers: waiting for them leaves these in flight
@@ -376,6 +458,7 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
                 s_f1[pos] = make_float4(-Cp, -Bp, r1.z, r1.w);
             }
             s_f2[pos] = make_float2(r2x, __int_as_float(lane | (qm << 8) | ((k - beg + 1) << 12)));
+            if constexpr (AUX) s_fz[pos] = r3z;
         }
         const int cnt = (dbg & 8) ? 0 : __popcll(mask);      // timing experiment only: chunk overhead without entries
         {
@@ -390,7 +473,7 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        auto replay = [&](int j, Sums9 &s, int &e) {
+        auto replay = [&](int j, Sums &s, int &e) {
             const float4 a = s_f0[j];
             const float4 b = s_f1[j];
             const float2 c = s_f2[j];
@@ -398,19 +481,21 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
             const int contributor = tag >> 12, quads = (tag >> 8) & 0xf;
             e = tag & 0xff;
             s.h = s.x = s.y = s.xx = s.xy = s.yy = s.r = s.g = s.b = 0.f;
+            float z = 0.f;
+            if constexpr (AUX) { s.z = 0.f; z = s_fz[j]; }
             const float dxb = a.x - (tcx + xa), dyb = a.y - (tcy + ya);      // exact: small integers + halves
             if (dbg & 1) { s.h = dxb; s.x = dyb; return; }     // timing experiment only (GSVC_BWD_DEBUG): no replay
 #pragma unroll
             for (int q = 0; q < 4; q++)
                 if (quads & (1 << q)) {
-                    const bool v = bwd_pixel<CLAMP_STOP, ZERO_BG>(ps[q], dxb - (float)(8 * (q & 1)), dyb - (float)(8 * (q >> 1)), a, b, c.x, contributor, s);
+                    const bool v = bwd_pixel<CLAMP_STOP, ZERO_BG, AUX>(ps[q], dxb - (float)(8 * (q & 1)), dyb - (float)(8 * (q >> 1)), a, b, c.x, contributor, s, z);
                     if (dbg & 128) {      // lane-efficiency probe (tools/bwd_lane_efficiency.py): replays and the lanes they were for
                         probe_replays++;
                         probe_lanes += __popcll(__ballot(v));
                     }
                 }
         };
-        auto replay_poly = [&](int j, Sums9 &s, int &e) {
+        auto replay_poly = [&](int j, Sums &s, int &e) {
             const float4 a = s_f0[j];
             const float4 b = s_f1[j];
             const float2 c = s_f2[j];
@@ -418,29 +503,33 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
             const int contributor = tag >> 12, quads = (tag >> 8) & 0xf;
             e = tag & 0xff;
             s.h = s.x = s.y = s.xx = s.xy = s.yy = s.r = s.g = s.b = 0.f;
+            float z = 0.f;
+            if constexpr (AUX) { s.z = 0.f; z = s_fz[j]; }
 #pragma unroll
             for (int q = 0; q < 4; q++)
                 if (quads & (1 << q))
-                    bwd_pixel_poly<CLAMP_STOP, ZERO_BG>(ps[q], px_[q], py_[q], px2_[q], py2_[q], pxy_[q], a, b, c.x, contributor, s);
+                    bwd_pixel_poly<CLAMP_STOP, ZERO_BG, AUX>(ps[q], px_[q], py_[q], px2_[q], py2_[q], pxy_[q], a, b, c.x, contributor, s, z);
         };
         // four entries per reduction pass (r4_pair / r4_tail above); rows of the reduced registers = entries j, j + 2, j + 1, j + 3.
         // Lane (row r, bank b, t): t = 0 stores value {0,2,1,3}[b], t = 1 value {4,6,5,7}[b], (b, t) = (0, 2) the ninth, into the
         // sums of chunk position j + {0,2,1,3}[r]; a group's missing entries (cnt not a multiple of 4) contribute zeros.
+        // AUX: (b, t) = (0, 3) stores the tenth.
         {
             const int r = lane >> 4, bk = (lane >> 2) & 3, t = lane & 3;
             const int perm_r = ((r & 1) << 1) | (r >> 1), perm_b = ((bk & 1) << 1) | (bk >> 1);
-            const bool wr = t < 2 || (t == 2 && bk == 0);
-            const int off = perm_r * 9 + (t == 0 ? perm_b : (t == 1 ? 4 + perm_b : 8));
+            const bool wr = AUX ? (t < 2 || bk == 0) : (t < 2 || (t == 2 && bk == 0));
+            const int off = perm_r * NS + (t == 0 ? perm_b : (t == 1 ? 4 + perm_b : (AUX && t == 3 ? 9 : 8)));
             float *so = &s_out[0][0];
             auto pass = [&](auto &&replay) {
             for (int j = 0; j < cnt; j += 4) {
-                Sums9 sa, sb, sc, sd;
+                Sums sa, sb, sc, sd;
                 int e_;
                 replay(j, sa, e_);
-                if (j + 1 < cnt) replay(j + 1, sb, e_); else sb.h = sb.x = sb.y = sb.xx = sb.xy = sb.yy = sb.r = sb.g = sb.b = 0.f;
+                if (j + 1 < cnt) replay(j + 1, sb, e_); else { sb.h = sb.x = sb.y = sb.xx = sb.xy = sb.yy = sb.r = sb.g = sb.b = 0.f; if constexpr (AUX) sb.z = 0.f; }
                 if (!(dbg & 2)) r4_pair(sa, sb, false);      // (dbg & 2: timing experiment only, no reduction)
-                if (j + 2 < cnt) replay(j + 2, sc, e_); else sc.h = sc.x = sc.y = sc.xx = sc.xy = sc.yy = sc.r = sc.g = sc.b = 0.f;
-                if (j + 3 < cnt) replay(j + 3, sd, e_); else sd.h = sd.x = sd.y = sd.xx = sd.xy = sd.yy = sd.r = sd.g = sd.b = 0.f;
+                if constexpr (AUX) r1_pair(sa.z, sb.z, false);
+                if (j + 2 < cnt) replay(j + 2, sc, e_); else { sc.h = sc.x = sc.y = sc.xx = sc.xy = sc.yy = sc.r = sc.g = sc.b = 0.f; if constexpr (AUX) sc.z = 0.f; }
+                if (j + 3 < cnt) replay(j + 3, sd, e_); else { sd.h = sd.x = sd.y = sd.xx = sd.xy = sd.yy = sd.r = sd.g = sd.b = 0.f; if constexpr (AUX) sd.z = 0.f; }
                 if (!(dbg & 2)) {
                     r4_pair(sc, sd, false);
                     r4_pair(sa, sc, true);
@@ -448,8 +537,14 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
                 } else {
                     sa.h += sb.h + sc.h + sd.h;
                 }
-                const float v = t == 0 ? sa.xx : (t == 1 ? sa.g : sa.b);
-                if (wr) so[j * 9 + off] = v;
+                if constexpr (AUX) {
+                    r1_pair(sc.z, sd.z, false);
+                    r1_pair(sa.z, sc.z, true);
+                    r1_tail(sa.z);
+                }
+                float v = t == 0 ? sa.xx : (t == 1 ? sa.g : sa.b);
+                if constexpr (AUX) v = t == 3 ? sa.z : v;
+                if (wr) so[j * NS + off] = v;
             }
             };
             if (generic) pass(replay); else pass(replay_poly);
@@ -461,9 +556,9 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
         // the others zeros)
         const int gs_f = __float_as_int(s_park[0][lane]), pos_f = __float_as_int(s_park[1][lane]);
         if (gs_f >= 0) {
-            float v[9];
+            float v[NS];
 #pragma unroll
-            for (int c = 0; c < 9; c++) v[c] = pos_f >= 0 ? s_out[pos_f][c] : 0.f;      // sums by chunk position
+            for (int c = 0; c < NS; c++) v[c] = pos_f >= 0 ? s_out[pos_f][c] : 0.f;     // sums by chunk position
             if (!generic) {
                 // the polynomial replay's moments are of o h about the tile centre: shift to the Gaussian's centre, take o out
                 const float U = s_park[2][lane], V = s_park[3][lane], io = s_park[4][lane];
@@ -478,7 +573,7 @@ __global__ void __launch_bounds__(64, GSVC_BWD_WAVES) k_blend_bwd_tile(RasterPar
             float4 *row = reinterpret_cast<float4 *>(rows + (size_t)gs_f * ROW_FLOATS);
             row[0] = make_float4(v[0], v[1], v[2], v[3]);
             row[1] = make_float4(v[4], v[5], v[6], v[7]);
-            row[2] = make_float4(v[8], 0.f, 0.f, 0.f);
+            row[2] = make_float4(v[8], AUX ? v[NS - 1] : 0.f, 0.f, 0.f);
             row[3] = make_float4(0.f, 0.f, 0.f, 0.f);
         }
         __builtin_amdgcn_wave_barrier();
@@ -501,7 +596,9 @@ constexpr int GBWD_COOP_MIN_ROWS = GSVC_GBWD_COOP_MIN_ROWS;      // rectangles f
 //   SRC_COV  the covariance is read from cov3D; dL_dcov3D gets dL/dSigma per stored number, dL_dscales / dL_drotations zeros.
 //   SRC_SH   dL_dshs[k][c] = dL/dcolour[c] basis_k(dir) where channel c was not clamped (bits in GeomRec::pad), and, in the default
 //            direction convention, the gradient through dir = normalize(p - campos) is added to dL_dmeans3D.
-template <int SRC = 0, typename... Src>
+// AUX: float 9 of the rows (sum of w dL/ddepth, k_blend_bwd_tile<..., true>) is dL/dz, and z = M[2,:3] . p + M[2,3] adds
+// dL/dz M[2,:3] to dL_dmeans3D.
+template <int SRC = 0, bool AUX = false, typename... Src>
 __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, const float *__restrict__ means3D,
                                                       const float *__restrict__ scales,
                                                       const float *__restrict__ rotations,
@@ -542,7 +639,7 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
         if constexpr ((SRC & SRC_SH) != 0) sh_clamp = __float_as_uint(w3.w);
     }
     float4 a0 = make_float4(0.f, 0.f, 0.f, 0.f), a1 = a0;
-    float a2 = 0.f;
+    float a2 = 0.f, az = 0.f;       // az: AUX, dL/dz
     const bool big = act && n_rows >= GBWD_COOP_MIN_ROWS;
     if (act && !big) {
         const float4 *row = reinterpret_cast<const float4 *>(rows + (size_t)goff * ROW_FLOATS);
@@ -551,7 +648,7 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
         // dependent memory round trip per tile of the rectangle)
         for (int j = 0; j < n_rows; j += 4, row += 4 * (ROW_FLOATS / 4)) {
             float4 x0[4], x1[4];
-            float x2[4];
+            float x2[4], xz[4];
             bool hit[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
@@ -560,7 +657,12 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
                 const float4 *r4 = row + u * (ROW_FLOATS / 4);
                 x0[u] = hit[u] ? r4[0] : make_float4(0.f, 0.f, 0.f, 0.f);
                 x1[u] = hit[u] ? r4[1] : make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (AUX) {
+                    const float2 w = hit[u] ? reinterpret_cast<const float2 *>(r4 + 2)[0] : make_float2(0.f, 0.f);
+                    x2[u] = w.x; xz[u] = w.y;
+                } else {
                 x2[u] = hit[u] ? r4[2].x : 0.f;
+                }
             }
 #pragma unroll
             for (int u = 0; u < 4; u++) {
@@ -568,6 +670,7 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
                 a0.x += x0[u].x; a0.y += x0[u].y; a0.z += x0[u].z; a0.w += x0[u].w;
                 a1.x += x1[u].x; a1.y += x1[u].y; a1.z += x1[u].z; a1.w += x1[u].w;
                 a2 += x2[u];
+                if constexpr (AUX) az += xz[u];
             }
         }
     }
@@ -578,10 +681,11 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
         const int gof = __shfl(goff, src, 64);
         const uint32_t bx = (uint32_t)__shfl((int)abx, src, 64), by = (uint32_t)__shfl((int)aby, src, 64);
         const float4 *row0 = reinterpret_cast<const float4 *>(rows + (size_t)gof * ROW_FLOATS);
-        float v[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        constexpr int NS = AUX ? 10 : 9;
+        float v[NS] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // (AUX: the tenth is zero too)
         for (int j = lane; j < n; j += 128) {          // two rows in flight per lane
             float4 p0[2], p1[2];
-            float p2[2];
+            float p2[2], pz[2];
             bool hit[2];
 #pragma unroll
             for (int u = 0; u < 2; u++) {
@@ -591,7 +695,12 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
                 const float4 *r4 = row0 + (size_t)jj * (ROW_FLOATS / 4);
                 p0[u] = hit[u] ? r4[0] : make_float4(0.f, 0.f, 0.f, 0.f);
                 p1[u] = hit[u] ? r4[1] : make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (AUX) {
+                    const float2 t2 = hit[u] ? reinterpret_cast<const float2 *>(r4 + 2)[0] : make_float2(0.f, 0.f);
+                    p2[u] = t2.x; pz[u] = t2.y;
+                } else {
                 p2[u] = hit[u] ? r4[2].x : 0.f;
+                }
             }
 #pragma unroll
             for (int u = 0; u < 2; u++) {
@@ -599,16 +708,18 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
                 v[0] += p0[u].x; v[1] += p0[u].y; v[2] += p0[u].z; v[3] += p0[u].w;
                 v[4] += p1[u].x; v[5] += p1[u].y; v[6] += p1[u].z; v[7] += p1[u].w;
                 v[8] += p2[u];
+                if constexpr (AUX) v[NS - 1] += pz[u];
             }
         }
 #pragma unroll
-        for (int c = 0; c < 9; c++)
+        for (int c = 0; c < NS; c++)
 #pragma unroll
             for (int k = 32; k >= 1; k >>= 1) v[c] += __shfl_xor(v[c], k, 64);
         if (lane == src) {
             a0 = make_float4(v[0], v[1], v[2], v[3]);
             a1 = make_float4(v[4], v[5], v[6], v[7]);
             a2 = v[8];
+            if constexpr (AUX) az = v[NS - 1];
         }
     }
     if (i >= P) return;
@@ -637,6 +748,8 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
         g2[1] = pixel_units ? dv : dv * 0.5f * (float)st.H;
         const float *M = st.m;
         for (int j = 0; j < 3; j++) g3[j] = st.scale * (M[j] * du + M[4 + j] * dv);
+        if constexpr (AUX)
+            for (int j = 0; j < 3; j++) g3[j] = fmaf(az, M[8 + j], g3[j]);
 
         float s0 = 0.f, s1 = 0.f, s2 = 0.f;
         float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -762,7 +875,7 @@ static int raster_backward_impl(const gsvc_raster_settings *settings, int64_t P,
                                 const int32_t *radii, const void *geom, const void *binning, const void *image_state,
                                 const float *dL_dimage, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
                                 float *dL_dopacities, float *dL_dscales, float *dL_drotations, void *scratch, void *stream,
-                                int src_kind = 0, const RasterSrc *src = nullptr)
+                                int src_kind = 0, const RasterSrc *src = nullptr, const RasterAuxGrad *aux = nullptr)
 {
     GSVC_REQUIRE(settings != nullptr, "raster_backward: settings is NULL");
     GSVC_REQUIRE(P >= 0 && P < (int64_t)1 << 31 && max_instances >= 0, "raster_backward: bad sizes");
@@ -791,10 +904,16 @@ static int raster_backward_impl(const gsvc_raster_settings *settings, int64_t P,
             inst_bbox, gslot, (const GeomRec *)geom, final_T, n_contrib, dL_dimage, (float *)scratch, counters, dbg)
         const bool cs = p.flags & GSVC_RASTER_CLAMP_STOPS_GRADIENT;
         const bool zb = p.bg0 == 0.f && p.bg1 == 0.f && p.bg2 == 0.f;
-        if (dbg) { if (cs) GSVC_BWD_LAUNCH(true, true, false); else GSVC_BWD_LAUNCH(false, true, false); }
+#define GSVC_BWD_LAUNCH_AUX(CS, ZB) hipLaunchKernelGGL((k_blend_bwd_tile<CS, false, ZB, true, RasterAuxGrad>), dim3(L.gx, L.gy), dim3(64), 0, s, \
+            p, tile_offsets, point_list, inst_bbox, gslot, (const GeomRec *)geom, final_T, n_contrib, dL_dimage, (float *)scratch, counters, 0, *aux)
+        if (aux) {      // (the timing experiments have no AUX form)
+            if (zb) { if (cs) GSVC_BWD_LAUNCH_AUX(true, true); else GSVC_BWD_LAUNCH_AUX(false, true); }
+            else { if (cs) GSVC_BWD_LAUNCH_AUX(true, false); else GSVC_BWD_LAUNCH_AUX(false, false); }
+        } else if (dbg) { if (cs) GSVC_BWD_LAUNCH(true, true, false); else GSVC_BWD_LAUNCH(false, true, false); }
         else if (zb) { if (cs) GSVC_BWD_LAUNCH(true, false, true); else GSVC_BWD_LAUNCH(false, false, true); }
         else { if (cs) GSVC_BWD_LAUNCH(true, false, false); else GSVC_BWD_LAUNCH(false, false, false); }
 #undef GSVC_BWD_LAUNCH
+#undef GSVC_BWD_LAUNCH_AUX
     }
     {
         ProfScope _prof("k_gaussian_bwd", s);
@@ -803,9 +922,14 @@ static int raster_backward_impl(const gsvc_raster_settings *settings, int64_t P,
                                scales, rotations, opacities, radii, (const GeomRec *)geom, (const float *)scratch, counters,
                                dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, extra...);
         };
-        if (src_kind == SRC_SH) launch(&k_gaussian_bwd<SRC_SH, RasterSrc>, *src);
-        else if (src_kind == SRC_COV) launch(&k_gaussian_bwd<SRC_COV, RasterSrc>, *src);
-        else if (src_kind == (SRC_SH | SRC_COV)) launch(&k_gaussian_bwd<SRC_SH | SRC_COV, RasterSrc>, *src);
+        if (aux) {
+            if (src_kind == SRC_SH) launch(&k_gaussian_bwd<SRC_SH, true, RasterSrc>, *src);
+            else if (src_kind == SRC_COV) launch(&k_gaussian_bwd<SRC_COV, true, RasterSrc>, *src);
+            else if (src_kind == (SRC_SH | SRC_COV)) launch(&k_gaussian_bwd<SRC_SH | SRC_COV, true, RasterSrc>, *src);
+            else launch(&k_gaussian_bwd<0, true>);
+        } else if (src_kind == SRC_SH) launch(&k_gaussian_bwd<SRC_SH, false, RasterSrc>, *src);
+        else if (src_kind == SRC_COV) launch(&k_gaussian_bwd<SRC_COV, false, RasterSrc>, *src);
+        else if (src_kind == (SRC_SH | SRC_COV)) launch(&k_gaussian_bwd<SRC_SH | SRC_COV, false, RasterSrc>, *src);
         else launch(&k_gaussian_bwd<>);
     }
     return check_launch("raster_backward");
@@ -843,4 +967,30 @@ extern "C" int gsvc_raster_backward_ex(const gsvc_raster_settings *settings, int
     return raster_backward_impl(settings, P, max_instances, means3D, opacities, scales, rotations, radii, geom, binning,
                                 image_state, dL_dimage, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales,
                                 dL_drotations, scratch, stream, kind, &src);
+}
+
+extern "C" int gsvc_raster_backward_aux(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
+                                        const float *means3D, const float *colors, const float *opacities,
+                                        const float *scales, const float *rotations, const gsvc_raster_sources *sources,
+                                        const int32_t *radii, const void *geom, const void *binning, const void *image_state,
+                                        const float *dL_dimage, const float *dL_ddepth, const float *dL_dalpha,
+                                        float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities,
+                                        float *dL_dscales, float *dL_drotations, float *dL_dshs, float *dL_dcov3D, void *scratch,
+                                        void *stream)
+{
+    GSVC_REQUIRE(settings != nullptr, "raster_backward_aux: settings is NULL");
+    RasterSrc src;
+    int kind;
+    if (int rc = raster_sources_check("raster_backward_aux", colors, scales, rotations, sources, true, src, kind)) return rc;
+    src.dL_dshs = (kind & SRC_SH) ? dL_dshs : nullptr;
+    src.dL_dcov3D = (kind & SRC_COV) ? dL_dcov3D : nullptr;
+    GSVC_REQUIRE(!src.dL_dcov3D || ((uintptr_t)src.dL_dcov3D & 7u) == 0, "raster_backward_aux: dL_dcov3D must be 8-byte aligned");
+    src.sh_vec = (src.sh_coeffs % 4 == 0 && ((uintptr_t)src.shs & 15u) == 0 && ((uintptr_t)src.dL_dshs & 15u) == 0) ? 1 : 0;
+    RasterAuxGrad aux{dL_ddepth, dL_dalpha, 0};
+    aux.vec = (((uintptr_t)dL_dimage | (uintptr_t)dL_ddepth | (uintptr_t)dL_dalpha) & 15u) == 0 ? 1 : 0;
+    // with neither map's gradient the existing kernels run
+    return raster_backward_impl(settings, P, max_instances, means3D, opacities, scales, rotations, radii, geom, binning,
+                                image_state, dL_dimage, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales,
+                                dL_drotations, scratch, stream, kind, kind ? &src : nullptr,
+                                (dL_ddepth || dL_dalpha) ? &aux : nullptr);
 }

@@ -29,7 +29,8 @@ struct alignas(16) GeomRec {
     uint32_t pad;
 };
 static_assert(sizeof(GeomRec) == 64, "GeomRec must be 64 bytes");
-constexpr int ROW_FLOATS = 16;   // one backward partial-sum row: 9 sums + padding = one 64-B line, written whole
+constexpr int ROW_FLOATS = 16;   // one backward partial-sum row: 9 sums (10 with the depth map's sum w dL/ddepth) + padding
+                                 // = one 64-B line, written whole
 
 // One Gaussian as the binning kernels read it: 32 B.
 constexpr int BIN_SLOTS = 4;     // instance slots resolved by K1's LDS histogram; further tiles ("extras") are placed by K3
@@ -108,6 +109,19 @@ struct RasterSrc {
     int sh_degree, sh_coeffs;
     int sh_vec;                 // shs / dL_dshs rows are 16-byte aligned (sh_coeffs % 4 == 0, aligned bases): float4 access
     float campos[3];
+};
+
+// Optional per-pixel maps of the _aux entry points (gsvc_raster_forward_aux / _backward_aux), as the kernels take them.  As with
+// RasterSrc, a kernel instantiated with AUX = false has no such argument at all, so the existing kernels keep their code.
+//   depth = sum_i w_i z_i (z_i = GeomRec::depth, w_i = alpha_i T_i),  alpha = 1 - T_final
+struct RasterAuxOut {
+    float *depth;               // [H, W] or NULL (not written)
+    float *alpha;               // [H, W] or NULL (not written)
+};
+struct RasterAuxGrad {
+    const float *dL_ddepth;     // [H, W] or NULL (zero)
+    const float *dL_dalpha;     // [H, W] or NULL (zero)
+    int vec;                    // dL_dimage and the given maps are 16-byte aligned: the wide (float4) load of the prologue
 };
 
 // Host-side checks of gsvc_raster_sources for the _ex entry points (raster_fwd.hip): -1 with gsvc_last_error() set on degree

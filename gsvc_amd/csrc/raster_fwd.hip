@@ -1109,12 +1109,16 @@ constexpr float LOG2E = 1.44269504088896340736f;
 // lanes mirrored) and its own front-to-back recurrence with the alpha >= 1/255 and T < 1e-4 decisions.  Every pixel therefore
 // carries what two separate launches give, decision for decision (round 2 composited the opposite view back to front at this
 // view's coordinates without the T stop: 2.5e-3 on isolated pixels).
-template <bool PAIR, bool BACK>
+// AUX (single view): the entry's view-space z (GeomRec::depth) is staged in w_f3 next to it and D += z w accumulates the depth map
+// (one more multiply-add per entry); every decision stays the colour pass's.
+template <bool PAIR, bool BACK, bool AUX = false>
 __device__ __forceinline__ void blend_pass(const RasterParams &st, int beg, int end, const int32_t *__restrict__ point_list,
                                            const uint2 *__restrict__ inst_bbox, const GeomRec *__restrict__ geom,
                                            float4 *w_f0, float4 *w_f1, float2 *w_f2, int lane, int qx0, int qy0, bool inside,
-                                           float &T, float &C0, float &C1, float &C2, int &last)
+                                           float &T, float &C0, float &C1, float &C2, int &last, float *w_f3 = nullptr,
+                                           float *D = nullptr)
 {
+    static_assert(!(AUX && PAIR), "the depth / alpha maps serve the single-view forward");
     // the quadrant and the lane's pixel in THIS pass's view (BACK: mirrored; the image width is a multiple of the tile size)
     const int vqx0 = BACK ? st.W - 8 - qx0 : qx0;
     const int lx = BACK ? 7 - (lane & 7) : (lane & 7);
@@ -1168,6 +1172,7 @@ __device__ __forceinline__ void blend_pass(const RasterParams &st, int beg, int 
                 w_f1[pos] = make_float4(-Cp, -Bp, r1.z, r1.w);
             }
             w_f2[pos] = make_float2(rec[2].x, tagf);
+            if constexpr (AUX) w_f3[pos] = rec[3].z;
         }
         const int cnt = __popcll(mask);
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1200,6 +1205,7 @@ __device__ __forceinline__ void blend_pass(const RasterParams &st, int beg, int 
                 const bool acc = __builtin_amdgcn_inverse_ballot_w64(acc_m);
                 const float w = acc ? alpha * T : 0.0f;
                 C0 += rg.x * w; C1 += rg.y * w; C2 += c.x * w;
+                if constexpr (AUX) *D += w_f3[j] * w;
                 T = acc ? test_T : T;
                 last = acc ? tagv : last;
             };
@@ -1238,6 +1244,7 @@ __device__ __forceinline__ void blend_pass(const RasterParams &st, int beg, int 
                 done |= stop;
                 const float w = acc ? alpha * T : 0.0f;
                 C0 += b.z * w; C1 += b.w * w; C2 += c.x * w;
+                if constexpr (AUX) *D += w_f3[j] * w;
                 T = acc ? test_T : T;
                 last = acc ? tagv : last;
             }
@@ -1248,14 +1255,17 @@ __device__ __forceinline__ void blend_pass(const RasterParams &st, int beg, int 
     }
 }
 
-template <bool PAIR>
+// AUX (single view, gsvc_raster_forward_aux): also the depth and alpha maps of the same composite, from ONE trailing RasterAuxOut
+// argument (AUX = false: none, the kernel is the one it was before the maps existed).
+template <bool PAIR, bool AUX = false, typename... Aux>
 __global__ void __launch_bounds__(256) k_blend(RasterParams st, const int32_t *__restrict__ tile_offsets,
                                                const int32_t *__restrict__ point_list,
                                                const uint2 *__restrict__ inst_bbox, const GeomRec *__restrict__ geom,
                                                float *__restrict__ image, float *__restrict__ final_T,
                                                int32_t *__restrict__ n_contrib,
-                                               const gsvc_raster_counters *__restrict__ counters)
+                                               const gsvc_raster_counters *__restrict__ counters, Aux... aux_arg)
 {
+    static_assert(!AUX || (!PAIR && sizeof...(Aux) == 1), "one RasterAuxOut argument, single view only");
     // per-wave staging of the entries that survive the quadrant test (no cross-wave sharing, no barriers)
     __shared__ float4 s_f0[4][64];  // u v A' B'
     __shared__ float4 s_f1[4][64];  // C' opacity r g
@@ -1271,8 +1281,15 @@ __global__ void __launch_bounds__(256) k_blend(RasterParams st, const int32_t *_
 
     float T = 1.0f, C0 = 0.f, C1 = 0.f, C2 = 0.f;
     int last = 0;
+    float D = 0.f;
+    if constexpr (AUX) {
+        __shared__ float s_f3[4][64];   // z of the staged entries
+        blend_pass<PAIR, false, true>(st, beg, end, point_list, inst_bbox, geom, s_f0[wave], s_f1[wave], s_f2[wave], lane, qx0, qy0,
+                                      inside, T, C0, C1, C2, last, s_f3[wave], &D);
+    } else {
     blend_pass<PAIR, false>(st, beg, end, point_list, inst_bbox, geom, s_f0[wave], s_f1[wave], s_f2[wave], lane, qx0, qy0, inside,
                             T, C0, C1, C2, last);
+    }
     if (!PAIR) {
         // per-pixel state for the backward, TILE-MAJOR (tile, quadrant, lane): one coalesced 256-B store per wave here and
         // one coalesced load per quadrant there; pixels outside the image hold T = 1, last = 0 (nothing contributes)
@@ -1296,6 +1313,11 @@ __global__ void __launch_bounds__(256) k_blend(RasterParams st, const int32_t *_
             image[pix] = C0 + T * st.bg0;
             image[HW + pix] = C1 + T * st.bg1;
             image[2 * HW + pix] = C2 + T * st.bg2;
+            if constexpr (AUX) {
+                const RasterAuxOut &ax = (aux_arg, ...);
+                if (ax.depth) ax.depth[pix] = D;
+                if (ax.alpha) ax.alpha[pix] = 1.0f - T;
+            }
         }
     }
 }
@@ -1387,7 +1409,8 @@ extern "C" int gsvc_raster_visible_masks(const gsvc_raster_settings *const *sett
 static int raster_forward_impl(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
                                const float *means3D, const float *colors, const float *opacities, const float *scales,
                                const float *rotations, float *image, int32_t *radii, void *geom, void *binning,
-                               void *image_state, void *stream, bool pair, int src_kind = 0, const RasterSrc *src = nullptr)
+                               void *image_state, void *stream, bool pair, int src_kind = 0, const RasterSrc *src = nullptr,
+                               const RasterAuxOut *aux = nullptr)
 {
     if (int rc = check_settings(settings, P)) return rc;
     GSVC_REQUIRE(max_instances >= 0 && max_instances < (int64_t)1 << 31, "raster_forward: max_instances out of range");
@@ -1497,6 +1520,9 @@ static int raster_forward_impl(const gsvc_raster_settings *settings, int64_t P, 
         if (pair)
             hipLaunchKernelGGL(k_blend<true>, dim3(L.gx, L.gy), dim3(256), 0, s, p, tile_offsets, point_list, inst_bbox,
                                grec, image, final_T, n_contrib, counters);
+        else if (aux && (aux->depth || aux->alpha))      // (single view: checked by gsvc_raster_forward_aux)
+            hipLaunchKernelGGL((k_blend<false, true, RasterAuxOut>), dim3(L.gx, L.gy), dim3(256), 0, s, p, tile_offsets, point_list,
+                               inst_bbox, grec, image, final_T, n_contrib, counters, *aux);
         else
             hipLaunchKernelGGL(k_blend<false>, dim3(L.gx, L.gy), dim3(256), 0, s, p, tile_offsets, point_list, inst_bbox,
                                grec, image, final_T, n_contrib, counters);
@@ -1580,6 +1606,22 @@ extern "C" int gsvc_raster_forward_ex(const gsvc_raster_settings *settings, int6
     src.sh_vec = (src.sh_coeffs % 4 == 0 && ((uintptr_t)src.shs & 15u) == 0) ? 1 : 0;
     return raster_forward_impl(settings, P, max_instances, means3D, colors, opacities, scales, rotations, image, radii, geom,
                                binning, image_state, stream, false, kind, &src);
+}
+
+extern "C" int gsvc_raster_forward_aux(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
+                                       const float *means3D, const float *colors, const float *opacities,
+                                       const float *scales, const float *rotations, const gsvc_raster_sources *sources,
+                                       float *image, int32_t *radii, void *geom, void *binning, void *image_state, float *depth,
+                                       float *alpha, void *stream)
+{
+    if (int rc = check_settings(settings, P)) return rc;
+    RasterSrc src;
+    int kind;
+    if (int rc = raster_sources_check("raster_forward_aux", colors, scales, rotations, sources, true, src, kind)) return rc;
+    src.sh_vec = (src.sh_coeffs % 4 == 0 && ((uintptr_t)src.shs & 15u) == 0) ? 1 : 0;
+    const RasterAuxOut aux{depth, alpha};
+    return raster_forward_impl(settings, P, max_instances, means3D, colors, opacities, scales, rotations, image, radii, geom,
+                               binning, image_state, stream, false, kind, &src, &aux);
 }
 
 extern "C" int gsvc_raster_forward_pair(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,

@@ -16,7 +16,9 @@ from .preprocess import prefilter_geometry, prefilter_voxel, prefilter_voxels_ma
 
 
 def render(frame, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, retain_grad=False,
-           mode=GenerateMode.TRAINING_FULL_PRECISION):
+           mode=GenerateMode.TRAINING_FULL_PRECISION, return_depth=False, return_alpha=False):
+    """``return_depth`` / ``return_alpha``: also fill RenderResults.rendered_depth / rendered_alpha ([1, H, W], differentiable) with
+    the rasterizer's expected-depth and coverage maps of the same composite (GaussianRasterizer.forward)."""
     visible_mask = prefilter_voxel(frame, pc, pipe, bg_color)
     gss = generate_neural_gaussians(frame, pc, visible_mask, mode)
     # zero tensor whose .grad receives the screen-space gradient (densification statistics read it)
@@ -27,11 +29,17 @@ def render(frame, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, retain
         except Exception:
             pass
     rasterizer = GaussianRasterizer(raster_settings=raster_settings_for(frame, pc, pipe, bg_color, scaling_modifier))
-    rendered_image, radii, num_rendered = rasterizer(
-        means3D=gss.xyz, means2D=screenspace_points, shs=None, colors_precomp=gss.color, opacities=gss.opacity,
-        scales=gss.scaling, rotations=gss.rot, cov3D_precomp=None)
+    rendered_depth = rendered_alpha = None
+    if return_depth or return_alpha:
+        rendered_image, radii, num_rendered, rendered_depth, rendered_alpha = rasterizer(
+            means3D=gss.xyz, means2D=screenspace_points, shs=None, colors_precomp=gss.color, opacities=gss.opacity,
+            scales=gss.scaling, rotations=gss.rot, cov3D_precomp=None, return_depth=return_depth, return_alpha=return_alpha)
+    else:
+        rendered_image, radii, num_rendered = rasterizer(
+            means3D=gss.xyz, means2D=screenspace_points, shs=None, colors_precomp=gss.color, opacities=gss.opacity,
+            scales=gss.scaling, rotations=gss.rot, cov3D_precomp=None)
     return RenderResults(
-        rendered_image=rendered_image, viewspace_points=screenspace_points, visibility_filter=radii > 0,
+        rendered_image=rendered_image, rendered_depth=rendered_depth, rendered_alpha=rendered_alpha, viewspace_points=screenspace_points, visibility_filter=radii > 0,
         visible_mask=visible_mask, radii=radii, active_gaussains=(radii > 0).sum(), num_rendered=num_rendered,
         selection_mask=gss.mask, neural_opacity=gss.neural_opacity, scaling=gss.scaling,
         bit_per_param=gss.bit_per_param, bit_per_feat_param=gss.bit_per_feat_param,

@@ -23,6 +23,11 @@ Both colour sources and both covariance sources of the lineage are built:
 GSVC itself always passes colors_precomp + scales/rotations: that call keeps the original entry points
 (gsvc_raster_forward / _backward); only a call with shs or cov3D_precomp takes the gsvc_raster_*_ex ones.
 
+``forward(..., return_depth=True and / or return_alpha=True)`` also returns the two per-pixel maps of the same composite,
+``depth`` [1, H, W] = sum_i w_i z_i (z_i the view-space z, not normalised: divide by ``alpha`` for the mean depth) and
+``alpha`` [1, H, W] = 1 - T_final, as ``(image, radii, num_rendered, depth, alpha)`` (None for a map not asked for), with
+their backward (gsvc_raster_forward_aux / _backward_aux, any colour / covariance source).  Single view only.
+
 Error behaviour follows the 3DGS lineage: both/neither of shs and colors_precomp, or of scales/rotations
 and cov3D_precomp, raise ``Exception``.  SH colours are single-view only (not in raster_forward(pair=True) /
 rasterize_many).
@@ -145,14 +150,15 @@ _capacity_hint = {}
 
 
 def raster_forward(cs: _lib.RasterSettingsC, means3D, colors, opacities, scales, rotations, max_instances=None,
-                   sync=True, pair=False, readback=False, radii_out=None, side_stream=None, sources=None):
+                   sync=True, pair=False, readback=False, radii_out=None, side_stream=None, sources=None, maps_out=None):
     """Launch the forward pipeline.  Returns (image, radii, state).  With ``sync`` the instance counters
     are read back (16 B) and the call is repeated with a larger instance capacity if it overflowed; without
     it the caller must check ``state.counters()[1]`` itself (``readback``: the counters' copy to the host is queued right
     behind the forward, for resolve_deferred()).  ``pair=True`` returns the two-view frame
     (render(view) + flip(render(opposite view))) / 2 from one pass (inference only, see gsvc_raster_forward_pair).
     ``sources`` (a RasterSourcesC: SH colours and / or a precomputed covariance, single view only) selects
-    gsvc_raster_forward_ex; ``colors`` / ``scales`` + ``rotations`` are then None where it replaces them."""
+    gsvc_raster_forward_ex; ``colors`` / ``scales`` + ``rotations`` are then None where it replaces them.  ``maps_out`` (depth,
+    alpha): [1, H, W] float32 tensors or None, written by gsvc_raster_forward_aux (single view; ``sources`` may be None)."""
     L = _lib.lib()
     P = int(means3D.shape[0])
     dev = means3D.device
@@ -171,7 +177,15 @@ def raster_forward(cs: _lib.RasterSettingsC, means3D, colors, opacities, scales,
         image_state = torch.empty(sizes.image_bytes, dtype=torch.uint8, device=dev)
         image = torch.empty(3, H, W, dtype=torch.float32, device=dev)
         radii = radii_out if radii_out is not None else torch.empty(P, dtype=torch.int32, device=dev)
-        if sources is not None:
+        if maps_out is not None:
+            if pair:
+                raise ValueError("raster_forward: the depth / alpha maps serve the single-view forward only")
+            _lib.check(L.gsvc_raster_forward_aux(C.byref(cs), P, max_instances, _lib.ptr(means3D), _lib.ptr(colors),
+                                                 _lib.ptr(opacities), _lib.ptr(scales), _lib.ptr(rotations),
+                                                 None if sources is None else C.byref(sources), _lib.ptr(image), _lib.ptr(radii),
+                                                 _lib.ptr(geom), _lib.ptr(binning), _lib.ptr(image_state), _lib.ptr(maps_out[0]),
+                                                 _lib.ptr(maps_out[1]), stream), "gsvc_raster_forward_aux")
+        elif sources is not None:
             if pair:
                 raise ValueError("raster_forward: SH colours / cov3D_precomp serve the single-view forward only")
             _lib.check(L.gsvc_raster_forward_ex(C.byref(cs), P, max_instances, _lib.ptr(means3D), _lib.ptr(colors),
@@ -276,11 +290,14 @@ def _sources_c(shs, sh_degree, campos, cov3D):
 
 
 class _RasterizeGaussiansEx(torch.autograd.Function):
-    """The rasterization with SH colours and / or a precomputed 3-D covariance (gsvc_raster_forward_ex / _backward_ex).  The
-    plain call (colors_precomp + scales / rotations) stays on _RasterizeGaussians."""
+    """The rasterization with SH colours and / or a precomputed 3-D covariance (gsvc_raster_forward_ex / _backward_ex), or with
+    the depth / alpha maps (``maps`` = (depth?, alpha?) not (False, False): gsvc_raster_forward_aux / _backward_aux, any sources).
+    Outputs (image, radii, depth or None, alpha or None).  The plain call (colors_precomp + scales / rotations, no maps) stays on
+    _RasterizeGaussians."""
 
     @staticmethod
-    def forward(ctx, means3D, means2D, colors, opacities, scales, rotations, shs, cov3D, cs, sh_degree, campos, holder, sync=True):
+    def forward(ctx, means3D, means2D, colors, opacities, scales, rotations, shs, cov3D, cs, sh_degree, campos, holder, sync=True,
+                maps=(False, False)):
         f32 = lambda t, name: None if t is None else _as_f32(t, name)
         means3D, colors, opacities = _as_f32(means3D, "means3D"), f32(colors, "colors_precomp"), _as_f32(opacities, "opacities")
         scales, rotations, shs, cov3D = f32(scales, "scales"), f32(rotations, "rotations"), f32(shs, "shs"), f32(cov3D, "cov3D_precomp")
@@ -288,34 +305,51 @@ class _RasterizeGaussiansEx(torch.autograd.Function):
             raise ValueError(f"shs must be [P, coefficients, 3], got {tuple(shs.shape)}")
         if cov3D is not None and tuple(cov3D.shape) != (means3D.shape[0], 6):
             raise ValueError(f"cov3D_precomp must be [P, 6], got {tuple(cov3D.shape)}")
-        src = _sources_c(shs, sh_degree, campos, cov3D)
+        src = _sources_c(shs, sh_degree, campos, cov3D) if shs is not None or cov3D is not None else None
+        H, W = cs.image_height, cs.image_width
+        aux = any(maps)
+        depth, alpha = (torch.empty(1, H, W, dtype=torch.float32, device=means3D.device) if want else None for want in maps)
         image, radii, state = raster_forward(cs, means3D, colors, opacities, scales, rotations, sync=sync, readback=not sync,
-                                             sources=src)
-        ctx.state, ctx.src = state, src
+                                             sources=src, maps_out=(depth, alpha) if aux else None)
+        ctx.state, ctx.src, ctx.aux = state, src, aux
         ctx.save_for_backward(means3D, colors, opacities, scales, rotations, shs, cov3D)
         ctx.mark_non_differentiable(radii)
+        ctx.set_materialize_grads(False)
         holder["state"] = state
-        return image, radii
+        return image, radii, depth, alpha
 
     @staticmethod
-    def backward(ctx, grad_image, _grad_radii):
+    def backward(ctx, grad_image, _grad_radii, grad_depth=None, grad_alpha=None):
         means3D, colors, opacities, scales, rotations, shs, cov3D = ctx.saved_tensors
         st = ctx.state
         P = st.P
         dev = means3D.device
-        g = _as_f32(grad_image, "grad_image")
+        H, W = st.cs.image_height, st.cs.image_width
+        # (gradients are not materialised: an output the loss does not use arrives as None; a map's None is a NULL pointer)
+        g = _as_f32(grad_image, "grad_image") if grad_image is not None else torch.zeros(3, H, W, device=dev)
+        gD = _as_f32(grad_depth, "grad_depth") if grad_depth is not None else None
+        gA = _as_f32(grad_alpha, "grad_alpha") if grad_alpha is not None else None
         d3, d2, dc = torch.empty(P, 3, device=dev), torch.empty(P, 3, device=dev), torch.empty(P, 3, device=dev)
         do, ds, dq = torch.empty(P, 1, device=dev), torch.empty(P, 3, device=dev), torch.empty(P, 4, device=dev)
         dsh = torch.empty_like(shs) if shs is not None else None
         dcov = torch.empty(P, 6, device=dev) if cov3D is not None else None
         scratch = torch.empty(backward_scratch_floats(P, st.max_instances), device=dev)
-        _lib.check(_lib.lib().gsvc_raster_backward_ex(
-            C.byref(st.cs), P, st.max_instances, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(opacities), _lib.ptr(scales),
-            _lib.ptr(rotations), C.byref(ctx.src), _lib.ptr(st.radii), _lib.ptr(st.geom), _lib.ptr(st.binning),
-            _lib.ptr(st.image_state), _lib.ptr(g), _lib.ptr(d3), _lib.ptr(d2), _lib.ptr(dc), _lib.ptr(do), _lib.ptr(ds),
-            _lib.ptr(dq), _lib.ptr(dsh), _lib.ptr(dcov), _lib.ptr(scratch), _lib.current_stream(dev)), "gsvc_raster_backward_ex")
+        src = None if ctx.src is None else C.byref(ctx.src)
+        if ctx.aux:
+            _lib.check(_lib.lib().gsvc_raster_backward_aux(
+                C.byref(st.cs), P, st.max_instances, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(opacities), _lib.ptr(scales),
+                _lib.ptr(rotations), src, _lib.ptr(st.radii), _lib.ptr(st.geom), _lib.ptr(st.binning),
+                _lib.ptr(st.image_state), _lib.ptr(g), _lib.ptr(gD), _lib.ptr(gA), _lib.ptr(d3), _lib.ptr(d2), _lib.ptr(dc),
+                _lib.ptr(do), _lib.ptr(ds), _lib.ptr(dq), _lib.ptr(dsh), _lib.ptr(dcov), _lib.ptr(scratch),
+                _lib.current_stream(dev)), "gsvc_raster_backward_aux")
+        else:
+            _lib.check(_lib.lib().gsvc_raster_backward_ex(
+                C.byref(st.cs), P, st.max_instances, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(opacities), _lib.ptr(scales),
+                _lib.ptr(rotations), src, _lib.ptr(st.radii), _lib.ptr(st.geom), _lib.ptr(st.binning),
+                _lib.ptr(st.image_state), _lib.ptr(g), _lib.ptr(d3), _lib.ptr(d2), _lib.ptr(dc), _lib.ptr(do), _lib.ptr(ds),
+                _lib.ptr(dq), _lib.ptr(dsh), _lib.ptr(dcov), _lib.ptr(scratch), _lib.current_stream(dev)), "gsvc_raster_backward_ex")
         return (d3, d2, dc if colors is not None else None, do, ds if scales is not None else None,
-                dq if rotations is not None else None, dsh, dcov, None, None, None, None, None)
+                dq if rotations is not None else None, dsh, dcov, None, None, None, None, None, None)
 
 
 class _RasterizeMany(torch.autograd.Function):
@@ -455,23 +489,26 @@ class GaussianRasterizer(nn.Module):
         return radii
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
-                cov3D_precomp=None):
+                cov3D_precomp=None, *, return_depth=False, return_alpha=False):
         if (shs is None and colors_precomp is None) or (shs is not None and colors_precomp is not None):
             raise Exception("Please provide excatly one of either SHs or precomputed colors!")
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         holder = {}
-        if shs is None and cov3D_precomp is None:
+        maps = (bool(return_depth), bool(return_alpha))
+        depth = alpha = None
+        if shs is None and cov3D_precomp is None and not any(maps):
             image, radii = _RasterizeGaussians.apply(means3D, means2D, colors_precomp, opacities, scales, rotations,
                                                      self._c_settings(), holder, not self.deferred)
         else:
             campos = self._campos() if shs is not None else None
-            image, radii = _RasterizeGaussiansEx.apply(means3D, means2D, colors_precomp, opacities, scales, rotations, shs,
-                                                       cov3D_precomp, self._c_settings(), int(self.raster_settings.sh_degree),
-                                                       campos, holder, not self.deferred)
+            image, radii, depth, alpha = _RasterizeGaussiansEx.apply(
+                means3D, means2D, colors_precomp, opacities, scales, rotations, shs, cov3D_precomp, self._c_settings(),
+                int(self.raster_settings.sh_degree), campos, holder, not self.deferred, maps)
         self.last_state = holder["state"]
-        if self.deferred:      # counters stay on the device: the caller resolves them with resolve_deferred()
-            return image, radii, self.last_state
-        num_rendered = self.last_state.counters()[0]
-        return image, radii, num_rendered
+        # counters stay on the device under `deferred`: the caller resolves them with resolve_deferred()
+        third = self.last_state if self.deferred else self.last_state.counters()[0]
+        if any(maps):
+            return image, radii, third, depth, alpha
+        return image, radii, third

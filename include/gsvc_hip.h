@@ -216,6 +216,26 @@ int gsvc_raster_backward_ex(const gsvc_raster_settings *settings, int64_t P, int
                             float *dL_dscales, float *dL_drotations, float *dL_dshs, float *dL_dcov3D, void *scratch,
                             void *stream);
 
+/* [BOUNDARY] The _ex entry points plus two per-pixel maps of the same composite, the ones 3DGS-lineage code reads next to the
+ * image: depth[H, W] = sum_i w_i z_i (w_i = alpha_i T_i the compositing weight, z_i = viewmatrix[2,:3] . p_i + viewmatrix[2,3]
+ * the view-space z of the slab test; not normalised: the mean depth is depth / alpha) and alpha[H, W] = 1 - T_final.  Every
+ * decision is the image's, under every GSVC_RASTER_* switch.  `sources` may be NULL (colors + scales / rotations).  Each map
+ * pointer may be NULL: that map is not written.  The backward takes dL_ddepth[H, W] and dL_dalpha[H, W] next to dL_dimage, each
+ * may be NULL (= zero): the two maps are two more colour channels (z_i and 1) on a zero background, and dL/dz_i adds
+ * dL/dz_i viewmatrix[2,:3] to dL_dmeans3D.  With both map pointers NULL these are the _ex calls, kernel for kernel.  Single view
+ * only (no _pair form). */
+int gsvc_raster_forward_aux(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
+                            const float *means3D, const float *colors, const float *opacities, const float *scales,
+                            const float *rotations, const gsvc_raster_sources *sources, float *image, int32_t *radii,
+                            void *geom, void *binning, void *image_state, float *depth, float *alpha, void *stream);
+int gsvc_raster_backward_aux(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
+                             const float *means3D, const float *colors, const float *opacities, const float *scales,
+                             const float *rotations, const gsvc_raster_sources *sources, const int32_t *radii,
+                             const void *geom, const void *binning, const void *image_state, const float *dL_dimage,
+                             const float *dL_ddepth, const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D,
+                             float *dL_dcolors, float *dL_dopacities, float *dL_dscales, float *dL_drotations,
+                             float *dL_dshs, float *dL_dcov3D, void *scratch, void *stream);
+
 /* Test/inspection helpers: locate the sorted per-tile lists inside the binning blob.
  * tile_offsets_host_out: byte offset of int32 tile_offsets[T+1]; point_list: byte offset of int32 ids. */
 int gsvc_raster_binning_layout(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,

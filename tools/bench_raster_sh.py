@@ -1,6 +1,7 @@
 """Cost of the rasterizer's optional sources at BASELINE.json configs[1] (1080p, 200 k Gaussians): forward and forward +
 backward through GaussianRasterizer for colors_precomp + scale/rotation (the path GSVC takes), SH colours of degree 0, 1 and 3,
-and a precomputed 3-D covariance.  One process; hipEvents around each call after warm-ups; median of --repeats calls.
+a precomputed 3-D covariance, and the depth / alpha maps (return_depth / return_alpha: aux_fwd, aux_fwd_bwd) next to their
+emulation by a second render with colors_precomp = (z, 1, 0) on a black background (emulated_aux_fwd_bwd).  One process; hipEvents around each call after warm-ups; median of --repeats calls.
 Prints one JSON line (microseconds)."""
 import argparse
 import json
@@ -91,6 +92,43 @@ def main():
             image.backward(dL)
         out[f"{name}_fwd_us"] = round(timed(fwd), 1)
         out[f"{name}_fwd_bwd_us"] = round(timed(fwd_bwd), 1)
+
+    # depth + alpha maps with the image (colors_precomp + scale/rotation, the image's rows above are colors_precomp_*)
+    r = cases["colors_precomp"][0]
+    r0 = make(0)                   # the emulation's second render: black background
+    r.deferred = r0.deferred = True
+    kw = dict(colors_precomp=d["colors"], scales=d["scales"], rotations=d["rotations"])
+    gD, gA = torch.randn(1, H, W, device=dev), torch.randn(1, H, W, device=dev)
+    M2 = torch.tensor(s["viewmatrix"], device=dev, dtype=torch.float32)[2]
+
+    def aux_fwd():
+        with torch.no_grad():
+            r(means3D=d["means3D"], means2D=None, opacities=d["opacities"], return_depth=True, return_alpha=True, **kw)
+
+    def aux_fwd_bwd():
+        for t in d.values():
+            t.grad = None
+        m2 = torch.zeros_like(d["means3D"], requires_grad=True)
+        image, _, _, depth, alpha = r(means3D=d["means3D"], means2D=m2, opacities=d["opacities"], return_depth=True,
+                                      return_alpha=True, **kw)
+        torch.autograd.backward([image, depth, alpha], [dL, gD, gA])
+
+    def emulated_aux_fwd_bwd():
+        for t in d.values():
+            t.grad = None
+        m2 = torch.zeros_like(d["means3D"], requires_grad=True)
+        image, _, _ = r(means3D=d["means3D"], means2D=m2, opacities=d["opacities"], **kw)
+        z = d["means3D"] @ M2[:3] + M2[3]
+        maps, _, _ = r0(means3D=d["means3D"], means2D=m2, opacities=d["opacities"], scales=d["scales"], rotations=d["rotations"],
+                        colors_precomp=torch.stack([z, torch.ones_like(z), torch.zeros_like(z)], dim=1))
+        torch.autograd.backward([image, maps[0], maps[1]], [dL, gD[0], gA[0]])
+    with torch.no_grad():          # size the emulation's instance capacity too (same scene: same lists)
+        r0.deferred = False
+        r0(means3D=d["means3D"], means2D=None, opacities=d["opacities"], **kw)
+        r0.deferred = True
+    out["aux_fwd_us"] = round(timed(aux_fwd), 1)
+    out["aux_fwd_bwd_us"] = round(timed(aux_fwd_bwd), 1)
+    out["emulated_aux_fwd_bwd_us"] = round(timed(emulated_aux_fwd_bwd), 1)
     print(json.dumps(out))
 
 
