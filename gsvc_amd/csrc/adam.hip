@@ -27,6 +27,15 @@ struct AdamBatch {
 };
 
 // omb1 / omb2 = 1 - beta rounded from double (as torch does), not 1.0f - beta: that differs by 5e-5 relative for beta2 = 0.999
+// Which product of a sum is fused into it is the compiler's choice (contraction), and it differs between the call sites: the
+// whole-chunk path evaluates fma(omb1, g, b1 * m) and fma(g, omb2 * g, b2 * v), the piecewise and the scalar path fma(b1, m, omb1 * g)
+// and fma(b2, v, (omb2 * g) * g) (gfx950 ISA, hipcc -O3).  So the same numbers updated through 16-byte-aligned pointers and through
+// misaligned ones (the MLP weight gradients are back-to-back views of one buffer) can differ in the last bit of m, v and p; every
+// path is held to the float64 statement of the update (tests/test_film_adam_gpu.py), not to the other paths bit for bit.  Spelling
+// the fmaf calls out would make the paths agree, and move every fit's trajectory: left as it is.  The choice above is what one
+// compiler version made, and the last bit of every fitted parameter rests on it: another hipcc may choose otherwise and move every
+// fit the same way.  test_adam_unaligned_views prints how many elements differ between the paths (GSVC_PRINT_ERRORS=1) and warns
+// when that picture changes (no difference after the first step, some after the later ones): a warning, since either is correct.
 __device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, float b1, float b2, float omb1, float omb2, float eps,
                                       float step_size, float inv_sqrt_bc2)
 {

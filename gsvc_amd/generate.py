@@ -473,7 +473,8 @@ class _GenTail(torch.autograd.Function):
             _lib.ptr(grid_scaling), _lib.ptr(anchor), lo, hi, rows, K, _lib.ptr(no), _lib.ptr(mask), _lib.ptr(scaling), _lib.ptr(rot),
             _lib.ptr(world), _lib.ptr(xyz), _lib.current_stream(dev)), "gsvc_gen_tail_forward")
         ctx.save_for_backward(op_raw, offset_mask, grid_offsets, neural_offset, scale_rot, grid_scaling, world)
-        ctx.K, ctx.bounds, ctx.anchor_grad = K, (lo, hi), anchor.requires_grad
+        # (not anchor.requires_grad: the contiguous() copy of a strided or expanded anchor, made here without grad mode, has lost it)
+        ctx.K, ctx.bounds, ctx.anchor_grad = K, (lo, hi), ctx.needs_input_grad[6]
         ctx.mark_non_differentiable(mask)
         ctx.set_materialize_grads(False)      # an output nothing differentiates (world without the optical loss) arrives as None, not zeros
         return no, mask, scaling, rot, world, xyz

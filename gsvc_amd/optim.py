@@ -70,10 +70,16 @@ class FusedAdam(torch.optim.Adam):
         if guards:
             import ctypes
             gp = (ctypes.c_void_p * len(guards))(*[g.data_ptr() for g in guards])
-            _lib.check(_lib.lib().gsvc_adam_step_guarded(n, arr, b1, b2, eps, gp, len(guards), _lib.current_stream(dev)),
-                       "gsvc_adam_step_guarded")
+            rc = _lib.lib().gsvc_adam_step_guarded(n, arr, b1, b2, eps, gp, len(guards), _lib.current_stream(dev))
         else:
-            _lib.check(_lib.lib().gsvc_adam_step(n, arr, b1, b2, eps, _lib.current_stream(dev)), "gsvc_adam_step")
+            rc = _lib.lib().gsvc_adam_step(n, arr, b1, b2, eps, _lib.current_stream(dev))
+        if rc != 0:
+            # the library refused the call (five guard words, a NULL pointer): nothing was updated, so the counts advanced above go
+            # back: left one ahead, the next update would take the bias corrections of the wrong step
+            for i in stepped:
+                rows[i][6] -= 1
+            self._step_base.index_add_(0, torch.tensor(stepped, dtype=torch.int64), -torch.ones(len(stepped)))
+            _lib.check(rc, "gsvc_adam_step_guarded" if guards else "gsvc_adam_step")
         if only is not None:
             for p in only:
                 p.grad = None
