@@ -266,6 +266,9 @@ _SIGNATURES = {
     "gsvc_rate_sample_backward": (C.c_int, [C.POINTER(RateSampleC), _vp, _vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
                                             C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _vp, _vp]),
     "gsvc_rate_backward": (C.c_int, [_vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, C.c_int32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gsvc_frames_u8_bytes": (_i64, [C.c_int32, C.c_int32, C.c_int32]),
+    "gsvc_frames_to_u8": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                    _vp, _i64, _vp]),
 }
 
 

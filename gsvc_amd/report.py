@@ -19,10 +19,12 @@ from .ortho_gaussian_renderer import render_frames
 
 
 @torch.no_grad()
-def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_fn=None) -> dict:
+def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_fn=None, eight_bit: bool = False) -> dict:
     """Mean L1 / PSNR / SSIM / MS-SSIM (MS-SSIM only for frames at least 160 pixels high and large enough for 5 scales) of the
     rendered two-view frames, clamped to [0, 1], against ``dataset[i].image``; ``fps`` counts the whole loop's wall time,
-    metrics excluded."""
+    metrics excluded.  ``eight_bit=True``: the metrics are taken on what the decoder delivers — the frames quantised to 8 bits
+    (``frames_out.frames_to_u8``: rgb24, truncating, as the reference's PNGs) / 255 — as a codec's PSNR is, and the result says so
+    (``"eight_bit": True``)."""
     ids = list(range(dataset.len_z_frames)) if frame_ids is None else list(frame_ids)
     frames = [dataset[i] for i in ids]
     for _ in render_frames(frames[:min(len(frames), batch)], pc, pipe, bg_color, batch=batch):      # warm-up, as the reference does
@@ -32,6 +34,10 @@ def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_
     images = [torch.clamp(img, 0.0, 1.0) for img in render_frames(frames, pc, pipe, bg_color, batch=batch)]
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if eight_bit and images:
+        from .frames_out import FrameFormat, frames_to_u8, rgb24_to_image
+        H, W = images[0].shape[1:]
+        images = [rgb24_to_image(u8, H, W) for u8 in frames_to_u8(images, FrameFormat("rgb24", rounding="trunc"))]
     sums = {"l1": 0.0, "psnr": 0.0, "ssim": 0.0, "msssim": 0.0, "lpips": 0.0}
     n_ms = 0
     for fr, img in zip(frames, images):
@@ -45,8 +51,11 @@ def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_
         if lpips_fn is not None:
             sums["lpips"] += float(lpips_fn(img, gt, normalize=True))
     n = max(len(frames), 1)
-    return {"frames": len(frames), "l1": sums["l1"] / n, "psnr": sums["psnr"] / n, "ssim": sums["ssim"] / n,
-            "msssim": sums["msssim"] / n_ms if n_ms else float("nan"), "lpips": sums["lpips"] / n if lpips_fn is not None else None, "fps": len(frames) / elapsed if elapsed > 0 else float("inf")}
+    out = {"frames": len(frames), "l1": sums["l1"] / n, "psnr": sums["psnr"] / n, "ssim": sums["ssim"] / n,
+           "msssim": sums["msssim"] / n_ms if n_ms else float("nan"), "lpips": sums["lpips"] / n if lpips_fn is not None else None, "fps": len(frames) / elapsed if elapsed > 0 else float("inf")}
+    if eight_bit:
+        out["eight_bit"] = True
+    return out
 
 
 def _optimizer_state(optimizer):

@@ -888,6 +888,30 @@ int gsvc_octree_expand(const int64_t *nodes, const uint8_t *occ, const int64_t *
                        int64_t *nodes_out, int32_t *error, void *stream);
 int gsvc_morton_decode(const int64_t *keys, int64_t n, int64_t *xyz, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * [INTERNAL] Decoder output: 8-bit frames from the float images of the render loop (replaces the clamp + ToPILImage of reference
+ * utils/report_utils.py:439-445; csrc/frames_out.hip).  One launch converts n (1 .. 16) float32 images [3, H, W] (RGB, nominal
+ * [0, 1], separate allocations, each base 4-byte aligned) into n frames; frame k starts at out + k * out_stride.
+ *   per pixel   c = x > 0 ? x : 0; c = min(c, 1)            (NaN and -inf give 0, +inf gives 1)
+ *   layout      GSVC_FRAMES_RGB24: interleaved [H, W, 3].  GSVC_FRAMES_YUV444P / _YUV420P: planar Y, U (Cb), V (Cr) with
+ *               Y = Kr R + Kg G + Kb B, Cb = (B - Y) / (2 (1 - Kb)), Cr = (R - Y) / (2 (1 - Kr)); 4:2:0 chroma is the plain mean of
+ *               the 2x2 block taken in float before quantisation (centre siting), H and W even, H W 3 / 2 bytes = one I420 frame
+ *   matrix      GSVC_FRAMES_BT709 (Kr 0.2126, Kb 0.0722) or GSVC_FRAMES_BT601 (0.299, 0.114); Kg = 1 - Kr - Kb; ignored for RGB24
+ *   range       GSVC_FRAMES_LIMITED: Y8 = 16 + 219 Y, C8 = 128 + 224 C.  GSVC_FRAMES_FULL: Y8 = 255 Y, C8 = 128 + 255 C.
+ *               RGB24 is always 255 c.  The result is clamped to [0, 255].
+ *   rounding    GSVC_FRAMES_TRUNC: (uint8) v (what ToPILImage does to a float tensor).  GSVC_FRAMES_NEAREST: (uint8)(v + 0.5).
+ * images_host: host array of n device pointers (they travel in the kernel arguments: no upload).  out_stride >= the frame's bytes;
+ * bytes between frames are not written.  gsvc_frames_u8_bytes: bytes of one frame, < 0 for an invalid size or layout.
+ * ---------------------------------------------------------------------------------------------------- */
+#define GSVC_FRAMES_MAX_BATCH 16
+enum { GSVC_FRAMES_RGB24 = 0, GSVC_FRAMES_YUV444P = 1, GSVC_FRAMES_YUV420P = 2 };
+enum { GSVC_FRAMES_BT709 = 0, GSVC_FRAMES_BT601 = 1 };
+enum { GSVC_FRAMES_LIMITED = 0, GSVC_FRAMES_FULL = 1 };
+enum { GSVC_FRAMES_TRUNC = 0, GSVC_FRAMES_NEAREST = 1 };
+int64_t gsvc_frames_u8_bytes(int32_t H, int32_t W, int32_t layout);
+int gsvc_frames_to_u8(const float *const *images_host, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t matrix, int32_t range,
+                      int32_t rounding, uint8_t *out, int64_t out_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

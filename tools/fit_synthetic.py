@@ -20,6 +20,7 @@ built on:
     decodable segment, gsvc_amd/codec.py — at ~0.3 bit per symbol that framing is itself ~5 % and is reported beside it).
 
 usage: python tools/fit_synthetic.py [--steps 2000] [--height 1080 --width 1920 --frames 64 --anchors 100000] [--json out.json]
+                                     [--write-decoded out.y4m]
 """
 import argparse
 import copy
@@ -50,6 +51,8 @@ def main(argv=None):
     ap.add_argument("--dump-coder-inputs", default=None, help="npz of what the first slabs hand to the entropy coder (symbols, mu, sigma)")
     ap.add_argument("--lpips-weights", default=None, help="backbone (+ --lpips-lin-weights) file for gsvc_amd.lpips.LPIPS")
     ap.add_argument("--lpips-lin-weights", default=None)
+    ap.add_argument("--write-decoded", default=None, metavar="PATH",
+                    help="write the decoded 8-bit-MLP model's frames as 8-bit video: .y4m / .yuv (yuv420p), .rgb (rgb24), else a directory of PNGs")
     args = ap.parse_args(argv)
 
     from gsvc_amd.arguments import cfg_20240919
@@ -226,6 +229,11 @@ def main(argv=None):
             lp = lpips_fn_from(args.lpips_weights, lin_weights_path=args.lpips_lin_weights, device=dev)
         ev = evaluate(dec_q, cube, pipe, bg, frame_ids=eval_ids, lpips_fn=lp)
         log["decoded_8bit_mlp"] = ev
+        if args.write_decoded:
+            from gsvc_amd.frames_out import open_sink, write_video
+            sink, fmt = open_sink(args.write_decoded, W, H)
+            log["decoded_video"] = dict(write_video([cube[i] for i in range(T)], dec_q, pipe, bg, sink, fmt=fmt), path=args.write_decoded,
+                                        layout=fmt.layout)
         log["total_bytes"] = int(total_bytes)
         log["bpp"] = 8.0 * total_bytes / (H * W * T)
         log["anchors_final"], log["anchors_coded"] = int(pc._anchor.shape[0]), int(pack.n)
