@@ -870,15 +870,25 @@ extern "C" int64_t gsvc_raster_backward_scratch_bytes(int64_t P, int64_t max_ins
     return (max_instances > 0 ? max_instances : 1) * (int64_t)(ROW_FLOATS * sizeof(float));
 }
 
-static int raster_backward_impl(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
-                                const float *means3D, const float *opacities, const float *scales, const float *rotations,
-                                const int32_t *radii, const void *geom, const void *binning, const void *image_state,
-                                const float *dL_dimage, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
-                                float *dL_dopacities, float *dL_dscales, float *dL_drotations, void *scratch, void *stream,
-                                int src_kind = 0, const RasterSrc *src = nullptr, const RasterAuxGrad *aux = nullptr)
+// The one backward behind gsvc_raster_backward, _ex and _aux.  ex_fn: the name of the _ex / _aux entry point, NULL from the plain
+// one (raster_resolve); each passes NULL for what its signature lacks.  With sources that turn out empty and no map gradient
+// the plain kernels run, with neither map's gradient an _aux call is the _ex call, kernel for kernel.
+static int raster_backward_impl(const char *ex_fn, const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
+                                const float *means3D, const float *colors, const float *opacities, const float *scales,
+                                const float *rotations, const gsvc_raster_sources *sources, const int32_t *radii, const void *geom,
+                                const void *binning, const void *image_state, const float *dL_dimage, const float *dL_ddepth,
+                                const float *dL_dalpha, float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors,
+                                float *dL_dopacities, float *dL_dscales, float *dL_drotations, float *dL_dshs, float *dL_dcov3D,
+                                void *scratch, void *stream)
 {
-    GSVC_REQUIRE(settings != nullptr, "raster_backward: settings is NULL");
-    GSVC_REQUIRE(P >= 0 && P < (int64_t)1 << 31 && max_instances >= 0, "raster_backward: bad sizes");
+    RasterSrc src;
+    int src_kind;
+    if (int rc = raster_resolve(ex_fn, settings, P, colors, scales, rotations, sources, true, dL_dshs, dL_dcov3D, src, src_kind))
+        return rc;
+    const bool aux = dL_ddepth || dL_dalpha;      // with neither map's gradient the existing kernels run
+    const RasterAuxGrad grad{dL_ddepth, dL_dalpha,
+                             (((uintptr_t)dL_dimage | (uintptr_t)dL_ddepth | (uintptr_t)dL_dalpha) & 15u) == 0 ? 1 : 0};
+    GSVC_REQUIRE(max_instances >= 0, "raster_backward: bad sizes");
     if (P == 0) return GSVC_OK;
     GSVC_REQUIRE(means3D && opacities && ((src_kind & SRC_COV) || (scales && rotations)) && radii && geom && binning &&
                      image_state && dL_dimage && scratch,
@@ -900,20 +910,20 @@ static int raster_backward_impl(const gsvc_raster_settings *settings, int64_t P,
     const int dbg = dbg_env | (bwd_probe_enabled() ? 128 : 0);     // gsvc_profile_enable(2): the lane-efficiency probe, at run time
     {
         ProfScope _prof("k_blend_bwd", s);
-#define GSVC_BWD_LAUNCH(CS, DB, ZB) hipLaunchKernelGGL((k_blend_bwd_tile<CS, DB, ZB>), dim3(L.gx, L.gy), dim3(64), 0, s, p, tile_offsets, point_list, \
-            inst_bbox, gslot, (const GeomRec *)geom, final_T, n_contrib, dL_dimage, (float *)scratch, counters, dbg)
         const bool cs = p.flags & GSVC_RASTER_CLAMP_STOPS_GRADIENT;
         const bool zb = p.bg0 == 0.f && p.bg1 == 0.f && p.bg2 == 0.f;
-#define GSVC_BWD_LAUNCH_AUX(CS, ZB) hipLaunchKernelGGL((k_blend_bwd_tile<CS, false, ZB, true, RasterAuxGrad>), dim3(L.gx, L.gy), dim3(64), 0, s, \
-            p, tile_offsets, point_list, inst_bbox, gslot, (const GeomRec *)geom, final_T, n_contrib, dL_dimage, (float *)scratch, counters, 0, *aux)
-        if (aux) {      // (the timing experiments have no AUX form)
-            if (zb) { if (cs) GSVC_BWD_LAUNCH_AUX(true, true); else GSVC_BWD_LAUNCH_AUX(false, true); }
-            else { if (cs) GSVC_BWD_LAUNCH_AUX(true, false); else GSVC_BWD_LAUNCH_AUX(false, false); }
-        } else if (dbg) { if (cs) GSVC_BWD_LAUNCH(true, true, false); else GSVC_BWD_LAUNCH(false, true, false); }
-        else if (zb) { if (cs) GSVC_BWD_LAUNCH(true, false, true); else GSVC_BWD_LAUNCH(false, false, true); }
-        else { if (cs) GSVC_BWD_LAUNCH(true, false, false); else GSVC_BWD_LAUNCH(false, false, false); }
-#undef GSVC_BWD_LAUNCH
-#undef GSVC_BWD_LAUNCH_AUX
+        auto launch = [&](auto kernel, int dbg_arg, auto... extra) {
+            hipLaunchKernelGGL(kernel, dim3(L.gx, L.gy), dim3(64), 0, s, p, tile_offsets, point_list, inst_bbox, gslot,
+                               (const GeomRec *)geom, final_T, n_contrib, dL_dimage, (float *)scratch, counters, dbg_arg, extra...);
+        };
+        // CLAMP_STOP x ZERO_BG, with the maps' trailing RasterAuxGrad argument or without; the timing experiments (DBG) have
+        // neither an AUX nor a ZERO_BG form
+        dispatch_bool(cs, [&](auto c) {
+            constexpr bool CS = decltype(c)::value;
+            if (aux) dispatch_bool(zb, [&](auto z) { launch(&k_blend_bwd_tile<CS, false, decltype(z)::value, true, RasterAuxGrad>, 0, grad); });
+            else if (dbg) launch(&k_blend_bwd_tile<CS, true, false>, dbg);
+            else dispatch_bool(zb, [&](auto z) { launch(&k_blend_bwd_tile<CS, false, decltype(z)::value>, dbg); });
+        });
     }
     {
         ProfScope _prof("k_gaussian_bwd", s);
@@ -922,15 +932,14 @@ static int raster_backward_impl(const gsvc_raster_settings *settings, int64_t P,
                                scales, rotations, opacities, radii, (const GeomRec *)geom, (const float *)scratch, counters,
                                dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, extra...);
         };
-        if (aux) {
-            if (src_kind == SRC_SH) launch(&k_gaussian_bwd<SRC_SH, true, RasterSrc>, *src);
-            else if (src_kind == SRC_COV) launch(&k_gaussian_bwd<SRC_COV, true, RasterSrc>, *src);
-            else if (src_kind == (SRC_SH | SRC_COV)) launch(&k_gaussian_bwd<SRC_SH | SRC_COV, true, RasterSrc>, *src);
-            else launch(&k_gaussian_bwd<0, true>);
-        } else if (src_kind == SRC_SH) launch(&k_gaussian_bwd<SRC_SH, false, RasterSrc>, *src);
-        else if (src_kind == SRC_COV) launch(&k_gaussian_bwd<SRC_COV, false, RasterSrc>, *src);
-        else if (src_kind == (SRC_SH | SRC_COV)) launch(&k_gaussian_bwd<SRC_SH | SRC_COV, false, RasterSrc>, *src);
-        else launch(&k_gaussian_bwd<>);
+        // SRC x AUX; SRC = 0 has no trailing RasterSrc argument
+        dispatch_bool(aux, [&](auto ax) {
+            dispatch_src(src_kind, [&](auto k) {
+                constexpr int SRC = decltype(k)::value;
+                if constexpr (SRC != 0) launch(&k_gaussian_bwd<SRC, decltype(ax)::value, RasterSrc>, src);
+                else launch(&k_gaussian_bwd<0, decltype(ax)::value>);
+            });
+        });
     }
     return check_launch("raster_backward");
 }
@@ -942,10 +951,9 @@ extern "C" int gsvc_raster_backward(const gsvc_raster_settings *settings, int64_
                                     float *dL_dmeans3D, float *dL_dmeans2D, float *dL_dcolors, float *dL_dopacities,
                                     float *dL_dscales, float *dL_drotations, void *scratch, void *stream)
 {
-    (void)colors;
-    return raster_backward_impl(settings, P, max_instances, means3D, opacities, scales, rotations, radii, geom, binning,
-                                image_state, dL_dimage, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales,
-                                dL_drotations, scratch, stream);
+    return raster_backward_impl(nullptr, settings, P, max_instances, means3D, colors, opacities, scales, rotations, nullptr, radii,
+                                geom, binning, image_state, dL_dimage, nullptr, nullptr, dL_dmeans3D, dL_dmeans2D, dL_dcolors,
+                                dL_dopacities, dL_dscales, dL_drotations, nullptr, nullptr, scratch, stream);
 }
 
 extern "C" int gsvc_raster_backward_ex(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
@@ -956,17 +964,9 @@ extern "C" int gsvc_raster_backward_ex(const gsvc_raster_settings *settings, int
                                        float *dL_dopacities, float *dL_dscales, float *dL_drotations, float *dL_dshs,
                                        float *dL_dcov3D, void *scratch, void *stream)
 {
-    GSVC_REQUIRE(settings != nullptr, "raster_backward_ex: settings is NULL");
-    RasterSrc src;
-    int kind;
-    if (int rc = raster_sources_check("raster_backward_ex", colors, scales, rotations, sources, true, src, kind)) return rc;
-    src.dL_dshs = (kind & SRC_SH) ? dL_dshs : nullptr;
-    src.dL_dcov3D = (kind & SRC_COV) ? dL_dcov3D : nullptr;
-    GSVC_REQUIRE(!src.dL_dcov3D || ((uintptr_t)src.dL_dcov3D & 7u) == 0, "raster_backward_ex: dL_dcov3D must be 8-byte aligned");
-    src.sh_vec = (src.sh_coeffs % 4 == 0 && ((uintptr_t)src.shs & 15u) == 0 && ((uintptr_t)src.dL_dshs & 15u) == 0) ? 1 : 0;
-    return raster_backward_impl(settings, P, max_instances, means3D, opacities, scales, rotations, radii, geom, binning,
-                                image_state, dL_dimage, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales,
-                                dL_drotations, scratch, stream, kind, &src);
+    return raster_backward_impl("raster_backward_ex", settings, P, max_instances, means3D, colors, opacities, scales, rotations,
+                                sources, radii, geom, binning, image_state, dL_dimage, nullptr, nullptr, dL_dmeans3D, dL_dmeans2D,
+                                dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, dL_dshs, dL_dcov3D, scratch, stream);
 }
 
 extern "C" int gsvc_raster_backward_aux(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
@@ -978,19 +978,8 @@ extern "C" int gsvc_raster_backward_aux(const gsvc_raster_settings *settings, in
                                         float *dL_dscales, float *dL_drotations, float *dL_dshs, float *dL_dcov3D, void *scratch,
                                         void *stream)
 {
-    GSVC_REQUIRE(settings != nullptr, "raster_backward_aux: settings is NULL");
-    RasterSrc src;
-    int kind;
-    if (int rc = raster_sources_check("raster_backward_aux", colors, scales, rotations, sources, true, src, kind)) return rc;
-    src.dL_dshs = (kind & SRC_SH) ? dL_dshs : nullptr;
-    src.dL_dcov3D = (kind & SRC_COV) ? dL_dcov3D : nullptr;
-    GSVC_REQUIRE(!src.dL_dcov3D || ((uintptr_t)src.dL_dcov3D & 7u) == 0, "raster_backward_aux: dL_dcov3D must be 8-byte aligned");
-    src.sh_vec = (src.sh_coeffs % 4 == 0 && ((uintptr_t)src.shs & 15u) == 0 && ((uintptr_t)src.dL_dshs & 15u) == 0) ? 1 : 0;
-    RasterAuxGrad aux{dL_ddepth, dL_dalpha, 0};
-    aux.vec = (((uintptr_t)dL_dimage | (uintptr_t)dL_ddepth | (uintptr_t)dL_dalpha) & 15u) == 0 ? 1 : 0;
-    // with neither map's gradient the existing kernels run
-    return raster_backward_impl(settings, P, max_instances, means3D, opacities, scales, rotations, radii, geom, binning,
-                                image_state, dL_dimage, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales,
-                                dL_drotations, scratch, stream, kind, kind ? &src : nullptr,
-                                (dL_ddepth || dL_dalpha) ? &aux : nullptr);
+    return raster_backward_impl("raster_backward_aux", settings, P, max_instances, means3D, colors, opacities, scales, rotations,
+                                sources, radii, geom, binning, image_state, dL_dimage, dL_ddepth, dL_dalpha, dL_dmeans3D,
+                                dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, dL_dshs, dL_dcov3D, scratch,
+                                stream);
 }

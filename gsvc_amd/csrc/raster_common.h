@@ -5,6 +5,8 @@
 // diff_gaussian_rasterization.cuda_ortho_gaussian_rasterizer (reference README.md:52; call sites
 // reference ortho_gaussian_renderer/renderer.py:63-98, preprocess.py:58-104).  Spec: DESIGN.md "Raster spec".
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace gsvc {
@@ -124,11 +126,35 @@ struct RasterAuxGrad {
     int vec;                    // dL_dimage and the given maps are 16-byte aligned: the wide (float4) load of the prologue
 };
 
-// Host-side checks of gsvc_raster_sources for the _ex entry points (raster_fwd.hip): -1 with gsvc_last_error() set on degree
-// outside 0..3, too small an sh_coeffs, both or neither colour sources (need_colour) and both or neither covariance sources.
-// Fills the kernels' RasterSrc (campos, degree, pointers) and the SRC_* bits of what was given.
-int raster_sources_check(const char *fn, const float *colors, const float *scales, const float *rotations,
-                         const gsvc_raster_sources *sources, bool need_colour, RasterSrc &src, int &kind);
+// The one host-side resolution step of a rasterizer call (raster_fwd.hip): the settings check, and for an _ex / _aux entry point
+// (fn: its name, for the messages; NULL from the plain entry points, whose signatures have no optional inputs, so that nothing
+// more is looked at) the checks of gsvc_raster_sources: -1 with gsvc_last_error() set on degree outside 0..3, too small an
+// sh_coeffs, both or neither colour sources (need_colour: not for the visibility test), both or neither covariance sources, a
+// cov3D or dL_dcov3D that is not 8-byte aligned.  Fills the kernels' RasterSrc (campos, degree, pointers, sh_vec; dL_dshs /
+// dL_dcov3D: the backward's outputs, kept for the sources given, NULL from a forward) and the SRC_* bits of what was given.
+int raster_resolve(const char *fn, const gsvc_raster_settings *settings, int64_t P, const float *colors, const float *scales,
+                   const float *rotations, const gsvc_raster_sources *sources, bool need_colour, float *dL_dshs,
+                   float *dL_dcov3D, RasterSrc &src, int &kind);
+
+// Compile-time dispatch on a flag and on the SRC_* bits: f(std::bool_constant<b>) / f(std::integral_constant<int, kind>), so that
+// the instantiations of a kernel are chosen in one expression (k_preprocess, k_blend_bwd_tile, k_gaussian_bwd).
+template <typename F>
+inline void dispatch_bool(bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+template <typename F>
+inline void dispatch_src(int kind, F &&f)
+{
+    switch (kind) {
+    case SRC_SH: f(std::integral_constant<int, SRC_SH>{}); break;
+    case SRC_COV: f(std::integral_constant<int, SRC_COV>{}); break;
+    case SRC_SH | SRC_COV: f(std::integral_constant<int, SRC_SH | SRC_COV>{}); break;
+    default: f(std::integral_constant<int, 0>{}); break;
+    }
+}
 
 inline RasterParams make_params(const gsvc_raster_settings &s)
 {

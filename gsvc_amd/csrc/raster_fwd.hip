@@ -1370,20 +1370,81 @@ extern "C" int gsvc_raster_image_layout(const gsvc_raster_settings *settings, ui
     return GSVC_OK;
 }
 
-extern "C" int gsvc_raster_visible_filter(const gsvc_raster_settings *settings, int64_t P, const float *means3D,
-                                          const float *scales, const float *rotations, int32_t *radii, void *stream)
+int gsvc::raster_resolve(const char *fn, const gsvc_raster_settings *settings, int64_t P, const float *colors, const float *scales,
+                         const float *rotations, const gsvc_raster_sources *sources, bool need_colour, float *dL_dshs,
+                         float *dL_dcov3D, RasterSrc &src, int &kind)
 {
+    src = RasterSrc{};
+    kind = 0;
     if (int rc = check_settings(settings, P)) return rc;
+    if (!fn) return GSVC_OK;      // a plain entry point: colors + scales / rotations as given (gsvc_raster_backward never reads colors)
+    const float *shs = sources ? sources->shs : nullptr;
+    const float *cov = sources ? sources->cov3D : nullptr;
+    if (need_colour) {
+        GSVC_REQUIRE((shs != nullptr) != (colors != nullptr), "%s: give exactly one of shs and colors (got %s)", fn,
+                     shs ? "both" : "neither");
+        if (shs) {
+            GSVC_REQUIRE(sources->sh_degree >= 0 && sources->sh_degree <= 3, "%s: sh_degree must be 0..3 (got %d)", fn,
+                         (int)sources->sh_degree);
+            const int need = (sources->sh_degree + 1) * (sources->sh_degree + 1);
+            GSVC_REQUIRE(sources->sh_coeffs >= need && sources->sh_coeffs <= (1 << 20),
+                         "%s: sh_coeffs (%d) must be >= (sh_degree+1)^2 = %d", fn, (int)sources->sh_coeffs, need);
+            kind |= SRC_SH;
+            src.shs = shs;
+            src.dL_dshs = dL_dshs;
+            src.sh_degree = sources->sh_degree;
+            src.sh_coeffs = sources->sh_coeffs;
+            for (int c = 0; c < 3; c++) src.campos[c] = sources->campos[c];
+        }
+    }
+    const bool sr = scales != nullptr && rotations != nullptr;
+    GSVC_REQUIRE((cov != nullptr) != sr, "%s: give exactly one of cov3D and scales + rotations (got %s)", fn,
+                 cov ? "both" : "neither");
+    if (cov) {
+        GSVC_REQUIRE(((uintptr_t)cov & 7u) == 0, "%s: cov3D must be 8-byte aligned", fn);
+        GSVC_REQUIRE(((uintptr_t)dL_dcov3D & 7u) == 0, "%s: dL_dcov3D must be 8-byte aligned", fn);
+        kind |= SRC_COV;
+        src.cov3D = cov;
+        src.dL_dcov3D = dL_dcov3D;
+    }
+    // float4 access to the SH rows and, in the backward, to their gradient's (a forward has no dL_dshs: NULL counts as aligned)
+    src.sh_vec = (src.sh_coeffs % 4 == 0 && (((uintptr_t)src.shs | (uintptr_t)src.dL_dshs) & 15u) == 0) ? 1 : 0;
+    return GSVC_OK;
+}
+
+// The one body of gsvc_raster_visible_filter and _visible_filter_ex (ex_fn: the latter's name, else NULL; see raster_resolve).
+static int visible_filter_impl(const char *ex_fn, const gsvc_raster_settings *settings, int64_t P, const float *means3D,
+                               const float *scales, const float *rotations, const gsvc_raster_sources *sources, int32_t *radii,
+                               void *stream)
+{
+    RasterSrc src;
+    int kind;
+    if (int rc = raster_resolve(ex_fn, settings, P, nullptr, scales, rotations, sources, false, nullptr, nullptr, src, kind)) return rc;
     if (P == 0) return GSVC_OK;
-    GSVC_REQUIRE(means3D && scales && rotations && radii, "visible_filter: NULL pointer");
+    const char *fn = ex_fn ? ex_fn : "visible_filter";
+    GSVC_REQUIRE(means3D && radii && (kind || (scales && rotations)), "%s: NULL pointer", fn);
     const RasterParams p = make_params(*settings);
     hipStream_t s = (hipStream_t)stream;
     {
         ProfScope _prof("k_visible_filter", s);
-        hipLaunchKernelGGL(k_visible_filter, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, p, (int)P, means3D,
-                           scales, rotations, radii);
+        const dim3 grid((unsigned)((P + 255) / 256));
+        if (kind) hipLaunchKernelGGL(k_visible_filter_cov, grid, dim3(256), 0, s, p, (int)P, means3D, src.cov3D, radii);
+        else hipLaunchKernelGGL(k_visible_filter, grid, dim3(256), 0, s, p, (int)P, means3D, scales, rotations, radii);
     }
-    return check_launch("visible_filter");
+    return check_launch(fn);
+}
+
+extern "C" int gsvc_raster_visible_filter(const gsvc_raster_settings *settings, int64_t P, const float *means3D,
+                                          const float *scales, const float *rotations, int32_t *radii, void *stream)
+{
+    return visible_filter_impl(nullptr, settings, P, means3D, scales, rotations, nullptr, radii, stream);
+}
+
+extern "C" int gsvc_raster_visible_filter_ex(const gsvc_raster_settings *settings, int64_t P, const float *means3D,
+                                             const float *scales, const float *rotations, const gsvc_raster_sources *sources,
+                                             int32_t *radii, void *stream)
+{
+    return visible_filter_impl("visible_filter_ex", settings, P, means3D, scales, rotations, sources, radii, stream);
 }
 
 extern "C" int gsvc_raster_visible_masks(const gsvc_raster_settings *const *settings, int32_t views, int64_t P, const float *means3D,
@@ -1406,13 +1467,19 @@ extern "C" int gsvc_raster_visible_masks(const gsvc_raster_settings *const *sett
     return check_launch("visible_masks");
 }
 
-static int raster_forward_impl(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
+// The one forward behind gsvc_raster_forward, _ex, _aux and _pair.  ex_fn: the name of the _ex / _aux entry point, NULL from the
+// plain and pair ones (raster_resolve); each passes NULL for what its signature lacks.  With sources that turn out empty and
+// no map the plain kernels run, with both map pointers NULL an _aux call is the _ex call, kernel for kernel.
+static int raster_forward_impl(const char *ex_fn, const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
                                const float *means3D, const float *colors, const float *opacities, const float *scales,
-                               const float *rotations, float *image, int32_t *radii, void *geom, void *binning,
-                               void *image_state, void *stream, bool pair, int src_kind = 0, const RasterSrc *src = nullptr,
-                               const RasterAuxOut *aux = nullptr)
+                               const float *rotations, const gsvc_raster_sources *sources, float *image, int32_t *radii,
+                               void *geom, void *binning, void *image_state, float *depth, float *alpha, void *stream, bool pair)
 {
-    if (int rc = check_settings(settings, P)) return rc;
+    RasterSrc src;
+    int src_kind;
+    if (int rc = raster_resolve(ex_fn, settings, P, colors, scales, rotations, sources, true, nullptr, nullptr, src, src_kind))
+        return rc;
+    const RasterAuxOut aux{depth, alpha};
     GSVC_REQUIRE(max_instances >= 0 && max_instances < (int64_t)1 << 31, "raster_forward: max_instances out of range");
     GSVC_REQUIRE(image && geom && binning && image_state, "raster_forward: NULL output/state pointer");
     if (pair && (settings->image_width % TILE != 0 || P >= ((int64_t)1 << 29))) {
@@ -1466,20 +1533,16 @@ static int raster_forward_impl(const gsvc_raster_settings *settings, int64_t P, 
                                rotations, radii, grec, brec, tile_count, tile_extra, counters, tile_offsets, big_list, wg_extras,
                                (long long)max_instances, extra...);
         };
-        if (src_kind) {        // (single view: checked by gsvc_raster_forward_ex)
-            const RasterSrc a = *src;
-            switch (src_kind | (use_lds ? 4 : 0)) {
-            case SRC_SH | 4: launch(&k_preprocess<true, false, SRC_SH, RasterSrc>, a); break;
-            case SRC_COV | 4: launch(&k_preprocess<true, false, SRC_COV, RasterSrc>, a); break;
-            case SRC_SH | SRC_COV | 4: launch(&k_preprocess<true, false, SRC_SH | SRC_COV, RasterSrc>, a); break;
-            case SRC_SH: launch(&k_preprocess<false, false, SRC_SH, RasterSrc>, a); break;
-            case SRC_COV: launch(&k_preprocess<false, false, SRC_COV, RasterSrc>, a); break;
-            default: launch(&k_preprocess<false, false, SRC_SH | SRC_COV, RasterSrc>, a); break;
-            }
-        } else if (use_lds && pair) launch(&k_preprocess<true, true>);
-        else if (use_lds) launch(&k_preprocess<true, false>);
-        else if (pair) launch(&k_preprocess<false, true>);
-        else launch(&k_preprocess<false, false>);
+        // USE_LDS x PAIR, or USE_LDS x SRC with the trailing RasterSrc argument: the sources are single view (only the plain and
+        // the pair entry points, which have none, reach here with pair set), so there is no PAIR x SRC kernel
+        dispatch_bool(use_lds, [&](auto lds) {
+            constexpr bool LDS = decltype(lds)::value;
+            if (src_kind)
+                dispatch_src(src_kind, [&](auto k) {
+                    if constexpr (decltype(k)::value != 0) launch(&k_preprocess<LDS, false, decltype(k)::value, RasterSrc>, src);
+                });
+            else dispatch_bool(pair, [&](auto pr) { launch(&k_preprocess<LDS, decltype(pr)::value>); });
+        });
     }
     if (P == 0 || L.tiles > LDS_HIST_MAX_TILES) {      // otherwise the scan ran inside k_preprocess (last workgroup)
         ProfScope _prof("k_scan_tiles", s);
@@ -1520,9 +1583,9 @@ static int raster_forward_impl(const gsvc_raster_settings *settings, int64_t P, 
         if (pair)
             hipLaunchKernelGGL(k_blend<true>, dim3(L.gx, L.gy), dim3(256), 0, s, p, tile_offsets, point_list, inst_bbox,
                                grec, image, final_T, n_contrib, counters);
-        else if (aux && (aux->depth || aux->alpha))      // (single view: checked by gsvc_raster_forward_aux)
+        else if (depth || alpha)      // (single view: only gsvc_raster_forward_aux has them)
             hipLaunchKernelGGL((k_blend<false, true, RasterAuxOut>), dim3(L.gx, L.gy), dim3(256), 0, s, p, tile_offsets, point_list,
-                               inst_bbox, grec, image, final_T, n_contrib, counters, *aux);
+                               inst_bbox, grec, image, final_T, n_contrib, counters, aux);
         else
             hipLaunchKernelGGL(k_blend<false>, dim3(L.gx, L.gy), dim3(256), 0, s, p, tile_offsets, point_list, inst_bbox,
                                grec, image, final_T, n_contrib, counters);
@@ -1535,63 +1598,8 @@ extern "C" int gsvc_raster_forward(const gsvc_raster_settings *settings, int64_t
                                    const float *scales, const float *rotations, float *image, int32_t *radii,
                                    void *geom, void *binning, void *image_state, void *stream)
 {
-    return raster_forward_impl(settings, P, max_instances, means3D, colors, opacities, scales, rotations, image, radii, geom,
-                               binning, image_state, stream, false);
-}
-
-int gsvc::raster_sources_check(const char *fn, const float *colors, const float *scales, const float *rotations,
-                         const gsvc_raster_sources *sources, bool need_colour, RasterSrc &src, int &kind)
-{
-    src = RasterSrc{};
-    kind = 0;
-    const float *shs = sources ? sources->shs : nullptr;
-    const float *cov = sources ? sources->cov3D : nullptr;
-    if (need_colour) {
-        GSVC_REQUIRE((shs != nullptr) != (colors != nullptr), "%s: give exactly one of shs and colors (got %s)", fn,
-                     shs ? "both" : "neither");
-        if (shs) {
-            GSVC_REQUIRE(sources->sh_degree >= 0 && sources->sh_degree <= 3, "%s: sh_degree must be 0..3 (got %d)", fn,
-                         (int)sources->sh_degree);
-            const int need = (sources->sh_degree + 1) * (sources->sh_degree + 1);
-            GSVC_REQUIRE(sources->sh_coeffs >= need && sources->sh_coeffs <= (1 << 20),
-                         "%s: sh_coeffs (%d) must be >= (sh_degree+1)^2 = %d", fn, (int)sources->sh_coeffs, need);
-            kind |= SRC_SH;
-            src.shs = shs;
-            src.sh_degree = sources->sh_degree;
-            src.sh_coeffs = sources->sh_coeffs;
-            for (int c = 0; c < 3; c++) src.campos[c] = sources->campos[c];
-        }
-    }
-    const bool sr = scales != nullptr && rotations != nullptr;
-    GSVC_REQUIRE((cov != nullptr) != sr, "%s: give exactly one of cov3D and scales + rotations (got %s)", fn,
-                 cov ? "both" : "neither");
-    if (cov) {
-        GSVC_REQUIRE(((uintptr_t)cov & 7u) == 0, "%s: cov3D must be 8-byte aligned", fn);
-        kind |= SRC_COV;
-        src.cov3D = cov;
-    }
-    return GSVC_OK;
-}
-
-extern "C" int gsvc_raster_visible_filter_ex(const gsvc_raster_settings *settings, int64_t P, const float *means3D,
-                                             const float *scales, const float *rotations, const gsvc_raster_sources *sources,
-                                             int32_t *radii, void *stream)
-{
-    if (int rc = check_settings(settings, P)) return rc;
-    RasterSrc src;
-    int kind;
-    if (int rc = raster_sources_check("visible_filter_ex", nullptr, scales, rotations, sources, false, src, kind)) return rc;
-    if (!kind) return gsvc_raster_visible_filter(settings, P, means3D, scales, rotations, radii, stream);
-    if (P == 0) return GSVC_OK;
-    GSVC_REQUIRE(means3D && radii, "visible_filter_ex: NULL pointer");
-    const RasterParams p = make_params(*settings);
-    hipStream_t s = (hipStream_t)stream;
-    {
-        ProfScope _prof("k_visible_filter", s);
-        hipLaunchKernelGGL(k_visible_filter_cov, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, s, p, (int)P, means3D,
-                           src.cov3D, radii);
-    }
-    return check_launch("visible_filter_ex");
+    return raster_forward_impl(nullptr, settings, P, max_instances, means3D, colors, opacities, scales, rotations, nullptr, image,
+                               radii, geom, binning, image_state, nullptr, nullptr, stream, false);
 }
 
 extern "C" int gsvc_raster_forward_ex(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
@@ -1599,13 +1607,8 @@ extern "C" int gsvc_raster_forward_ex(const gsvc_raster_settings *settings, int6
                                       const float *scales, const float *rotations, const gsvc_raster_sources *sources,
                                       float *image, int32_t *radii, void *geom, void *binning, void *image_state, void *stream)
 {
-    if (int rc = check_settings(settings, P)) return rc;
-    RasterSrc src;
-    int kind;
-    if (int rc = raster_sources_check("raster_forward_ex", colors, scales, rotations, sources, true, src, kind)) return rc;
-    src.sh_vec = (src.sh_coeffs % 4 == 0 && ((uintptr_t)src.shs & 15u) == 0) ? 1 : 0;
-    return raster_forward_impl(settings, P, max_instances, means3D, colors, opacities, scales, rotations, image, radii, geom,
-                               binning, image_state, stream, false, kind, &src);
+    return raster_forward_impl("raster_forward_ex", settings, P, max_instances, means3D, colors, opacities, scales, rotations,
+                               sources, image, radii, geom, binning, image_state, nullptr, nullptr, stream, false);
 }
 
 extern "C" int gsvc_raster_forward_aux(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
@@ -1614,14 +1617,8 @@ extern "C" int gsvc_raster_forward_aux(const gsvc_raster_settings *settings, int
                                        float *image, int32_t *radii, void *geom, void *binning, void *image_state, float *depth,
                                        float *alpha, void *stream)
 {
-    if (int rc = check_settings(settings, P)) return rc;
-    RasterSrc src;
-    int kind;
-    if (int rc = raster_sources_check("raster_forward_aux", colors, scales, rotations, sources, true, src, kind)) return rc;
-    src.sh_vec = (src.sh_coeffs % 4 == 0 && ((uintptr_t)src.shs & 15u) == 0) ? 1 : 0;
-    const RasterAuxOut aux{depth, alpha};
-    return raster_forward_impl(settings, P, max_instances, means3D, colors, opacities, scales, rotations, image, radii, geom,
-                               binning, image_state, stream, false, kind, &src, &aux);
+    return raster_forward_impl("raster_forward_aux", settings, P, max_instances, means3D, colors, opacities, scales, rotations,
+                               sources, image, radii, geom, binning, image_state, depth, alpha, stream, false);
 }
 
 extern "C" int gsvc_raster_forward_pair(const gsvc_raster_settings *settings, int64_t P, int64_t max_instances,
@@ -1629,6 +1626,6 @@ extern "C" int gsvc_raster_forward_pair(const gsvc_raster_settings *settings, in
                                         const float *scales, const float *rotations, float *image_pair, int32_t *radii,
                                         void *geom, void *binning, void *image_state, void *stream)
 {
-    return raster_forward_impl(settings, P, max_instances, means3D, colors, opacities, scales, rotations, image_pair, radii,
-                               geom, binning, image_state, stream, true);
+    return raster_forward_impl(nullptr, settings, P, max_instances, means3D, colors, opacities, scales, rotations, nullptr,
+                               image_pair, radii, geom, binning, image_state, nullptr, nullptr, stream, true);
 }

@@ -29,15 +29,11 @@ def render(frame, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, retain
         except Exception:
             pass
     rasterizer = GaussianRasterizer(raster_settings=raster_settings_for(frame, pc, pipe, bg_color, scaling_modifier))
-    rendered_depth = rendered_alpha = None
-    if return_depth or return_alpha:
-        rendered_image, radii, num_rendered, rendered_depth, rendered_alpha = rasterizer(
-            means3D=gss.xyz, means2D=screenspace_points, shs=None, colors_precomp=gss.color, opacities=gss.opacity,
-            scales=gss.scaling, rotations=gss.rot, cov3D_precomp=None, return_depth=return_depth, return_alpha=return_alpha)
-    else:
-        rendered_image, radii, num_rendered = rasterizer(
-            means3D=gss.xyz, means2D=screenspace_points, shs=None, colors_precomp=gss.color, opacities=gss.opacity,
-            scales=gss.scaling, rotations=gss.rot, cov3D_precomp=None)
+    # (image, radii, num_rendered), with a map asked for also (depth, alpha)
+    rendered_image, radii, num_rendered, *maps = rasterizer(
+        means3D=gss.xyz, means2D=screenspace_points, shs=None, colors_precomp=gss.color, opacities=gss.opacity,
+        scales=gss.scaling, rotations=gss.rot, cov3D_precomp=None, return_depth=return_depth, return_alpha=return_alpha)
+    rendered_depth, rendered_alpha = maps or (None, None)
     return RenderResults(
         rendered_image=rendered_image, rendered_depth=rendered_depth, rendered_alpha=rendered_alpha, viewspace_points=screenspace_points, visibility_filter=radii > 0,
         visible_mask=visible_mask, radii=radii, active_gaussains=(radii > 0).sum(), num_rendered=num_rendered,

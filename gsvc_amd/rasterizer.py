@@ -20,8 +20,13 @@ Both colour sources and both covariance sources of the lineage are built:
     gradient through dir to dL/dmeans3D;
   * ``cov3D_precomp`` [P, 6] = xx, xy, xz, yy, yz, zz (with ``scales``/``rotations`` None), used as given
     (``scale_modifier`` is not applied, as in the lineage); the backward returns dL/dcov3D_precomp.
-GSVC itself always passes colors_precomp + scales/rotations: that call keeps the original entry points
-(gsvc_raster_forward / _backward); only a call with shs or cov3D_precomp takes the gsvc_raster_*_ex ones.
+
+One host path serves every call: one autograd function (``_RasterizeGaussians``), one foreign call in ``raster_forward`` and one
+in ``_raster_backward`` (which the batched ``_RasterizeMany`` shares), with the entry point chosen by one rule,
+    pair -> gsvc_raster_forward_pair;  else maps -> _forward_aux / _backward_aux;  else shs or cov3D_precomp -> _forward_ex /
+    _backward_ex;  else gsvc_raster_forward / _backward
+(``visible_filter``: cov3D_precomp -> _visible_filter_ex, else gsvc_raster_visible_filter).  GSVC itself always passes
+colors_precomp + scales/rotations without maps, so its calls keep the original entry points and their kernels.
 
 ``forward(..., return_depth=True and / or return_alpha=True)`` also returns the two per-pixel maps of the same composite,
 ``depth`` [1, H, W] = sum_i w_i z_i (z_i the view-space z, not normalised: divide by ``alpha`` for the mean depth) and
@@ -86,12 +91,19 @@ def settings_to_c(rs: GaussianRasterizationSettings) -> _lib.RasterSettingsC:
     return s
 
 
-def _as_f32(t: torch.Tensor, name: str) -> torch.Tensor:
+def _as_f32(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
+    if t is None:       # an input a source replaces, a gradient nothing was computed from
+        return None
     if not t.is_cuda:
         raise RuntimeError(f"{name} must be a CUDA tensor")
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
+
+
+def _inputs_f32(means3D, colors, opacities, scales, rotations):
+    return (_as_f32(means3D, "means3D"), _as_f32(colors, "colors_precomp"), _as_f32(opacities, "opacities"),
+            _as_f32(scales, "scales"), _as_f32(rotations, "rotations"))
 
 
 class RasterState:
@@ -158,7 +170,18 @@ def raster_forward(cs: _lib.RasterSettingsC, means3D, colors, opacities, scales,
     (render(view) + flip(render(opposite view))) / 2 from one pass (inference only, see gsvc_raster_forward_pair).
     ``sources`` (a RasterSourcesC: SH colours and / or a precomputed covariance, single view only) selects
     gsvc_raster_forward_ex; ``colors`` / ``scales`` + ``rotations`` are then None where it replaces them.  ``maps_out`` (depth,
-    alpha): [1, H, W] float32 tensors or None, written by gsvc_raster_forward_aux (single view; ``sources`` may be None)."""
+    alpha): [1, H, W] float32 tensors or None, written by gsvc_raster_forward_aux (single view; ``sources`` may be None).
+    One foreign call: ``pair`` -> _pair, else ``maps_out`` -> _aux, else ``sources`` -> _ex, else gsvc_raster_forward."""
+    if pair and maps_out is not None:
+        raise ValueError("raster_forward: the depth / alpha maps serve the single-view forward only")
+    if pair and sources is not None:
+        raise ValueError("raster_forward: SH colours / cov3D_precomp serve the single-view forward only")
+    # the entry point and what its signature has beyond the plain one's: the sources (_ex, _aux), the two maps (_aux)
+    p = _lib.ptr
+    suffix = "_pair" if pair else "_aux" if maps_out is not None else "_ex" if sources is not None else ""
+    name = "gsvc_raster_forward" + suffix
+    src_arg = (None if sources is None else C.byref(sources),) if suffix in ("_ex", "_aux") else ()
+    maps_arg = (p(maps_out[0]), p(maps_out[1])) if suffix == "_aux" else ()
     L = _lib.lib()
     P = int(means3D.shape[0])
     dev = means3D.device
@@ -177,27 +200,8 @@ def raster_forward(cs: _lib.RasterSettingsC, means3D, colors, opacities, scales,
         image_state = torch.empty(sizes.image_bytes, dtype=torch.uint8, device=dev)
         image = torch.empty(3, H, W, dtype=torch.float32, device=dev)
         radii = radii_out if radii_out is not None else torch.empty(P, dtype=torch.int32, device=dev)
-        if maps_out is not None:
-            if pair:
-                raise ValueError("raster_forward: the depth / alpha maps serve the single-view forward only")
-            _lib.check(L.gsvc_raster_forward_aux(C.byref(cs), P, max_instances, _lib.ptr(means3D), _lib.ptr(colors),
-                                                 _lib.ptr(opacities), _lib.ptr(scales), _lib.ptr(rotations),
-                                                 None if sources is None else C.byref(sources), _lib.ptr(image), _lib.ptr(radii),
-                                                 _lib.ptr(geom), _lib.ptr(binning), _lib.ptr(image_state), _lib.ptr(maps_out[0]),
-                                                 _lib.ptr(maps_out[1]), stream), "gsvc_raster_forward_aux")
-        elif sources is not None:
-            if pair:
-                raise ValueError("raster_forward: SH colours / cov3D_precomp serve the single-view forward only")
-            _lib.check(L.gsvc_raster_forward_ex(C.byref(cs), P, max_instances, _lib.ptr(means3D), _lib.ptr(colors),
-                                                _lib.ptr(opacities), _lib.ptr(scales), _lib.ptr(rotations), C.byref(sources),
-                                                _lib.ptr(image), _lib.ptr(radii), _lib.ptr(geom), _lib.ptr(binning),
-                                                _lib.ptr(image_state), stream), "gsvc_raster_forward_ex")
-        else:
-            fn = L.gsvc_raster_forward_pair if pair else L.gsvc_raster_forward
-            _lib.check(fn(C.byref(cs), P, max_instances, _lib.ptr(means3D), _lib.ptr(colors),
-                                             _lib.ptr(opacities), _lib.ptr(scales), _lib.ptr(rotations), _lib.ptr(image),
-                                             _lib.ptr(radii), _lib.ptr(geom), _lib.ptr(binning), _lib.ptr(image_state), stream),
-                       "gsvc_raster_forward")
+        _lib.check(getattr(L, name)(C.byref(cs), P, max_instances, p(means3D), p(colors), p(opacities), p(scales), p(rotations),
+                                    *src_arg, p(image), p(radii), p(geom), p(binning), p(image_state), *maps_arg, stream), name)
         state = RasterState(cs, P, max_instances, geom, binning, image_state, radii)
         if not sync and readback:
             # the counters are final once the forward kernels have run: their 16 bytes start travelling to the host
@@ -245,40 +249,6 @@ def backward_scratch_floats(P: int, max_instances: int) -> int:
     return int(_lib.lib().gsvc_raster_backward_scratch_bytes(int(P), int(max_instances))) // 4
 
 
-class _RasterizeGaussians(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, means3D, means2D, colors, opacities, scales, rotations, cs, holder, sync=True):
-        means3D, colors = _as_f32(means3D, "means3D"), _as_f32(colors, "colors_precomp")
-        opacities, scales, rotations = _as_f32(opacities, "opacities"), _as_f32(scales, "scales"), _as_f32(rotations, "rotations")
-        image, radii, state = raster_forward(cs, means3D, colors, opacities, scales, rotations, sync=sync, readback=not sync)
-        ctx.state = state
-        ctx.save_for_backward(means3D, colors, opacities, scales, rotations)
-        ctx.mark_non_differentiable(radii)
-        holder["state"] = state
-        return image, radii
-
-    @staticmethod
-    def backward(ctx, grad_image, _grad_radii):
-        means3D, colors, opacities, scales, rotations = ctx.saved_tensors
-        st = ctx.state
-        P = st.P
-        dev = means3D.device
-        g = _as_f32(grad_image, "grad_image")
-        d3 = torch.empty(P, 3, device=dev)
-        d2 = torch.empty(P, 3, device=dev)
-        dc = torch.empty(P, 3, device=dev)
-        do = torch.empty(P, 1, device=dev)
-        ds = torch.empty(P, 3, device=dev)
-        dq = torch.empty(P, 4, device=dev)
-        scratch = torch.empty(backward_scratch_floats(P, st.max_instances), device=dev)
-        _lib.check(_lib.lib().gsvc_raster_backward(
-            C.byref(st.cs), P, st.max_instances, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(opacities),
-            _lib.ptr(scales), _lib.ptr(rotations), _lib.ptr(st.radii), _lib.ptr(st.geom), _lib.ptr(st.binning),
-            _lib.ptr(st.image_state), _lib.ptr(g), _lib.ptr(d3), _lib.ptr(d2), _lib.ptr(dc), _lib.ptr(do), _lib.ptr(ds),
-            _lib.ptr(dq), _lib.ptr(scratch), _lib.current_stream(dev)), "gsvc_raster_backward")
-        return d3, d2, dc, do, ds, dq, None, None, None
-
-
 def _sources_c(shs, sh_degree, campos, cov3D):
     """gsvc_raster_sources for the tensors given (None: that source is not used)."""
     src = _lib.RasterSourcesC()
@@ -289,18 +259,46 @@ def _sources_c(shs, sh_degree, campos, cov3D):
     return src
 
 
-class _RasterizeGaussiansEx(torch.autograd.Function):
-    """The rasterization with SH colours and / or a precomputed 3-D covariance (gsvc_raster_forward_ex / _backward_ex), or with
-    the depth / alpha maps (``maps`` = (depth?, alpha?) not (False, False): gsvc_raster_forward_aux / _backward_aux, any sources).
-    Outputs (image, radii, depth or None, alpha or None).  The plain call (colors_precomp + scales / rotations, no maps) stays on
-    _RasterizeGaussians."""
+def _grad_buffers(n, dev):
+    """The six gradient tensors of n Gaussians: means3D, means2D, colors, opacities, scales, rotations."""
+    return tuple(torch.empty(n, k, device=dev) for k in (3, 3, 3, 1, 3, 4))
+
+
+def _backward_scratch(st, dev):
+    return torch.empty(backward_scratch_floats(st.P, st.max_instances), device=dev)
+
+
+def _raster_backward(st, inputs, g, grads, scratch, stream, src=None, src_grads=(None, None), map_grads=None):
+    """The backward of the forward ``st``, queued on ``stream``: ``inputs`` (means3D, colors, opacities, scales, rotations: the
+    forward's, None where a source replaces one) and the six ``grads`` are the render's own rows, ``g`` its image gradient,
+    ``scratch`` its partial-sum rows.  One foreign call, chosen by raster_forward's rule: ``map_grads`` (dL/ddepth, dL/dalpha,
+    each a tensor or None) -> gsvc_raster_backward_aux, else ``src`` -> _ex (both with ``src_grads`` = dL/dshs, dL/dcov3D),
+    else gsvc_raster_backward."""
+    p = _lib.ptr
+    suffix = "_aux" if map_grads is not None else "_ex" if src is not None else ""
+    name = "gsvc_raster_backward" + suffix
+    args = [C.byref(st.cs), st.P, st.max_instances, *map(p, inputs)]
+    if suffix:
+        args.append(None if src is None else C.byref(src))
+    args += (p(st.radii), p(st.geom), p(st.binning), p(st.image_state), p(g))
+    if map_grads is not None:
+        args += map(p, map_grads)
+    args += map(p, grads)
+    if suffix:
+        args += map(p, src_grads)
+    _lib.check(getattr(_lib.lib(), name)(*args, p(scratch), stream), name)
+
+
+class _RasterizeGaussians(torch.autograd.Function):
+    """One rasterization: outputs (image, radii, depth or None, alpha or None).  colors_precomp + scales / rotations without maps
+    take gsvc_raster_forward / _backward; SH colours and / or a precomputed 3-D covariance (``shs`` / ``cov3D``, the input they
+    replace is None) the _ex entry points; ``maps`` = (depth?, alpha?) not (False, False) the _aux ones, with any sources."""
 
     @staticmethod
     def forward(ctx, means3D, means2D, colors, opacities, scales, rotations, shs, cov3D, cs, sh_degree, campos, holder, sync=True,
                 maps=(False, False)):
-        f32 = lambda t, name: None if t is None else _as_f32(t, name)
-        means3D, colors, opacities = _as_f32(means3D, "means3D"), f32(colors, "colors_precomp"), _as_f32(opacities, "opacities")
-        scales, rotations, shs, cov3D = f32(scales, "scales"), f32(rotations, "rotations"), f32(shs, "shs"), f32(cov3D, "cov3D_precomp")
+        means3D, colors, opacities, scales, rotations = _inputs_f32(means3D, colors, opacities, scales, rotations)
+        shs, cov3D = _as_f32(shs, "shs"), _as_f32(cov3D, "cov3D_precomp")
         if shs is not None and (shs.dim() != 3 or shs.shape[0] != means3D.shape[0] or shs.shape[2] != 3):
             raise ValueError(f"shs must be [P, coefficients, 3], got {tuple(shs.shape)}")
         if cov3D is not None and tuple(cov3D.shape) != (means3D.shape[0], 6):
@@ -327,27 +325,13 @@ class _RasterizeGaussiansEx(torch.autograd.Function):
         H, W = st.cs.image_height, st.cs.image_width
         # (gradients are not materialised: an output the loss does not use arrives as None; a map's None is a NULL pointer)
         g = _as_f32(grad_image, "grad_image") if grad_image is not None else torch.zeros(3, H, W, device=dev)
-        gD = _as_f32(grad_depth, "grad_depth") if grad_depth is not None else None
-        gA = _as_f32(grad_alpha, "grad_alpha") if grad_alpha is not None else None
-        d3, d2, dc = torch.empty(P, 3, device=dev), torch.empty(P, 3, device=dev), torch.empty(P, 3, device=dev)
-        do, ds, dq = torch.empty(P, 1, device=dev), torch.empty(P, 3, device=dev), torch.empty(P, 4, device=dev)
+        map_grads = (_as_f32(grad_depth, "grad_depth"), _as_f32(grad_alpha, "grad_alpha")) if ctx.aux else None
+        grads = _grad_buffers(P, dev)
         dsh = torch.empty_like(shs) if shs is not None else None
         dcov = torch.empty(P, 6, device=dev) if cov3D is not None else None
-        scratch = torch.empty(backward_scratch_floats(P, st.max_instances), device=dev)
-        src = None if ctx.src is None else C.byref(ctx.src)
-        if ctx.aux:
-            _lib.check(_lib.lib().gsvc_raster_backward_aux(
-                C.byref(st.cs), P, st.max_instances, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(opacities), _lib.ptr(scales),
-                _lib.ptr(rotations), src, _lib.ptr(st.radii), _lib.ptr(st.geom), _lib.ptr(st.binning),
-                _lib.ptr(st.image_state), _lib.ptr(g), _lib.ptr(gD), _lib.ptr(gA), _lib.ptr(d3), _lib.ptr(d2), _lib.ptr(dc),
-                _lib.ptr(do), _lib.ptr(ds), _lib.ptr(dq), _lib.ptr(dsh), _lib.ptr(dcov), _lib.ptr(scratch),
-                _lib.current_stream(dev)), "gsvc_raster_backward_aux")
-        else:
-            _lib.check(_lib.lib().gsvc_raster_backward_ex(
-                C.byref(st.cs), P, st.max_instances, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(opacities), _lib.ptr(scales),
-                _lib.ptr(rotations), src, _lib.ptr(st.radii), _lib.ptr(st.geom), _lib.ptr(st.binning),
-                _lib.ptr(st.image_state), _lib.ptr(g), _lib.ptr(d3), _lib.ptr(d2), _lib.ptr(dc), _lib.ptr(do), _lib.ptr(ds),
-                _lib.ptr(dq), _lib.ptr(dsh), _lib.ptr(dcov), _lib.ptr(scratch), _lib.current_stream(dev)), "gsvc_raster_backward_ex")
+        _raster_backward(st, (means3D, colors, opacities, scales, rotations), g, grads, _backward_scratch(st, dev),
+                         _lib.current_stream(dev), ctx.src, (dsh, dcov), map_grads)
+        d3, d2, dc, do, ds, dq = grads
         return (d3, d2, dc if colors is not None else None, do, ds if scales is not None else None,
                 dq if rotations is not None else None, dsh, dcov, None, None, None, None, None, None)
 
@@ -361,8 +345,7 @@ class _RasterizeMany(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, means3D, means2D, colors, opacities, scales, rotations, cs_list, bounds, holder):
-        means3D, colors = _as_f32(means3D, "means3D"), _as_f32(colors, "colors_precomp")
-        opacities, scales, rotations = _as_f32(opacities, "opacities"), _as_f32(scales, "scales"), _as_f32(rotations, "rotations")
+        means3D, colors, opacities, scales, rotations = _inputs_f32(means3D, colors, opacities, scales, rotations)
         N = int(means3D.shape[0])
         radii = torch.empty(N, dtype=torch.int32, device=means3D.device)
         images, states = [], []
@@ -388,44 +371,35 @@ class _RasterizeMany(torch.autograd.Function):
         return (*images, radii)
 
     @staticmethod
-    def backward(ctx, *grads):
-        means3D, colors, opacities, scales, rotations = ctx.saved_tensors
-        N, dev = means3D.shape[0], means3D.device
-        d3, d2, dc = torch.empty(N, 3, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, 3, device=dev)
-        do, ds, dq = torch.empty(N, 1, device=dev), torch.empty(N, 3, device=dev), torch.empty(N, 4, device=dev)
-        L = _lib.lib()
+    def backward(ctx, *grad_images):
+        inputs = ctx.saved_tensors          # means3D, colors, opacities, scales, rotations
+        N, dev = inputs[0].shape[0], inputs[0].device
+        grads = _grad_buffers(N, dev)
         side = schedule.raster_streams(dev, len(ctx.states))
         main = torch.cuda.current_stream(dev)
         # everything the side streams read is produced / allocated on the main stream BEFORE the fork: an image gradient that is
         # not contiguous fp32 (an expanded gradient of images[r].sum(), autocast) is converted by a copy kernel on main, and the
         # scratch rows are allocated there — converting after the fork left the side stream's backward reading the copy's
         # destination with nothing ordering the two
-        gs = [None if g is None else _as_f32(g, "grad_image") for g in grads[:len(ctx.states)]]
-        scratches = [None if g is None else torch.empty(backward_scratch_floats(st.P, st.max_instances), device=dev)
-                     for g, st in zip(gs, ctx.states)]              # alive until the join below
+        gs = [_as_f32(g, "grad_image") for g in grad_images[:len(ctx.states)]]
+        scratches = [None if g is None else _backward_scratch(st, dev) for g, st in zip(gs, ctx.states)]  # alive until the join below
         for r, g in enumerate(gs):
             if g is None:           # a render nothing was computed from: its Gaussians get no gradient
                 a, b = ctx.bounds[r], ctx.bounds[r + 1]
-                for t in (d3, d2, dc, do, ds, dq):
+                for t in grads:
                     t[a:b].zero_()
         for sd in side:
             sd.wait_stream(main)
         for r, st in enumerate(ctx.states):
             a, b = ctx.bounds[r], ctx.bounds[r + 1]
-            g, scratch = gs[r], scratches[r]
-            if g is None:
+            if gs[r] is None:
                 continue
             stream = C.c_void_p(side[r % len(side)].cuda_stream) if side else _lib.current_stream(dev)
-            P = st.P
-            _lib.check(L.gsvc_raster_backward(
-                C.byref(st.cs), P, st.max_instances, _lib.ptr(means3D[a:b]), _lib.ptr(colors[a:b]), _lib.ptr(opacities[a:b]),
-                _lib.ptr(scales[a:b]), _lib.ptr(rotations[a:b]), _lib.ptr(st.radii), _lib.ptr(st.geom), _lib.ptr(st.binning),
-                _lib.ptr(st.image_state), _lib.ptr(g), _lib.ptr(d3[a:b]), _lib.ptr(d2[a:b]), _lib.ptr(dc[a:b]), _lib.ptr(do[a:b]),
-                _lib.ptr(ds[a:b]), _lib.ptr(dq[a:b]), _lib.ptr(scratch), stream), "gsvc_raster_backward")
+            _raster_backward(st, [t[a:b] for t in inputs], gs[r], [t[a:b] for t in grads], scratches[r], stream)
         for sd in side:
             main.wait_stream(sd)
         del scratches, gs
-        return d3, d2, dc, do, ds, dq, None, None, None
+        return (*grads, None, None, None)
 
 
 def rasterize_many(cs_list, bounds, means3D, means2D, colors, opacities, scales, rotations):
@@ -467,25 +441,19 @@ class GaussianRasterizer(nn.Module):
         if ((scales is None or rotations is None) and cov3D_precomp is None) or \
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
-        if cov3D_precomp is not None:
-            with torch.no_grad():
-                m, cov = _as_f32(means3D, "means3D"), _as_f32(cov3D_precomp, "cov3D_precomp")
-                P = int(m.shape[0])
-                if tuple(cov.shape) != (P, 6):
-                    raise ValueError(f"cov3D_precomp must be [P, 6], got {tuple(cov.shape)}")
-                radii = torch.empty(P, dtype=torch.int32, device=m.device)
-                src = _sources_c(None, 0, None, cov)
-                _lib.check(_lib.lib().gsvc_raster_visible_filter_ex(C.byref(self._c_settings()), P, _lib.ptr(m), None, None,
-                                                                    C.byref(src), _lib.ptr(radii), _lib.current_stream(m.device)),
-                           "gsvc_raster_visible_filter_ex")
-            return radii
         with torch.no_grad():
             m, s, q = _as_f32(means3D, "means3D"), _as_f32(scales, "scales"), _as_f32(rotations, "rotations")
             P = int(m.shape[0])
+            name, src_arg = "gsvc_raster_visible_filter", ()
+            if cov3D_precomp is not None:
+                cov = _as_f32(cov3D_precomp, "cov3D_precomp")
+                if tuple(cov.shape) != (P, 6):
+                    raise ValueError(f"cov3D_precomp must be [P, 6], got {tuple(cov.shape)}")
+                src = _sources_c(None, 0, None, cov)        # (keeps cov alive over the call)
+                name, src_arg = "gsvc_raster_visible_filter_ex", (C.byref(src),)
             radii = torch.empty(P, dtype=torch.int32, device=m.device)
-            _lib.check(_lib.lib().gsvc_raster_visible_filter(C.byref(self._c_settings()), P, _lib.ptr(m), _lib.ptr(s),
-                                                             _lib.ptr(q), _lib.ptr(radii), _lib.current_stream(m.device)),
-                       "gsvc_raster_visible_filter")
+            _lib.check(getattr(_lib.lib(), name)(C.byref(self._c_settings()), P, _lib.ptr(m), _lib.ptr(s), _lib.ptr(q), *src_arg,
+                                                 _lib.ptr(radii), _lib.current_stream(m.device)), name)
         return radii
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
@@ -497,15 +465,9 @@ class GaussianRasterizer(nn.Module):
             raise Exception("Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!")
         holder = {}
         maps = (bool(return_depth), bool(return_alpha))
-        depth = alpha = None
-        if shs is None and cov3D_precomp is None and not any(maps):
-            image, radii = _RasterizeGaussians.apply(means3D, means2D, colors_precomp, opacities, scales, rotations,
-                                                     self._c_settings(), holder, not self.deferred)
-        else:
-            campos = self._campos() if shs is not None else None
-            image, radii, depth, alpha = _RasterizeGaussiansEx.apply(
-                means3D, means2D, colors_precomp, opacities, scales, rotations, shs, cov3D_precomp, self._c_settings(),
-                int(self.raster_settings.sh_degree), campos, holder, not self.deferred, maps)
+        image, radii, depth, alpha = _RasterizeGaussians.apply(
+            means3D, means2D, colors_precomp, opacities, scales, rotations, shs, cov3D_precomp, self._c_settings(),
+            int(self.raster_settings.sh_degree), self._campos() if shs is not None else None, holder, not self.deferred, maps)
         self.last_state = holder["state"]
         # counters stay on the device under `deferred`: the caller resolves them with resolve_deferred()
         third = self.last_state if self.deferred else self.last_state.counters()[0]

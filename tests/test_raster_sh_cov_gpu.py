@@ -335,7 +335,8 @@ def test_default_call_takes_the_existing_entry_points(monkeypatch):
             return fn(*a)
         monkeypatch.setattr(L, name, wrapped)
     for name in ("gsvc_raster_forward", "gsvc_raster_backward", "gsvc_raster_forward_ex", "gsvc_raster_backward_ex",
-                 "gsvc_raster_visible_filter", "gsvc_raster_visible_filter_ex"):
+                 "gsvc_raster_forward_aux", "gsvc_raster_backward_aux", "gsvc_raster_visible_filter",
+                 "gsvc_raster_visible_filter_ex"):
         spy(name)
     r = _rasterizer(s, sh_degree=1, campos=_campos(sc))
     image, _, _ = r(means3D=d["means3D"], means2D=torch.zeros_like(d["means3D"]), colors_precomp=d["colors"],
@@ -349,6 +350,12 @@ def test_default_call_takes_the_existing_entry_points(monkeypatch):
                     scales=d["scales"], rotations=d["rotations"])
     image.sum().backward()
     assert calls == ["gsvc_raster_forward_ex", "gsvc_raster_backward_ex"]
+    calls.clear()
+    # a map asked for: the _aux entry points, also with the default colours and covariance
+    img_d, _, _, depth, _ = r(means3D=d["means3D"], means2D=torch.zeros_like(d["means3D"]), colors_precomp=d["colors"],
+                              opacities=d["opacities"], scales=d["scales"], rotations=d["rotations"], return_depth=True)
+    (img_d.sum() + depth.sum()).backward()
+    assert calls == ["gsvc_raster_forward_aux", "gsvc_raster_backward_aux"]
     # a zero SH row is the colour 0.5 in every channel
     img_c, _, _ = r(means3D=d["means3D"], means2D=torch.zeros_like(d["means3D"]), opacities=d["opacities"],
                     colors_precomp=torch.full_like(d["colors"], 0.5), scales=d["scales"], rotations=d["rotations"])
