@@ -180,9 +180,6 @@ _SIGNATURES = {
     "gsvc_film_row_maps": (C.c_int, [_vp, C.POINTER(C.c_int64), C.c_int32, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gsvc_pair_rows_sum": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int32, _vp, _vp]),
     "gsvc_set_deterministic": (C.c_int, [C.c_int]),
-    "gsvc_set_wgrad_stream": (C.c_int, [_vp]),
-    "gsvc_wgrad_hold": (C.c_int, [C.c_int32]),
-    "gsvc_wgrad_flush": (C.c_int, [_vp]),
     "gsvc_segment_rows_sum": (C.c_int, [_vp, _vp, _vp, _i64, C.c_int32, _vp, C.c_int32, _vp]),
     "gsvc_ste_binary_count_many": (C.c_int, [_vp, _vp, C.POINTER(C.c_int64), C.c_int32, _vp, _vp]),
     "gsvc_ste_binary_backward_many": (C.c_int, [_vp, _vp, C.POINTER(C.c_int64), C.c_int32, _vp, C.c_int32, _vp, _vp]),
@@ -240,27 +237,19 @@ _SIGNATURES = {
     "gsvc_linear_wgrad_workspace": (_i64, [C.c_int32, C.c_int32]),
     "gsvc_generator_saved_floats": (_i64, [C.POINTER(GeneratorNetC), _i64, _i64]),
     "gsvc_generator_scratch_floats": (_i64, [C.POINTER(GeneratorNetC), _i64, _i64]),
-    "gsvc_generator_forward": (C.c_int, [C.POINTER(GeneratorNetC), _vp, _vp, _i64, _vp, _vp, _vp]),
-    "gsvc_generator_backward": (C.c_int, [C.POINTER(GeneratorNetC), _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, C.c_int32,
-                                          C.POINTER(GeneratorGradsC), _vp]),
     "gsvc_quant_step_nets_forward": (C.c_int, [C.POINTER(QuantStepNetC), _vp, _i64, C.c_int32, C.c_int32, C.POINTER(C.c_void_p),
                                                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _vp]),
     "gsvc_quant_step_nets_backward": (C.c_int, [C.POINTER(QuantStepNetC), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _i64, C.c_int32,
                                                 C.c_int32, C.POINTER(C.c_void_p), _vp, _vp]),
     "gsvc_deform_saved_floats": (_i64, [C.POINTER(DeformNetC), _i64]),
     "gsvc_deform_scratch_floats": (_i64, [C.POINTER(DeformNetC), _i64]),
-    "gsvc_deform_forward": (C.c_int, [C.POINTER(DeformNetC), _vp, _vp, _i64, _vp, _vp, _vp]),
-    "gsvc_deform_backward": (C.c_int, [C.POINTER(DeformNetC), _vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
-                                       C.POINTER(DeformGradsC), _vp]),
     "gsvc_generator_inference_floats": (_i64, [C.POINTER(GeneratorNetC), _i64, _i64]),
-    "gsvc_generators_forward_inference": (C.c_int, [C.POINTER(GeneratorNetC), C.c_int32, _vp, _vp, _i64, C.POINTER(FilmRowsC), C.POINTER(C.c_void_p),
-                                                    C.POINTER(C.c_void_p), _vp]),
-    "gsvc_deform_forward_inference": (C.c_int, [C.POINTER(DeformNetC), _vp, _vp, _i64, _vp, _vp, _vp]),
-    "gsvc_generators_forward": (C.c_int, [C.POINTER(GeneratorNetC), C.c_int32, _vp, _vp, _i64, C.POINTER(FilmRowsC), C.POINTER(C.c_void_p),
-                                          C.POINTER(C.c_void_p), _vp]),
-    "gsvc_generators_backward": (C.c_int, [C.POINTER(GeneratorNetC), C.c_int32, _vp, _vp, _i64, C.POINTER(FilmRowsC), C.POINTER(C.c_void_p),
-                                           C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _vp, C.POINTER(C.c_void_p), C.POINTER(GeneratorGradsC),
-                                           _vp]),
+    "gsvc_deform_inference_floats": (_i64, [C.POINTER(DeformNetC), _i64]),
+    "gsvc_generate_all_forward": (C.c_int, [C.POINTER(GeneratorNetC), C.c_int32, C.POINTER(DeformNetC), _vp, _vp, _i64, C.POINTER(FilmRowsC),
+                                            C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32, _vp]),
+    "gsvc_generate_all_backward": (C.c_int, [C.POINTER(GeneratorNetC), C.c_int32, C.POINTER(DeformNetC), _vp, _vp, _i64, C.POINTER(FilmRowsC),
+                                             C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), _vp, _vp, _vp,
+                                             C.POINTER(C.c_void_p), C.POINTER(GeneratorGradsC), C.POINTER(DeformGradsC), _vp, _vp]),
     "gsvc_rate_sample_scratch_floats": (_i64, [_i64]),
     "gsvc_rate_sample_forward": (C.c_int, [C.POINTER(RateSampleC), _vp, _vp, _vp]),
     "gsvc_rate_sample_backward": (C.c_int, [C.POINTER(RateSampleC), _vp, _vp, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

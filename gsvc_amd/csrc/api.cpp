@@ -1,6 +1,7 @@
 // gsvc_amd/csrc/api.cpp — error slot and version of libgsvc_hip.so.
 #include "common.h"
 
+#include <atomic>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -23,9 +24,9 @@ struct ProfRec {
     std::string name;
     hipEvent_t a, b;
 };
-static bool g_prof_on = false;
+static std::atomic<bool> g_prof_on{false};
 static bool g_bwd_probe = false;
-static bool g_deterministic = false;
+static std::atomic<bool> g_deterministic{false};
 static std::mutex g_prof_mu;
 static std::vector<ProfRec> g_prof;
 static std::vector<hipEvent_t> g_pool;

@@ -22,10 +22,8 @@
 // Instantiated for the production widths (feat 50, condition 66, hidden 100, K = 10 offsets: outputs 10 / 30 / 70 / 30);
 // other widths return GSVC_E_UNSUPPORTED and the caller keeps the layer-by-layer path.
 #include <cstdlib>
-#include <functional>
 #include <mutex>
 #include <set>
-#include <vector>
 
 #include "linear_ws.h"
 
@@ -1265,42 +1263,46 @@ int generators_forward(const gsvc_generator_net *nets, int n, const float *feat,
     return check_launch("generators_forward");
 }
 
-// The weight gradients of a backward pass read what its chain kernels wrote and nothing downstream reads THEM before the optimizer:
-// with gsvc_set_wgrad_stream they are queued on that stream behind an event of the caller's, and the caller's stream goes on with
-// the feature gradient (the quantisers', gathers' and hash grid's backward) while they run.
-hipStream_t g_wgrad_stream = nullptr;
-
-// gsvc_wgrad_hold(1): the entries keep their weight-gradient launches back (operands by value) until gsvc_wgrad_flush — so that a
-// caller with several chain backward passes in a row (the generators', then mlp_deform's) gets every chain kernel onto its stream
-// BEFORE the first product starts beside them: a chain workgroup needs its whole CU, a product queued in between made the second
-// network's chain kernels wait for the first network's products to retire.
-struct DeferredWgrad {
-    std::vector<gsvc_wgrad_partial_job> part;
-    std::vector<gsvc_wgrad_reduce_job> red;
-    std::function<void(hipStream_t)> tail;
+// The weight gradients dW = G^T X (+ db) of a backward pass: row-split partial sums into consecutive regions of a workspace, then one
+// batched slot reduce.  They read what the chain kernels wrote and nothing downstream reads THEM before the optimizer, so
+// gsvc_generate_all_backward may queue them on a stream of their own (wgrad_stream_behind) beside the feature gradient's way back.
+struct WgradJobs {
+    gsvc_wgrad_partial_job part[7 * MAX_NETS];
+    gsvc_wgrad_reduce_job red[7 * MAX_NETS];
+    int n = 0;
+    void add(const float *G, const float *X, float *dW, float *db, int N, int K, long long rows, float *&ws)      // NULL dW: layer skipped
+    {
+        if (!dW) return;
+        const long long need = gsvc_linear_wgrad_workspace(N, K);
+        part[n] = gsvc_wgrad_partial_job{G, X, ws, rows, need, db != nullptr, N, K, 0};
+        red[n++] = gsvc_wgrad_reduce_job{ws, dW, db, 0, N, K};
+        ws += need;
+    }
+    int run(hipStream_t s)
+    {
+        if (!n) return GSVC_OK;
+        if (int rc = gsvc_linear_wgrad_partial_many(part, n, s)) return rc;
+        for (int i = 0; i < n; i++) red[i].slots = part[i].slots_used;
+        return gsvc_linear_wgrad_reduce_many(red, n, s);
+    }
 };
-bool g_wgrad_hold = false;
-std::vector<DeferredWgrad> g_wgrad_deferred;
 
-int run_wgrad(gsvc_wgrad_partial_job *part, gsvc_wgrad_reduce_job *red, int n, hipStream_t s)
+// `side` made to wait for everything queued on `s` so far (an event from a small pool: creating one per call costs host time in the
+// step); returns the stream to queue on — `s` itself when there is no side stream or the event could not be made
+hipStream_t wgrad_stream_behind(hipStream_t s, hipStream_t side)
 {
-    if (int rc = gsvc_linear_wgrad_partial_many(part, n, s)) return rc;
-    for (int i = 0; i < n; i++) red[i].slots = part[i].slots_used;
-    return gsvc_linear_wgrad_reduce_many(red, n, s);
-}
-
-hipStream_t wgrad_stream_behind(hipStream_t s)
-{
-    if (g_wgrad_stream == nullptr || g_wgrad_stream == s) return s;
+    if (side == nullptr || side == s) return s;
     constexpr int POOL = 32;
+    static std::mutex mu;
     static hipEvent_t pool[POOL];
     static int at = -1;
     static bool disabled = false;      // the pool could not be made: the caller's stream from then on
+    std::lock_guard<std::mutex> lock(mu);
     if (disabled) return s;
     if (at < 0) {
         for (int i = 0; i < POOL; i++)
             if (hipEventCreateWithFlags(&pool[i], hipEventDisableTiming) != hipSuccess) {
-                while (i-- > 0) hipEventDestroy(pool[i]);
+                while (i-- > 0) (void)hipEventDestroy(pool[i]);
                 disabled = true;
                 return s;
             }
@@ -1308,13 +1310,15 @@ hipStream_t wgrad_stream_behind(hipStream_t s)
     }
     hipEvent_t e = pool[at];
     at = (at + 1) % POOL;
-    if (hipEventRecord(e, s) != hipSuccess || hipStreamWaitEvent(g_wgrad_stream, e, 0) != hipSuccess) return s;
-    return g_wgrad_stream;
+    if (hipEventRecord(e, s) != hipSuccess || hipStreamWaitEvent(side, e, 0) != hipSuccess) return s;
+    return side;
 }
 
+// the generators' two chain kernels on `s`; their seven weight gradients per network are appended to `jobs`, not launched.  The FiLM
+// networks' four run over the FiLM rows (the summed gradients of the two views when they share them)
 int generators_backward(const gsvc_generator_net *nets, int n, const float *feat, const float *cond, long long M, const gsvc_film_rows *film,
                         const float *const *saved, const float *const *y, const float *const *gy, float *scratch, float *const *gfeat,
-                        const int *accumulate, const gsvc_generator_grads *grads, hipStream_t s)
+                        const gsvc_generator_grads *grads, WgradJobs &jobs, hipStream_t s)
 {
     const FilmRows fr(film, M, cond);
     TrunkBwdBatch tb;
@@ -1337,51 +1341,27 @@ int generators_backward(const gsvc_generator_net *nets, int n, const float *feat
         const gsvc_generator_net &g = nets[j];
         const GenSaved sv(const_cast<float *>(saved[j]), M, fr.rows);
         const GenScratch sc(sbase[j], M, fr.rows, g.out_dim, fr.shared);
-        tb.out[i] = g.out_dim; tb.act[i] = g.out_act; tb.accumulate[i] = accumulate ? accumulate[j] : 0;
+        tb.out[i] = g.out_dim; tb.act[i] = g.out_act; tb.accumulate[i] = 0;
         tb.w[i] = TrunkW{g.W1, g.b1, g.W2, g.b2, g.W3, g.b3};
         tb.gy[i] = gy[j]; tb.y[i] = y[j]; tb.h[i] = sv.h; tb.gamma[i] = sv.gamma;
         tb.go[i] = sc.go; tb.gbeta[i] = sc.gbeta; tb.ggamma[i] = sc.ggamma; tb.gh[i] = sc.gh; tb.gz1[i] = sc.gz1; tb.gfeat[i] = gfeat[j];
         fb.ggamma[i] = sc.ggamma; fb.gbeta[i] = sc.gbeta; fb.cg[i] = sv.cg; fb.cb[i] = sv.cb; fb.Wg1[i] = g.Wg1; fb.Wb1[i] = g.Wb1;
         fb.gcg[i] = sc.gcg; fb.gcb[i] = sc.gcb; fb.ggamma_sum[i] = sc.ggamma_sum; fb.gbeta_sum[i] = sc.gbeta_sum;
+        if (i >= n) continue;
+        const gsvc_generator_grads &gr = grads[i];
+        float *ws = sc.wg;
+        jobs.add(sc.gz1, feat, gr.W1, gr.b1, HID, FEAT, M, ws);
+        jobs.add(sc.gh, sv.a1, gr.W2, gr.b2, HID, HID, M, ws);
+        jobs.add(sc.go, sv.x3, gr.W3, gr.b3, g.out_dim, HID, M, ws);
+        jobs.add(sc.gcg, fr.cond, gr.Wg0, gr.bg0, COND, COND, fr.rows, ws);
+        jobs.add(sc.ggamma_sum, sv.cg, gr.Wg1, gr.bg1, HID, COND, fr.rows, ws);
+        jobs.add(sc.gcb, fr.cond, gr.Wb0, gr.bb0, COND, COND, fr.rows, ws);
+        jobs.add(sc.gbeta_sum, sv.cb, gr.Wb1, gr.bb1, HID, COND, fr.rows, ws);
     }
     chain_launch("k_trunk_bwd", &k_trunk_bwd<FEAT, HID, CHAIN_T>, TrunkBwdLds<FEAT, HID, 70>::FLOATS * 4, M * n, n, s, tb, M);
     chain_launch("k_film_nets_bwd", &k_film_nets_bwd<COND, HID, CHAIN_T>, (size_t)2 * cl_kg(COND) * 16 * cl_ld(HID) * 4, fr.rows * n, n, s, fb,
                  fr.rows);
-    if (int rc = check_launch("generators_backward")) return rc;
-    // the seven weight gradients dW = G^T X (+ db) of every network: row-split partial sums, batched slot reduces.  The FiLM
-    // networks' four run over the FiLM rows (the summed gradients of the two views when they share them)
-    struct Job { const float *G, *X; float *dW, *db; int N, K; long long rows; };
-    gsvc_wgrad_partial_job part[7 * MAX_NETS];
-    gsvc_wgrad_reduce_job red[7 * MAX_NETS];
-    int nred = 0;
-    for (int i = 0; i < n; i++) {
-        const gsvc_generator_net &g = nets[i];
-        const gsvc_generator_grads &gr = grads[i];
-        const GenSaved sv(const_cast<float *>(saved[i]), M, fr.rows);
-        const GenScratch sc(sbase[i], M, fr.rows, g.out_dim, fr.shared);
-        const Job jobs[7] = {
-            {sc.gz1, feat, gr.W1, gr.b1, HID, FEAT, M},        {sc.gh, sv.a1, gr.W2, gr.b2, HID, HID, M},
-            {sc.go, sv.x3, gr.W3, gr.b3, g.out_dim, HID, M},   {sc.gcg, fr.cond, gr.Wg0, gr.bg0, COND, COND, fr.rows},
-            {sc.ggamma_sum, sv.cg, gr.Wg1, gr.bg1, HID, COND, fr.rows}, {sc.gcb, fr.cond, gr.Wb0, gr.bb0, COND, COND, fr.rows},
-            {sc.gbeta_sum, sv.cb, gr.Wb1, gr.bb1, HID, COND, fr.rows}};
-        float *ws = sc.wg;
-        for (const Job &j : jobs) {
-            if (!j.dW) continue;
-            const long long need = gsvc_linear_wgrad_workspace(j.N, j.K);
-            part[nred] = gsvc_wgrad_partial_job{j.G, j.X, ws, j.rows, need, j.db != nullptr, j.N, j.K, 0};
-            red[nred++] = gsvc_wgrad_reduce_job{ws, j.dW, j.db, 0, j.N, j.K};
-            ws += need;
-        }
-    }
-    if (nred) {
-        if (g_wgrad_hold && g_wgrad_stream != nullptr) {
-            g_wgrad_deferred.push_back(DeferredWgrad{std::vector<gsvc_wgrad_partial_job>(part, part + nred),
-                                                     std::vector<gsvc_wgrad_reduce_job>(red, red + nred), nullptr});
-            return GSVC_OK;
-        }
-        return run_wgrad(part, red, nred, wgrad_stream_behind(s));
-    }
-    return GSVC_OK;
+    return check_launch("generators_backward");
 }
 
 constexpr int DEF_OUT = 30;
@@ -1392,6 +1372,64 @@ long long deform_wgrad_floats()
 {
     return gsvc_linear_wgrad_workspace(HID, FEAT) + gsvc_linear_wgrad_workspace(HID, COND) + 3 * gsvc_linear_wgrad_workspace(HID, HID) +
            gsvc_linear_wgrad_workspace(DEF_OUT, HID);
+}
+
+DeformW deform_weights(const gsvc_deform_net *n)
+{
+    DeformW w;
+    for (int i = 0; i < 5; i++) { w.W[i] = n->W[i]; w.b[i] = n->b[i]; }
+    return w;
+}
+
+inline float *align16(float *p) { return reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(p) + 15) & ~uintptr_t(15)); }
+
+// what the deformation network's forward leaves for its backward: pre-activation z and activation a of the four hidden layers,
+// [M, HID] each.  Forward only: a2 alone (it travels from the first kernel to the second), nothing else is stored
+struct DeformSaved {
+    float *z1, *a1, *z2, *a2, *z3, *a3, *z4, *a4;
+    DeformSaved(float *base, long long M, bool inference = false)
+    {
+        z1 = a1 = z2 = z3 = a3 = z4 = a4 = nullptr;
+        a2 = base;
+        if (inference) return;
+        z1 = base; a1 = z1 + M * HID; z2 = a1 + M * HID; a2 = z2 + M * HID; z3 = a2 + M * HID; a3 = z3 + M * HID; z4 = a3 + M * HID;
+        a4 = z4 + M * HID;
+    }
+};
+
+// backward scratch of the deformation network: the hidden layers' gradients g1 .. g4 [M, HID]; the two halves of layer 1's weight
+// gradient [g1^T feat | g1^T cond] (the reduce writes contiguous [N][K] blocks; grads->W[0] is [HID][FEAT + COND]: two strided
+// copies put the halves side by side); then the wgrad partial sums
+struct DeformScratch {
+    float *g1, *g2, *g3, *g4, *stage_f, *stage_c, *wg;
+    DeformScratch(float *base, long long M)
+    {
+        g1 = base; g2 = g1 + M * HID; g3 = g2 + M * HID; g4 = g3 + M * HID;
+        stage_f = align16(g4 + M * HID); stage_c = stage_f + (size_t)HID * FEAT;
+        wg = align16(stage_c + (size_t)HID * COND);
+    }
+};
+
+// the deformation network's two chain kernels on `s` (gfeat = its own feature gradient + the addends'); its six products are
+// appended to `jobs`, not launched
+int deform_backward(const gsvc_deform_net *n, const float *feat, const float *cond, long long M, const float *saved, const float *gy,
+                    float *scratch, float *gfeat, const float *const *add, const gsvc_deform_grads *grads, WgradJobs &jobs, hipStream_t s)
+{
+    const DeformW w = deform_weights(n);
+    const DeformSaved sv(const_cast<float *>(saved), M);
+    const DeformScratch sc(scratch, M);
+    chain_launch("k_deform_b_bwd", &k_deform_b_bwd<HID, DEF_OUT, CHAIN_T>, DeformBBwdLds<HID, DEF_OUT>::FLOATS * 4,
+                 M, 1, s, gy, sv.z4, sv.z3, sv.z2, w, sc.g4, sc.g3, sc.g2, M);
+    chain_launch("k_deform_a_bwd", &k_deform_a_bwd<FEAT, HID, CHAIN_T>, (size_t)(cl_kg(HID) + cl_kg(FEAT)) * 16 * cl_ld(HID) * 4, M, 1, s, sc.g2, sv.z1, w, FEAT + COND, sc.g1, gfeat, 0, add[0], add[1], add[2], M);
+    const bool want1 = grads->W[0] != nullptr;
+    float *ws = sc.wg;
+    jobs.add(sc.g1, feat, want1 ? sc.stage_f : nullptr, grads->b[0], HID, FEAT, M, ws);
+    jobs.add(sc.g1, cond, want1 ? sc.stage_c : nullptr, nullptr, HID, COND, M, ws);
+    jobs.add(sc.g2, sv.a1, grads->W[1], grads->b[1], HID, HID, M, ws);
+    jobs.add(sc.g3, sv.a2, grads->W[2], grads->b[2], HID, HID, M, ws);
+    jobs.add(sc.g4, sv.a3, grads->W[3], grads->b[3], HID, HID, M, ws);
+    jobs.add(gy, sv.a4, grads->W[4], grads->b[4], DEF_OUT, HID, M, ws);
+    return check_launch("deform_backward");
 }
 
 }  // namespace
@@ -1426,118 +1464,27 @@ extern "C" int64_t gsvc_generator_scratch_floats(const gsvc_generator_net *n, in
     return (int64_t)(n->out_dim + 4 * HID) * M + (int64_t)(2 * COND + (film_rows > 0 ? 2 * HID : 0)) * Mf + gen_wgrad_floats(n->out_dim) + 96;
 }
 
-static int gens_supported(const gsvc_generator_net *nets, int32_t n, const char *what)
-{
-    GSVC_REQUIRE(nets && n >= 1 && n <= MAX_NETS, "%s: 1 .. %d networks per call", what, MAX_NETS);
-    for (int i = 0; i < n; i++)
-        if (int rc = gen_supported(&nets[i], what)) return rc;
-    return GSVC_OK;
-}
-
-static int film_rows_ok(const gsvc_film_rows *f, int64_t M, const char *what)
-{
-    if (!f || f->rows <= 0) return GSVC_OK;
-    GSVC_REQUIRE(f->cond && f->row_of && f->src_a && f->src_b && aligned16({f->cond}), "%s: shared FiLM rows need cond, row_of, src_a, src_b", what);
-    GSVC_REQUIRE((M > f->rows ? M : f->rows) * (int64_t)HID * 4 < ((int64_t)1 << 31), "%s: %lld rows exceed the 2 GiB reach of the row maps", what,
-                 (long long)(M > f->rows ? M : f->rows));
-    return GSVC_OK;
-}
-
-extern "C" int gsvc_generators_forward(const gsvc_generator_net *nets, int32_t n_nets, const float *feat, const float *cond, int64_t M,
-                                       const gsvc_film_rows *film, float *const *saved, float *const *y, void *stream)
-{
-    if (int rc = gens_supported(nets, n_nets, "generators_forward")) return rc;
-    GSVC_REQUIRE(M >= 0, "generators_forward: bad row count");
-    if (M == 0) return GSVC_OK;
-    GSVC_REQUIRE(feat && cond && saved && y && aligned16({feat, cond}), "generators_forward: NULL or unaligned pointer");
-    if (int rc = film_rows_ok(film, M, "generators_forward")) return rc;
-    for (int i = 0; i < n_nets; i++)
-        GSVC_REQUIRE(saved[i] && y[i] && aligned16({saved[i], y[i]}), "generators_forward: NULL or unaligned pointer (network %d)", i);
-    return generators_forward(nets, n_nets, feat, cond, M, film, saved, y, (hipStream_t)stream);
-}
-
 extern "C" int64_t gsvc_generator_inference_floats(const gsvc_generator_net *n, int64_t M, int64_t film_rows)
 {
     if (!n || M < 0 || film_rows < 0) return -1;
     return 2 * (int64_t)HID * (film_rows > 0 ? film_rows : M) + 64;
 }
 
-// forward only: nothing the backward would read is written (the trunk of a generator stores four [M, 100] activations per
-// network for it: 60 % of the forward's traffic)
-extern "C" int gsvc_generators_forward_inference(const gsvc_generator_net *nets, int32_t n_nets, const float *feat, const float *cond, int64_t M,
-                                                 const gsvc_film_rows *film, float *const *scratch, float *const *y, void *stream)
+// the generators of a call: 1 .. MAX_NETS networks of instantiated widths; with rows, the rows' matrices and the shared FiLM rows
+static int gens_supported(const gsvc_generator_net *nets, int32_t n, const float *feat, const float *cond, int64_t M, const gsvc_film_rows *f,
+                          const char *what)
 {
-    if (int rc = gens_supported(nets, n_nets, "generators_forward_inference")) return rc;
-    GSVC_REQUIRE(M >= 0, "generators_forward_inference: bad row count");
+    GSVC_REQUIRE(nets && n >= 1 && n <= MAX_NETS, "%s: 1 .. %d networks per call", what, MAX_NETS);
+    for (int i = 0; i < n; i++)
+        if (int rc = gen_supported(&nets[i], what)) return rc;
+    GSVC_REQUIRE(M >= 0, "%s: bad row count", what);
     if (M == 0) return GSVC_OK;
-    GSVC_REQUIRE(feat && cond && scratch && y && aligned16({feat, cond}), "generators_forward_inference: NULL or unaligned pointer");
-    if (int rc = film_rows_ok(film, M, "generators_forward_inference")) return rc;
-    for (int i = 0; i < n_nets; i++)
-        GSVC_REQUIRE(scratch[i] && y[i] && aligned16({scratch[i], y[i]}), "generators_forward_inference: NULL or unaligned pointer (network %d)", i);
-    return generators_forward(nets, n_nets, feat, cond, M, film, scratch, y, (hipStream_t)stream, true);
-}
-
-extern "C" int gsvc_generators_backward(const gsvc_generator_net *nets, int32_t n_nets, const float *feat, const float *cond, int64_t M,
-                                        const gsvc_film_rows *film, const float *const *saved, const float *const *y,
-                                        const float *const *gy, float *scratch, float *const *gfeat, const gsvc_generator_grads *grads,
-                                        void *stream)
-{
-    if (int rc = gens_supported(nets, n_nets, "generators_backward")) return rc;
-    GSVC_REQUIRE(M >= 0 && grads, "generators_backward: bad arguments");
-    if (M == 0) return GSVC_OK;
-    GSVC_REQUIRE(feat && cond && saved && y && gy && scratch && gfeat && aligned16({feat, cond, scratch}),
-                 "generators_backward: NULL or unaligned pointer");
-    if (int rc = film_rows_ok(film, M, "generators_backward")) return rc;
-    for (int i = 0; i < n_nets; i++) {
-        GSVC_REQUIRE(saved[i] && y[i] && gy[i] && gfeat[i] && aligned16({saved[i], y[i], gy[i], gfeat[i]}),
-                     "generators_backward: NULL or unaligned pointer (network %d)", i);
-        for (int j = 0; j < i; j++) GSVC_REQUIRE(gfeat[i] != gfeat[j], "generators_backward: the networks' feature gradients must be distinct buffers");
-    }
-    return generators_backward(nets, n_nets, feat, cond, M, film, saved, y, gy, scratch, gfeat, nullptr, grads, (hipStream_t)stream);
-}
-
-extern "C" int gsvc_generator_forward(const gsvc_generator_net *n, const float *feat, const float *cond, int64_t M, float *saved, float *y,
-                                      void *stream)
-{
-    return gsvc_generators_forward(n, 1, feat, cond, M, nullptr, &saved, &y, stream);
-}
-
-extern "C" int gsvc_generator_backward(const gsvc_generator_net *n, const float *feat, const float *cond, int64_t M, const float *saved,
-                                       const float *y, const float *gy, float *scratch, float *gfeat, int32_t accumulate_gfeat,
-                                       const gsvc_generator_grads *grads, void *stream)
-{
-    if (int rc = gens_supported(n, 1, "generator_backward")) return rc;
-    GSVC_REQUIRE(M >= 0 && grads, "generator_backward: bad arguments");
-    if (M == 0) return GSVC_OK;
-    GSVC_REQUIRE(feat && cond && saved && y && gy && scratch && gfeat, "generator_backward: NULL pointer");
-    GSVC_REQUIRE(aligned16({feat, cond, saved, y, gy, scratch, gfeat}), "generator_backward: operands must be 16-byte aligned");
-    const int acc = accumulate_gfeat;
-    return generators_backward(n, 1, feat, cond, M, nullptr, &saved, &y, &gy, scratch, &gfeat, &acc, grads, (hipStream_t)stream);
-}
-
-extern "C" int gsvc_set_wgrad_stream(void *stream)
-{
-    gsvc::g_wgrad_stream = (hipStream_t)stream;
+    GSVC_REQUIRE(feat && cond && aligned16({feat, cond}), "%s: NULL or unaligned feature / condition matrix", what);
+    if (!f || f->rows <= 0) return GSVC_OK;
+    GSVC_REQUIRE(f->cond && f->row_of && f->src_a && f->src_b && aligned16({f->cond}), "%s: shared FiLM rows need cond, row_of, src_a, src_b", what);
+    GSVC_REQUIRE((M > f->rows ? M : f->rows) * (int64_t)HID * 4 < ((int64_t)1 << 31), "%s: %lld rows exceed the 2 GiB reach of the row maps", what,
+                 (long long)(M > f->rows ? M : f->rows));
     return GSVC_OK;
-}
-
-extern "C" int gsvc_wgrad_hold(int32_t on)
-{
-    gsvc::g_wgrad_hold = on != 0;
-    return GSVC_OK;
-}
-
-extern "C" int gsvc_wgrad_flush(void *stream)
-{
-    if (gsvc::g_wgrad_deferred.empty()) return GSVC_OK;
-    hipStream_t ws = gsvc::g_wgrad_stream != nullptr ? gsvc::wgrad_stream_behind((hipStream_t)stream) : (hipStream_t)stream;
-    int rc = GSVC_OK;
-    for (auto &d : gsvc::g_wgrad_deferred) {
-        if (rc == GSVC_OK) rc = gsvc::run_wgrad(d.part.data(), d.red.data(), (int)d.part.size(), ws);
-        if (rc == GSVC_OK && d.tail) d.tail(ws);
-    }
-    gsvc::g_wgrad_deferred.clear();
-    return rc != GSVC_OK ? rc : check_launch("wgrad_flush");
 }
 
 static int deform_supported(const gsvc_deform_net *n, const char *what)
@@ -1564,107 +1511,80 @@ extern "C" int64_t gsvc_deform_scratch_floats(const gsvc_deform_net *n, int64_t 
     return DEF_SCRATCH_PER_ROW * M + deform_wgrad_floats() + 2 * (int64_t)HID * (FEAT + COND) + 64;
 }
 
-extern "C" int gsvc_deform_forward(const gsvc_deform_net *n, const float *feat, const float *cond, int64_t M, float *saved, float *y,
-                                   void *stream)
+extern "C" int64_t gsvc_deform_inference_floats(const gsvc_deform_net *n, int64_t M)
 {
-    if (int rc = deform_supported(n, "deform_forward")) return rc;
-    GSVC_REQUIRE(M >= 0, "deform_forward: bad row count");
-    if (M == 0) return GSVC_OK;
-    GSVC_REQUIRE(feat && cond && saved && y, "deform_forward: NULL pointer");
-    GSVC_REQUIRE(aligned16({feat, cond, saved, y}), "deform_forward: operands must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    DeformW w;
-    for (int i = 0; i < 5; i++) { w.W[i] = n->W[i]; w.b[i] = n->b[i]; }
-    float *z1 = saved, *a1 = z1 + M * HID, *z2 = a1 + M * HID, *a2 = z2 + M * HID, *z3 = a2 + M * HID, *a3 = z3 + M * HID,
-          *z4 = a3 + M * HID, *a4 = z4 + M * HID;
-    chain_launch("k_deform_a_fwd", &k_deform_a_fwd<FEAT, COND, HID, CHAIN_T>, DeformALds<FEAT, COND, HID>::FLOATS * 4, M, 1, s, feat, cond, w, z1, a1, z2, a2, M);
-    chain_launch("k_deform_b_fwd", &k_deform_b_fwd<HID, DEF_OUT, CHAIN_T>, DeformBLds<HID, DEF_OUT>::FLOATS * 4, M, 1, s,
-                 a2, w, z3, a3, z4, a4, y, M);
-    return check_launch("deform_forward");
+    if (!n || M < 0) return -1;
+    return (int64_t)HID * M;      // the activation that travels from the first kernel to the second
 }
 
-// forward only: scratch = HID * M floats (the activation that travels from the first kernel to the second)
-extern "C" int gsvc_deform_forward_inference(const gsvc_deform_net *n, const float *feat, const float *cond, int64_t M, float *scratch, float *y,
-                                             void *stream)
+extern "C" int gsvc_generate_all_forward(const gsvc_generator_net *nets, int32_t n_nets, const gsvc_deform_net *deform, const float *feat,
+                                         const float *cond, int64_t M, const gsvc_film_rows *film, float *const *saved, float *const *y,
+                                         int32_t keep_for_backward, void *stream)
 {
-    if (int rc = deform_supported(n, "deform_forward_inference")) return rc;
-    GSVC_REQUIRE(M >= 0, "deform_forward_inference: bad row count");
+    const char *what = "generate_all_forward";
+    if (int rc = gens_supported(nets, n_nets, feat, cond, M, film, what)) return rc;
+    if (int rc = deform_supported(deform, what)) return rc;
     if (M == 0) return GSVC_OK;
-    GSVC_REQUIRE(feat && cond && scratch && y && aligned16({feat, cond, scratch, y}), "deform_forward_inference: NULL or unaligned pointer");
+    GSVC_REQUIRE(saved && y, "%s: NULL pointer array", what);
+    for (int i = 0; i <= n_nets; i++)
+        GSVC_REQUIRE(saved[i] && y[i] && aligned16({saved[i], y[i]}), "%s: NULL or unaligned pointer (network %d)", what, i);
     hipStream_t s = (hipStream_t)stream;
-    DeformW w;
-    for (int i = 0; i < 5; i++) { w.W[i] = n->W[i]; w.b[i] = n->b[i]; }
-    float *none = nullptr;
-    chain_launch("k_deform_a_fwd", &k_deform_a_fwd<FEAT, COND, HID, CHAIN_T>, DeformALds<FEAT, COND, HID>::FLOATS * 4, M, 1, s, feat, cond, w, none, none,
-                 none, scratch, M);
+    const bool inference = keep_for_backward == 0;
+    if (int rc = generators_forward(nets, n_nets, feat, cond, M, film, saved, y, s, inference)) return rc;
+    const DeformW w = deform_weights(deform);
+    const DeformSaved sv(saved[n_nets], M, inference);
+    chain_launch("k_deform_a_fwd", &k_deform_a_fwd<FEAT, COND, HID, CHAIN_T>, DeformALds<FEAT, COND, HID>::FLOATS * 4, M, 1, s, feat, cond, w, sv.z1, sv.a1,
+                 sv.z2, sv.a2, M);
     chain_launch("k_deform_b_fwd", &k_deform_b_fwd<HID, DEF_OUT, CHAIN_T>, DeformBLds<HID, DEF_OUT>::FLOATS * 4, M, 1, s,
-                 (const float *)scratch, w, none, none, none, none, y, M);
-    return check_launch("deform_forward_inference");
+                 (const float *)sv.a2, w, sv.z3, sv.a3, sv.z4, sv.a4, y[n_nets], M);
+    return check_launch(what);
 }
 
-extern "C" int gsvc_deform_backward(const gsvc_deform_net *n, const float *feat, const float *cond, int64_t M, const float *saved,
-                                    const float *gy, float *scratch, float *gfeat, int32_t accumulate_gfeat,
-                                    const float *const *gfeat_addends, int32_t n_addends, const gsvc_deform_grads *grads, void *stream)
+extern "C" int gsvc_generate_all_backward(const gsvc_generator_net *nets, int32_t n_nets, const gsvc_deform_net *deform, const float *feat,
+                                          const float *cond, int64_t M, const gsvc_film_rows *film, const float *const *saved,
+                                          const float *const *y, const float *const *gy, float *scratch, float *scratch_deform,
+                                          float *gfeat_sum, float *const *gfeat_parts, const gsvc_generator_grads *gen_grads,
+                                          const gsvc_deform_grads *deform_grads, void *stream, void *wgrad_stream)
 {
-    if (int rc = deform_supported(n, "deform_backward")) return rc;
-    GSVC_REQUIRE(M >= 0 && grads && n_addends >= 0 && n_addends <= 3 && (n_addends == 0 || gfeat_addends), "deform_backward: bad arguments");
-    const float *add[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < n_addends; i++) {
-        GSVC_REQUIRE(gfeat_addends[i] && aligned16({gfeat_addends[i]}) && gfeat_addends[i] != gfeat, "deform_backward: bad addend %d", i);
-        add[i] = gfeat_addends[i];
-    }
+    const char *what = "generate_all_backward";
+    if (int rc = gens_supported(nets, n_nets, feat, cond, M, film, what)) return rc;
+    if (int rc = deform_supported(deform, what)) return rc;
+    GSVC_REQUIRE(gen_grads && deform_grads, "%s: NULL gradient descriptors", what);
     if (M == 0) return GSVC_OK;
-    GSVC_REQUIRE(feat && cond && saved && gy && scratch && gfeat, "deform_backward: NULL pointer");
-    GSVC_REQUIRE(aligned16({feat, cond, saved, gy, scratch, gfeat}),
-                 "deform_backward: operands must be 16-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    DeformW w;
-    for (int i = 0; i < 5; i++) { w.W[i] = n->W[i]; w.b[i] = n->b[i]; }
-    const float *z1 = saved, *a1 = z1 + M * HID, *z2 = a1 + M * HID, *a2 = z2 + M * HID, *z3 = a2 + M * HID, *a3 = z3 + M * HID,
-                *z4 = a3 + M * HID, *a4 = z4 + M * HID;
-    float *g1 = scratch, *g2 = g1 + M * HID, *g3 = g2 + M * HID, *g4 = g3 + M * HID, *ws = g4 + M * HID;
-    ws = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(ws) + 15) & ~uintptr_t(15));
-    chain_launch("k_deform_b_bwd", &k_deform_b_bwd<HID, DEF_OUT, CHAIN_T>, DeformBBwdLds<HID, DEF_OUT>::FLOATS * 4,
-                 M, 1, s, gy, z4, z3, z2, w, g4, g3, g2, M);
-    chain_launch("k_deform_a_bwd", &k_deform_a_bwd<FEAT, HID, CHAIN_T>, (size_t)(cl_kg(HID) + cl_kg(FEAT)) * 16 * cl_ld(HID) * 4, M, 1, s, g2, z1, w, FEAT + COND, g1, gfeat, (int)accumulate_gfeat, add[0], add[1], add[2], M);
-    if (int rc = check_launch("deform_backward")) return rc;
-    // weight gradients; layer 1 = [g1^T feat | g1^T cond] formed as two products into a staging area, interleaved by the caller's
-    // layout (grads->W[0] is [HID][FEAT + COND]): the reduce writes contiguous [N][K] blocks, so the two halves go to scratch
-    // and a strided copy puts them side by side
-    struct Job { const float *G, *X; float *dW, *db; int N, K; };
-    float *stage_f = ws, *stage_c = stage_f + (size_t)HID * FEAT;
-    ws = stage_c + (size_t)HID * COND;
-    ws = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(ws) + 15) & ~uintptr_t(15));
-    const bool want1 = grads->W[0] != nullptr;
-    const Job jobs[6] = {{g1, feat, want1 ? stage_f : nullptr, grads->b[0], HID, FEAT}, {g1, cond, want1 ? stage_c : nullptr, nullptr, HID, COND},
-                         {g2, a1, grads->W[1], grads->b[1], HID, HID},                 {g3, a2, grads->W[2], grads->b[2], HID, HID},
-                         {g4, a3, grads->W[3], grads->b[3], HID, HID},                 {gy, a4, grads->W[4], grads->b[4], DEF_OUT, HID}};
-    gsvc_wgrad_partial_job part[6];
-    gsvc_wgrad_reduce_job red[6];
-    int nred = 0;
-    for (const Job &j : jobs) {
-        if (!j.dW) continue;
-        const long long need = gsvc_linear_wgrad_workspace(j.N, j.K);
-        part[nred] = gsvc_wgrad_partial_job{j.G, j.X, ws, M, need, j.db != nullptr, j.N, j.K, 0};
-        red[nred++] = gsvc_wgrad_reduce_job{ws, j.dW, j.db, 0, j.N, j.K};
-        ws += need;
+    GSVC_REQUIRE(saved && y && gy && gfeat_parts && scratch && scratch_deform && gfeat_sum && aligned16({scratch, scratch_deform, gfeat_sum}),
+                 "%s: NULL or unaligned pointer", what);
+    const float *add[MAX_NETS] = {nullptr, nullptr, nullptr};
+    int64_t gen_floats = 0;
+    for (int i = 0; i < n_nets; i++) {
+        GSVC_REQUIRE(saved[i] && y[i] && gy[i] && gfeat_parts[i] && aligned16({saved[i], y[i], gy[i], gfeat_parts[i]}),
+                     "%s: NULL or unaligned pointer (network %d)", what, i);
+        GSVC_REQUIRE(gfeat_parts[i] != gfeat_sum, "%s: the networks' feature gradients must be distinct buffers", what);
+        for (int j = 0; j < i; j++) GSVC_REQUIRE(gfeat_parts[i] != gfeat_parts[j], "%s: the networks' feature gradients must be distinct buffers", what);
+        add[i] = gfeat_parts[i];
+        gen_floats += (gsvc_generator_scratch_floats(&nets[i], M, film && film->rows > 0 ? film->rows : 0) + 3) / 4 * 4;
     }
-    float *const w0 = grads->W[0];
-    auto tail = [=](hipStream_t wst) {
-        if (!want1) return;
-        (void)hipMemcpy2DAsync(w0, (size_t)(FEAT + COND) * 4, stage_f, (size_t)FEAT * 4, (size_t)FEAT * 4, HID, hipMemcpyDeviceToDevice, wst);
-        (void)hipMemcpy2DAsync(w0 + FEAT, (size_t)(FEAT + COND) * 4, stage_c, (size_t)COND * 4, (size_t)COND * 4, HID, hipMemcpyDeviceToDevice, wst);
-    };
-    if (nred && g_wgrad_hold && g_wgrad_stream != nullptr) {
-        g_wgrad_deferred.push_back(DeferredWgrad{std::vector<gsvc_wgrad_partial_job>(part, part + nred),
-                                                 std::vector<gsvc_wgrad_reduce_job>(red, red + nred), tail});
-        return check_launch("deform_backward");
+    GSVC_REQUIRE(saved[n_nets] && gy[n_nets] && aligned16({saved[n_nets], gy[n_nets]}), "%s: NULL or unaligned pointer (deformation network)", what);
+    // on a side stream the generators' products still read their scratch when the deformation network's chain kernels write theirs
+    GSVC_REQUIRE(!wgrad_stream || scratch + gen_floats <= scratch_deform || scratch_deform + gsvc_deform_scratch_floats(deform, M) <= scratch,
+                 "%s: scratch and scratch_deform overlap (with a wgrad_stream they must be two buffers)", what);
+    hipStream_t s = (hipStream_t)stream, ws = s;
+    WgradJobs gen_jobs, deform_jobs;
+    if (int rc = generators_backward(nets, n_nets, feat, cond, M, film, saved, y, gy, scratch, gfeat_parts, gen_grads, gen_jobs, s)) return rc;
+    if (!wgrad_stream)
+        if (int rc = gen_jobs.run(s)) return rc;
+    if (int rc = deform_backward(deform, feat, cond, M, saved[n_nets], gy[n_nets], scratch_deform, gfeat_sum, add, deform_grads, deform_jobs, s))
+        return rc;
+    if (wgrad_stream && gen_jobs.n + deform_jobs.n > 0) {      // all four chain kernels are queued: the products beside what follows them
+        ws = wgrad_stream_behind(s, (hipStream_t)wgrad_stream);
+        if (int rc = gen_jobs.run(ws)) return rc;
     }
-    hipStream_t wst = nred ? wgrad_stream_behind(s) : s;
-    if (nred)
-        if (int rc = run_wgrad(part, red, nred, wst)) return rc;
-    tail(wst);
-    return check_launch("deform_backward");
+    if (int rc = deform_jobs.run(ws)) return rc;
+    if (float *w0 = deform_grads->W[0]) {      // layer 1's halves side by side
+        const DeformScratch sc(scratch_deform, M);
+        (void)hipMemcpy2DAsync(w0, (size_t)(FEAT + COND) * 4, sc.stage_f, (size_t)FEAT * 4, (size_t)FEAT * 4, HID, hipMemcpyDeviceToDevice, ws);
+        (void)hipMemcpy2DAsync(w0 + FEAT, (size_t)(FEAT + COND) * 4, sc.stage_c, (size_t)COND * 4, (size_t)COND * 4, HID, hipMemcpyDeviceToDevice, ws);
+    }
+    return check_launch(what);
 }
 
 // ---- quant_step nets ----------------------------------------------------------------------------------------------------------

@@ -20,6 +20,7 @@ everything that depends on the anchor features) and the trunk.
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 
 import torch
@@ -76,8 +77,7 @@ class WgradBatch:
     ARENA = 1 << 26     # floats (a product asks for 256 slots of N K + N; the batch launch uses 256 slots in all)
 
     def __init__(self, dev):
-        import ctypes as C
-        self.dev, self.C = dev, C
+        self.dev = dev
         self.ws = _workspace(dev, self.ARENA)
         self.off, self.jobs, self.keep = 0, [], []
         self.stream = _lib.current_stream(dev)
@@ -295,7 +295,6 @@ class _QuantStepNets(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, *params):
-        import ctypes as C
         x = x.contiguous()
         params = [p.contiguous() for p in params]
         M, dev = x.shape[0], x.device
@@ -331,7 +330,6 @@ class _QuantStepNets(torch.autograd.Function):
         nets = (_lib.QuantStepNetC * 3)()
         for i in range(3):
             nets[i] = _lib.QuantStepNetC(*[t.data_ptr() for t in params[4 * i:4 * i + 4]])
-        import ctypes as C
         dq = (C.c_void_p * 3)(*[None if g is None else g.data_ptr() for g in gq])
         _lib.check(_lib.lib().gsvc_quant_step_nets_backward(nets, _ptr_array(zs), dq, M, x.shape[1], H, _ptr_array(dzs), _lib.ptr(dX),
                                                             _lib.current_stream(dev)), "gsvc_quant_step_nets_backward")
@@ -487,7 +485,7 @@ def film_nets(film, condition):
 
 def generator(net, feature, condition=None, film=None):
     """GeneratorNet forward as two autograd functions; ``film``: a (gamma, beta) pair computed ahead with ``film_nets``."""
-    act = {"Tanh": ACT_TANH, "Sigmoid": ACT_SIGMOID, "Identity": ACT_NONE}[type(net.out_act).__name__]
+    act = _act_code(net)
     gamma, beta = film if film is not None else film_nets(net.film, condition)
     params = []
     for l in (net.linear1, net.linear2, net.out_linear):
@@ -553,59 +551,65 @@ def _gen_desc(params, act, out_dim):
     return d
 
 
-def _deform_desc(params):
-    d = _lib.DeformNetC()
-    for i in range(5):
-        d.W[i], d.b[i] = params[2 * i].data_ptr(), params[2 * i + 1].data_ptr()
-    d.feat_dim, d.cond_dim, d.hidden_dim, d.out_dim = 50, 66, 100, 30
-    return d
-
-
-def _film_desc(film):
-    """gsvc_film_rows of (cond_film [Mf, 66], row_of [M] int32, src_a [Mf] int32, src_b [Mf] int32), or NULL."""
-    if film is None:
-        return None
-    import ctypes as C
-    cond_f, row_of, src_a, src_b = film
-    d = _lib.FilmRowsC(int(cond_f.shape[0]), cond_f.data_ptr(), row_of.data_ptr(), src_a.data_ptr(), src_b.data_ptr())
-    return C.byref(d)
-
-
 def _ptr_array(tensors):
-    import ctypes as C
     return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+def _chain_desc(params, acts, film, grads=None):
+    """The C descriptors of a generation pass: (nets, deform, film, film_rows, gen_grads, deform_grads) — the three gsvc_generator_net,
+    mlp_deform's gsvc_deform_net, the gsvc_film_rows of film = (cond_film [Mf, 66], row_of [M] int32, src_a [Mf] int32, src_b [Mf]
+    int32) or NULL with its row count (0), and, with ``grads`` (one tensor per parameter), where the backward writes them."""
+    nets = (_lib.GeneratorNetC * 3)()
+    for g in range(3):
+        pg = params[14 * g:14 * (g + 1)]
+        nets[g] = _gen_desc(pg, acts[g], pg[4].shape[0])
+    dd = _lib.DeformNetC()
+    for i in range(5):
+        dd.W[i], dd.b[i] = params[42 + 2 * i].data_ptr(), params[43 + 2 * i].data_ptr()
+    dd.feat_dim, dd.cond_dim, dd.hidden_dim, dd.out_dim = 50, 66, 100, 30
+    film_p, Mf = None, 0
+    if film is not None:
+        cond_f, row_of, src_a, src_b = film
+        Mf = int(cond_f.shape[0])
+        film_p = C.byref(_lib.FilmRowsC(Mf, cond_f.data_ptr(), row_of.data_ptr(), src_a.data_ptr(), src_b.data_ptr()))
+    gds = gd = None
+    if grads is not None:
+        gds = (_lib.GeneratorGradsC * 3)()
+        for g in range(3):
+            for name, v in zip(GEN_FIELDS, grads[14 * g:14 * (g + 1)]):
+                setattr(gds[g], name, v.data_ptr())
+        gd = _lib.DeformGradsC()
+        for i in range(5):
+            gd.W[i], gd.b[i] = grads[42 + 2 * i].data_ptr(), grads[43 + 2 * i].data_ptr()
+    return nets, dd, film_p, Mf, gds, gd
+
+
+def _chain_forward(feat, cond, acts, film, params, keep):
+    """(outs, saved) of gsvc_generate_all_forward on contiguous operands: the four outputs and, per network, what the backward
+    reads (keep) or the small scratch of the forward-only form, whose kernels leave out every store only a backward would read."""
+    M, dev = feat.shape[0], feat.device
+    L = _lib.lib()
+    nets, dd, film_p, Mf, _, _ = _chain_desc(params, acts, film)
+    gen_floats = L.gsvc_generator_saved_floats if keep else L.gsvc_generator_inference_floats
+    deform_floats = L.gsvc_deform_saved_floats if keep else L.gsvc_deform_inference_floats
+    sizes = [int(gen_floats(C.byref(nets[g]), M, Mf)) for g in range(3)] + [int(deform_floats(C.byref(dd), M))]
+    saved = [torch.empty(n, device=dev, dtype=torch.float32) for n in sizes]
+    outs = [torch.empty(M, n, device=dev, dtype=torch.float32) for n in (nets[0].out_dim, nets[1].out_dim, nets[2].out_dim, 30)]
+    _lib.check(L.gsvc_generate_all_forward(nets, 3, C.byref(dd), _lib.ptr(feat), _lib.ptr(cond), M, film_p, _ptr_array(saved), _ptr_array(outs),
+                                           int(keep), _lib.current_stream(dev)), "gsvc_generate_all_forward")
+    return outs, saved
 
 
 class _GenerateAll(torch.autograd.Function):
     """(opacity, color, cov, deform) outputs of the three GeneratorNets and mlp_deform for the rows (feature, condition).
     params = 3 x 14 generator tensors (GEN_FIELDS order) + 5 x (W, b) of mlp_deform; acts = the generators' output activations.
-    The three generators run as ONE pair of launches each way (gsvc_generators_*: workgroup b serves network b % 3)."""
+    One library call each way (gsvc_generate_all_*); the three generators share a pair of launches (workgroup b serves network b % 3)."""
 
     @staticmethod
     def forward(ctx, feat, cond, acts, film, *params):
-        import ctypes as C
         feat, cond = feat.contiguous(), cond.contiguous()
         params = [p.contiguous() for p in params]
-        M, dev = feat.shape[0], feat.device
-        L, st = _lib.lib(), _lib.current_stream(dev)
-        nets = (_lib.GeneratorNetC * 3)()
-        outs, saved = [], []
-        Mf = int(film[0].shape[0]) if film is not None else 0
-        for g in range(3):
-            pg = params[14 * g:14 * (g + 1)]
-            d = _gen_desc(pg, acts[g], pg[4].shape[0])
-            C.memmove(C.byref(nets[g]), C.byref(d), C.sizeof(d))
-            saved.append(torch.empty(int(L.gsvc_generator_saved_floats(C.byref(d), M, Mf)), device=dev, dtype=torch.float32))
-            outs.append(torch.empty(M, pg[4].shape[0], device=dev, dtype=torch.float32))
-        _lib.check(L.gsvc_generators_forward(nets, 3, _lib.ptr(feat), _lib.ptr(cond), M, _film_desc(film), _ptr_array(saved),
-                                             _ptr_array(outs), st), "gsvc_generators_forward")
-        pd = params[42:52]
-        dd = _deform_desc(pd)
-        sv = torch.empty(int(L.gsvc_deform_saved_floats(C.byref(dd), M)), device=dev, dtype=torch.float32)
-        y = torch.empty(M, 30, device=dev, dtype=torch.float32)
-        _lib.check(L.gsvc_deform_forward(C.byref(dd), _lib.ptr(feat), _lib.ptr(cond), M, _lib.ptr(sv), _lib.ptr(y), st), "gsvc_deform_forward")
-        outs.append(y)
-        saved.append(sv)
+        outs, saved = _chain_forward(feat, cond, acts, film, params, keep=True)
         ctx.acts = tuple(acts)
         ctx.film = film          # index tensors and the FiLM rows' condition: no gradient flows to them
         ctx.save_for_backward(feat, cond, *outs[:3], *saved, *params)
@@ -613,12 +617,10 @@ class _GenerateAll(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *gys):
-        import ctypes as C
         t = ctx.saved_tensors
         feat, cond, ys, saved, params = t[0], t[1], t[2:5], t[5:9], t[9:]
         M, dev = feat.shape[0], feat.device
         L, st = _lib.lib(), _lib.current_stream(dev)
-        need = ctx.needs_input_grad
         # an output nobody used has no gradient: it contributes zeros (rare: every training mode reads all four)
         gys = [g.contiguous() if g is not None else torch.zeros(M, n, device=dev, dtype=torch.float32) for g, n in
                zip(gys, [y.shape[1] for y in ys] + [30])]
@@ -627,59 +629,31 @@ class _GenerateAll(torch.autograd.Function):
         for p in params:
             grads.append(flat[at:at + p.numel()].view(p.shape))
             at += p.numel()
-        nets = (_lib.GeneratorNetC * 3)()
-        gds = (_lib.GeneratorGradsC * 3)()
-        total = 0
-        for g in range(3):
-            pg = params[14 * g:14 * (g + 1)]
-            d = _gen_desc(pg, ctx.acts[g], pg[4].shape[0])
-            C.memmove(C.byref(nets[g]), C.byref(d), C.sizeof(d))
-            for name, v in zip(GEN_FIELDS, grads[14 * g:14 * (g + 1)]):
-                setattr(gds[g], name, v.data_ptr())
-            total += (int(L.gsvc_generator_scratch_floats(C.byref(d), M, int(ctx.film[0].shape[0]) if ctx.film is not None else 0)) + 3) // 4 * 4
-        dd = _deform_desc(params[42:52])
+        nets, dd, film_p, Mf, gds, gd = _chain_desc(params, ctx.acts, ctx.film, grads)
+        total = sum((int(L.gsvc_generator_scratch_floats(C.byref(nets[g]), M, Mf)) + 3) // 4 * 4 for g in range(3))
+        total_d = int(L.gsvc_deform_scratch_floats(C.byref(dd), M))
         # a GPU-bound step's backward offers the weight gradients a stream of their own (gsvc_amd.schedule.backward_streams): the dW
-        # products run there behind the chain kernels while the step's stream carries the feature gradient on
+        # products run there behind all four chain kernels while the step's stream carries the feature gradient on
         side = schedule.take_wgrad_stream() if dev.type == "cuda" else None
         if side is None:
-            total = max(total, int(L.gsvc_deform_scratch_floats(C.byref(dd), M)))      # the deformation network reuses the generators' scratch
-            scratch = scratch_d = torch.empty(total, device=dev, dtype=torch.float32)
+            scratch = scratch_d = torch.empty(max(total, total_d), device=dev, dtype=torch.float32)      # the deformation network reuses the generators' scratch
         else:
             # the generators' weight gradients are still reading their scratch (on the side stream) when the deformation network's chain
             # kernels write theirs: two buffers; and everything those products touch outlives this function on THAT stream
             scratch = torch.empty(total, device=dev, dtype=torch.float32)
-            scratch_d = torch.empty(int(L.gsvc_deform_scratch_floats(C.byref(dd), M)), device=dev, dtype=torch.float32)
+            scratch_d = torch.empty(total_d, device=dev, dtype=torch.float32)
             for x in (feat, cond, *saved, scratch, scratch_d, flat, gys[3], *((ctx.film[0],) if ctx.film is not None else ())):
                 x.record_stream(side)
-            # both networks' chain kernels first, then every product beside what follows: a chain workgroup needs its whole CU, and the
-            # generators' products queued ahead of mlp_deform's chain kernels made those wait for them (6.81 -> 6.78 ms per step)
-            _lib.check(L.gsvc_set_wgrad_stream(side.cuda_stream), "gsvc_set_wgrad_stream")
-            _lib.check(L.gsvc_wgrad_hold(1), "gsvc_wgrad_hold")
         F_ = feat.shape[1]
         per = (M * F_ + 3) // 4 * 4                                                      # every buffer starts 16-byte aligned
         gflat = torch.empty(4 * per, device=dev, dtype=torch.float32)                   # three generators' + the sum
         gfeats = [gflat[i * per:i * per + M * F_].view(M, F_) for i in range(4)]
-        gen_gf = gfeats[:3]
-        try:
-            _lib.check(L.gsvc_generators_backward(nets, 3, _lib.ptr(feat), _lib.ptr(cond), M, _film_desc(ctx.film), _ptr_array(saved[:3]),
-                                                  _ptr_array(ys), _ptr_array(gys[:3]), _lib.ptr(scratch), _ptr_array(gen_gf), gds, st),
-                       "gsvc_generators_backward")
-            gd = _lib.DeformGradsC()
-            for i in range(5):
-                gd.W[i], gd.b[i] = grads[42 + 2 * i].data_ptr(), grads[43 + 2 * i].data_ptr()
-            # the deformation network's backward runs behind the generators' (same stream): it adds their three feature gradients to
-            # its own in the pass that writes gfeat
-            _lib.check(L.gsvc_deform_backward(C.byref(dd), _lib.ptr(feat), _lib.ptr(cond), M, _lib.ptr(saved[3]), _lib.ptr(gys[3]),
-                                              _lib.ptr(scratch_d), _lib.ptr(gfeats[3]), 0, _ptr_array(gen_gf), 3, C.byref(gd), st),
-                       "gsvc_deform_backward")
-        finally:
-            if side is not None:      # (also after an error: nothing stays held or set)
-                rc = L.gsvc_wgrad_flush(st)
-                L.gsvc_wgrad_hold(0)
-                L.gsvc_set_wgrad_stream(None)
-        if side is not None:
-            _lib.check(rc, "gsvc_wgrad_flush")
-        return (gfeats[3] if need[0] else None, None, None, None, *grads)
+        # the deformation network's chain kernel adds the generators' three feature gradients to its own in the pass that writes gfeats[3]
+        _lib.check(L.gsvc_generate_all_backward(nets, 3, C.byref(dd), _lib.ptr(feat), _lib.ptr(cond), M, film_p, _ptr_array(saved), _ptr_array(ys),
+                                                _ptr_array(gys), _lib.ptr(scratch), _lib.ptr(scratch_d), _lib.ptr(gfeats[3]), _ptr_array(gfeats[:3]),
+                                                gds, C.byref(gd), st, side.cuda_stream if side is not None else None),
+                   "gsvc_generate_all_backward")
+        return (gfeats[3] if ctx.needs_input_grad[0] else None, None, None, None, *grads)
 
 
 def generate_all(gens, deform_linears, feat, cond, film=None):
@@ -695,34 +669,6 @@ def generate_all(gens, deform_linears, feat, cond, film=None):
         film = tuple(t.contiguous() for t in film)
         assert film[0].dtype == torch.float32 and all(t.dtype == torch.int32 for t in film[1:])
     acts = tuple(_act_code(n) for n in gens)
-    if not torch.is_grad_enabled():
-        return _generate_all_inference(feat, cond, acts, film, params)
+    if not torch.is_grad_enabled():      # the decoder's render loop, evaluation: nothing is kept for a backward
+        return tuple(_chain_forward(feat.contiguous(), cond.contiguous(), acts, film, [p.detach().contiguous() for p in params], keep=False)[0])
     return _GenerateAll.apply(feat, cond, acts, film, *params)
-
-
-def _generate_all_inference(feat, cond, acts, film, params):
-    """generate_all without autograd (the decoder's render loop, evaluation): the chain kernels leave out every store only a
-    backward would read (gsvc_generators_forward_inference, gsvc_deform_forward_inference)."""
-    import ctypes as C
-    feat, cond = feat.contiguous(), cond.contiguous()
-    params = [p.detach().contiguous() for p in params]
-    M, dev = feat.shape[0], feat.device
-    L, st = _lib.lib(), _lib.current_stream(dev)
-    nets = (_lib.GeneratorNetC * 3)()
-    outs, scratch = [], []
-    Mf = int(film[0].shape[0]) if film is not None else 0
-    for g in range(3):
-        pg = params[14 * g:14 * (g + 1)]
-        d = _gen_desc(pg, acts[g], pg[4].shape[0])
-        C.memmove(C.byref(nets[g]), C.byref(d), C.sizeof(d))
-        scratch.append(torch.empty(int(L.gsvc_generator_inference_floats(C.byref(d), M, Mf)), device=dev, dtype=torch.float32))
-        outs.append(torch.empty(M, pg[4].shape[0], device=dev, dtype=torch.float32))
-    _lib.check(L.gsvc_generators_forward_inference(nets, 3, _lib.ptr(feat), _lib.ptr(cond), M, _film_desc(film), _ptr_array(scratch),
-                                                   _ptr_array(outs), st), "gsvc_generators_forward_inference")
-    dd = _deform_desc(params[42:52])
-    sc = torch.empty(max(M, 1) * 100, device=dev, dtype=torch.float32)
-    y = torch.empty(M, 30, device=dev, dtype=torch.float32)
-    _lib.check(L.gsvc_deform_forward_inference(C.byref(dd), _lib.ptr(feat), _lib.ptr(cond), M, _lib.ptr(sc), _lib.ptr(y), st),
-               "gsvc_deform_forward_inference")
-    outs.append(y)
-    return tuple(outs)

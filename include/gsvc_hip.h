@@ -635,21 +635,6 @@ int gsvc_pair_rows_sum(const float *g, const int32_t *src_a, const int32_t *src_
  * reference-shaped scatter-adds (utils/entropy_models.py:159-175's gradient, the index_add of guassian.py:160-176's gathers). */
 int gsvc_set_deterministic(int on);
 
-/* The weight gradients of gsvc_generators_backward / gsvc_generator_backward / gsvc_deform_backward on ANOTHER stream: with a non-NULL
- * stream set here those entries queue their chain kernels on the caller's stream as before, record an event there, and queue the
- * dW = G^T X products and their reduces (reference: autograd's weight gradients of scene/gaussian_model.py:150-196, 468-489) on
- * `stream` behind that event — so the caller's stream can go on with the feature gradient while they run.  The caller then owns
- * the hazards: the products read feat, cond, the saved activations, the scratch (which the two entries must therefore NOT share) and
- * gy of the deformation network, and write the gradient tensors, until `stream` has passed; the optimizer's stream must wait for
- * it.  NULL (the default): everything on the caller's stream.  Process-wide; not for concurrent callers. */
-int gsvc_set_wgrad_stream(void *stream);
-/* gsvc_wgrad_hold(1): while a stream is set, those entries keep their weight-gradient launches back (their operands by value);
- * gsvc_wgrad_flush(stream) records the event on `stream` NOW and queues every held product behind it — for a caller that runs
- * several chain backward passes in a row and wants all their chain kernels queued before the first product starts beside them
- * (a chain workgroup needs its whole CU).  Held launches that are never flushed are dropped by the next flush's owner: flush before
- * gsvc_wgrad_hold(0). */
-int gsvc_wgrad_hold(int32_t on);
-int gsvc_wgrad_flush(void *stream);
 int gsvc_segment_rows_sum(const float *src, const int64_t *order, const int64_t *sorted_idx, int64_t n, int32_t C, float *dst,
                           int32_t accumulate, void *stream);
 
@@ -797,12 +782,7 @@ int gsvc_linear_wgrad_partial_many(gsvc_wgrad_partial_job *jobs, int32_t n_jobs,
  * guassian.py:264-273) on cat([feature, condition]).  All matrices row-major fp32, weights in torch.nn.Linear layout [out, in],
  * every pointer 16-byte aligned.  Instantiated widths: feature 50, condition 66, hidden 100, outputs 10 / 30 / 70 (generators)
  * and 30 (deform); anything else returns GSVC_E_UNSUPPORTED (callers keep the gsvc_linear_* layer path).
- *   _forward : y[M, out]; `saved` (gsvc_*_saved_floats floats, caller-owned) receives what the backward reads.
- *   _backward: from gy[M, out] forms d feature (gfeat[M, feat]; accumulate_gfeat != 0 adds to what is there — the feature
- *              matrix feeds four networks), and every weight / bias gradient (dW = G^T X by the row-split kernels of
- *              gsvc_linear_wgrad_partial + one batched slot reduce: deterministic, no atomics) into the pointers of `grads`
- *              (a NULL weight pointer skips that layer).  The condition receives no gradient (it is the positional embedding of
- *              detached anchor positions / the frame time).  `scratch`: gsvc_*_scratch_floats floats.
+ * The condition receives no gradient (it is the positional embedding of detached anchor positions / the frame time).
  * out_act: 0 identity, 1 tanh, 2 sigmoid. */
 typedef struct gsvc_generator_net {
     const float *W1, *b1, *W2, *b2, *W3, *b3;                             /* linear1, linear2, out_linear */
@@ -812,11 +792,6 @@ typedef struct gsvc_generator_net {
 typedef struct gsvc_generator_grads {
     float *W1, *b1, *W2, *b2, *W3, *b3, *Wg0, *bg0, *Wg1, *bg1, *Wb0, *bb0, *Wb1, *bb1;
 } gsvc_generator_grads;
- /* gsvc_generators_*: n_nets (1 .. 3) networks on the same (feat, cond) rows in ONE pair of launches each way (workgroup b serves
- * network b % n_nets: one prologue and one partial last round for all of them).  saved / y / gy / gfeat are arrays of n_nets
- * pointers; `scratch` holds the networks' regions back to back (sum of gsvc_generator_scratch_floats, each rounded up to a
- * multiple of 4 floats); gfeat[i] receives network i's feature gradient (distinct buffers, written, not accumulated: pass them
- * to gsvc_deform_backward as addends, or add them up). */
 /* Shared FiLM rows.  gamma / beta depend on the condition only, and the two opposite views of a frame (the training step renders
  * both: reference pipeline/train.py:353-387) have the same condition for the same anchor — same camera z, same anchor z — while
  * their features differ (independent quantisation noise per render).  With a gsvc_film_rows the FiLM networks (4 of a
@@ -832,21 +807,7 @@ typedef struct gsvc_film_rows {
 } gsvc_film_rows;
 int64_t gsvc_generator_saved_floats(const gsvc_generator_net *net, int64_t M, int64_t film_rows);
 int64_t gsvc_generator_scratch_floats(const gsvc_generator_net *net, int64_t M, int64_t film_rows);
-int gsvc_generator_forward(const gsvc_generator_net *net, const float *feat, const float *cond, int64_t M, float *saved, float *y,
-                           void *stream);
-int gsvc_generators_forward(const gsvc_generator_net *nets, int32_t n_nets, const float *feat, const float *cond, int64_t M,
-                            const gsvc_film_rows *film, float *const *saved, float *const *y, void *stream);
-/* Forward only (the decoder's render loop, evaluation): the same kernels with every store the backward alone would read left out.
- * scratch[i]: gsvc_generator_inference_floats(net, M, film_rows) floats (gamma / beta of the FiLM networks); deform: HID M floats. */
 int64_t gsvc_generator_inference_floats(const gsvc_generator_net *net, int64_t M, int64_t film_rows);
-int gsvc_generators_forward_inference(const gsvc_generator_net *nets, int32_t n_nets, const float *feat, const float *cond, int64_t M,
-                                      const gsvc_film_rows *film, float *const *scratch, float *const *y, void *stream);
-int gsvc_generators_backward(const gsvc_generator_net *nets, int32_t n_nets, const float *feat, const float *cond, int64_t M,
-                             const gsvc_film_rows *film, const float *const *saved, const float *const *y, const float *const *gy,
-                             float *scratch, float *const *gfeat, const gsvc_generator_grads *grads, void *stream);
-int gsvc_generator_backward(const gsvc_generator_net *net, const float *feat, const float *cond, int64_t M, const float *saved,
-                            const float *y, const float *gy, float *scratch, float *gfeat, int32_t accumulate_gfeat,
-                            const gsvc_generator_grads *grads, void *stream);
 
 typedef struct gsvc_deform_net {
     const float *W[5], *b[5];                                             /* mlp_deform's five Linear layers, input = [feat | cond] */
@@ -857,13 +818,44 @@ typedef struct gsvc_deform_grads {
 } gsvc_deform_grads;
 int64_t gsvc_deform_saved_floats(const gsvc_deform_net *net, int64_t M);
 int64_t gsvc_deform_scratch_floats(const gsvc_deform_net *net, int64_t M);
-int gsvc_deform_forward(const gsvc_deform_net *net, const float *feat, const float *cond, int64_t M, float *saved, float *y, void *stream);
-/* gfeat_addends: n_addends (0 .. 3) further [M, feat] gradients summed into gfeat in the same pass (the generators' feature gradients) */
-int gsvc_deform_forward_inference(const gsvc_deform_net *net, const float *feat, const float *cond, int64_t M, float *scratch, float *y,
-                                  void *stream);
-int gsvc_deform_backward(const gsvc_deform_net *net, const float *feat, const float *cond, int64_t M, const float *saved, const float *gy,
-                         float *scratch, float *gfeat, int32_t accumulate_gfeat, const float *const *gfeat_addends, int32_t n_addends,
-                         const gsvc_deform_grads *grads, void *stream);
+int64_t gsvc_deform_inference_floats(const gsvc_deform_net *net, int64_t M);
+
+/* A generation pass: n_nets (1 .. 3) generators and the deformation network on the same (feat, cond) rows, one call each way.
+ * The generators share ONE pair of launches each way (workgroup b serves network b % n_nets: one prologue and one partial last
+ * round for all of them).
+ * gsvc_generate_all_forward: saved / y are arrays of n_nets + 1 pointers, the deformation network last; y[i] is [M, out].  Launch
+ *   order on `stream`: k_film_nets_fwd, k_trunk_fwd, k_deform_a_fwd, k_deform_b_fwd.  keep_for_backward != 0: saved[i] (caller-owned,
+ *   gsvc_*_saved_floats floats) receives what the backward reads.  keep_for_backward == 0 (the decoder's render loop, evaluation):
+ *   the same kernels with every store the backward alone would read left out; saved[i] is then the small scratch of
+ *   gsvc_*_inference_floats (gamma / beta of the FiLM networks; the deformation network's second activation).
+ * gsvc_generate_all_backward: from gy (n_nets + 1 pointers, [M, out] each; y: the n_nets generators' outputs) forms the feature
+ *   gradient and every weight / bias gradient (dW = G^T X by the row-split kernels of gsvc_linear_wgrad_partial + one batched slot
+ *   reduce per network kind: deterministic, no atomics) into the pointers of gen_grads[i] / deform_grads (a NULL weight pointer skips
+ *   that layer).  gfeat_parts[i] [M, feat] receives generator i's feature gradient (distinct buffers, written, not accumulated);
+ *   the deformation kernel adds them to its own in the pass that writes gfeat_sum [M, feat] (the feature matrix feeds all the
+ *   networks).  `scratch`: the generators' regions back to back (sum of gsvc_generator_scratch_floats, each rounded up to a multiple
+ *   of 4 floats); `scratch_deform`: gsvc_deform_scratch_floats floats.
+ *   wgrad_stream == NULL: everything on `stream`, in this order: k_trunk_bwd, k_film_nets_bwd, the generators' partial and reduce
+ *   launches, k_deform_b_bwd, k_deform_a_bwd, the deformation network's partial and reduce launches, the two strided copies that
+ *   interleave its first layer's halves.  scratch_deform may alias scratch (the larger of the two sizes).
+ *   wgrad_stream != NULL: the four chain kernels go on `stream` first (a chain workgroup needs its whole CU: a product queued in
+ *   between makes the second network's chain kernels wait for it), one event is recorded behind them, wgrad_stream waits for it
+ *   and carries the generators' products and reduce, the deformation network's, then the copies — so `stream` can go on with the
+ *   feature gradient while they run.  The generators' products still read `scratch` when the deformation network's chain kernels
+ *   write `scratch_deform`: an overlap of the two is refused (GSVC_E_INVALID, nothing launched; M == 0 returns before any buffer
+ *   is looked at).  If the event cannot be made, recorded or waited for, the products go on `stream` instead: still ordered, not
+ *   overlapped.  The caller owns the remaining hazards: the products read feat, cond (the FiLM rows' condition), saved, both
+ *   scratches and gy of the deformation network, and write the gradient tensors, until wgrad_stream has passed; the optimizer's
+ *   stream must wait for it.
+ * No state is kept between calls: thread-safe per stream like every other entry. */
+int gsvc_generate_all_forward(const gsvc_generator_net *nets, int32_t n_nets, const gsvc_deform_net *deform, const float *feat,
+                              const float *cond, int64_t M, const gsvc_film_rows *film, float *const *saved, float *const *y,
+                              int32_t keep_for_backward, void *stream);
+int gsvc_generate_all_backward(const gsvc_generator_net *nets, int32_t n_nets, const gsvc_deform_net *deform, const float *feat,
+                               const float *cond, int64_t M, const gsvc_film_rows *film, const float *const *saved, const float *const *y,
+                               const float *const *gy, float *scratch, float *scratch_deform, float *gfeat_sum, float *const *gfeat_parts,
+                               const gsvc_generator_grads *gen_grads, const gsvc_deform_grads *deform_grads, void *stream,
+                               void *wgrad_stream);
 
 /* ------------------------------------------------------------------------------------------------------
  * [INTERNAL] Anchor geometry decode (the G-PCC tmc3 step of reference utils/encodings.py:780-826 decode_anchor; coder and bitstream are this

@@ -198,21 +198,15 @@ def test_fused_row_gather_and_context_tail_match_the_tensor_paths(monkeypatch):
         assert (a - b).abs().max().item() <= 1e-6 * max(1.0, b.abs().max().item())
 
 
-@pytest.mark.parametrize("M,share", [(4096, False), (6001, False), (20011, False), (6001, True), (20011, True)])
-def test_whole_network_chain_kernels_match_torch(M, share):
-    """gsvc_generator_* / gsvc_deform_* (csrc/mlp_chain.hip: a 16-row block's activations stay in registers from the network's
-    input to its output) through gsvc_amd.mlp.generate_all — the three GeneratorNets (out 10 tanh / 30 sigmoid / 70) and
-    mlp_deform (116 -> 100 x4 -> 30) on the same (feature, condition) rows — against plain PyTorch fp32: the four outputs, the
-    accumulated feature gradient and every weight / bias gradient (reference scene/gaussian_model.py:150-196, 468-489).
-    M = 4096: whole 16-row blocks; 6001, 20011: ragged last block, odd row counts (8-byte aligned matrix bases)."""
-    from gsvc_amd import mlp
+def _chain_networks(M, share):
+    """The three GeneratorNets (out 10 tanh / 30 sigmoid / 70), mlp_deform (116 -> 100 x4 -> 30) and (feature, condition) rows of
+    the whole-network chain tests; share: the two "views" of the rows share FiLM rows (gsvc_film_rows)."""
     from gsvc_amd.model import GeluSequential, GeneratorNet, Linear
     torch.manual_seed(M)
     gens = [GeneratorNet(50, 10, 100, 66, out_act=torch.nn.Tanh()).cuda(), GeneratorNet(50, 30, 100, 66, out_act=torch.nn.Sigmoid()).cuda(),
             GeneratorNet(50, 70, 100, 66).cuda()]
     deform = GeluSequential(Linear(116, 100), torch.nn.GELU(), Linear(100, 100), torch.nn.GELU(), Linear(100, 100), torch.nn.GELU(),
                             Linear(100, 100), torch.nn.GELU(), Linear(100, 30)).cuda()
-    lin = list(deform)[0::2]
     feat = (torch.randn(M, 50, device="cuda") * 2).requires_grad_(True)
     cond = torch.randn(M, 66, device="cuda")
     film = None
@@ -232,6 +226,19 @@ def test_whole_network_chain_kernels_match_torch(M, share):
         src_b[in_b] = torch.arange(na, M, dtype=torch.int32, device="cuda")
         cond = cond_film.index_select(0, row_of.long())
         film = (cond_film, row_of, src_a, src_b)
+    return gens, deform, feat, cond, film
+
+
+@pytest.mark.parametrize("M,share", [(4096, False), (6001, False), (20011, False), (6001, True), (20011, True)])
+def test_whole_network_chain_kernels_match_torch(M, share):
+    """gsvc_generate_all_forward / _backward (csrc/mlp_chain.hip: a 16-row block's activations stay in registers from the network's
+    input to its output) through gsvc_amd.mlp.generate_all — the three GeneratorNets (out 10 tanh / 30 sigmoid / 70) and
+    mlp_deform (116 -> 100 x4 -> 30) on the same (feature, condition) rows — against plain PyTorch fp32: the four outputs, the
+    accumulated feature gradient and every weight / bias gradient (reference scene/gaussian_model.py:150-196, 468-489).
+    M = 4096: whole 16-row blocks; 6001, 20011: ragged last block, odd row counts (8-byte aligned matrix bases)."""
+    from gsvc_amd import mlp
+    gens, deform, feat, cond, film = _chain_networks(M, share)
+    lin = list(deform)[0::2]
     gs = [torch.randn(M, n, device="cuda") for n in (10, 30, 70, 30)]
     with torch.no_grad():
         # rows with a FiLM ReLU pre-activation within rounding of its kink take no part in the gradient comparison
@@ -283,7 +290,67 @@ def test_whole_network_chain_kernels_match_torch(M, share):
     d = mlp._gen_desc(mlp._generator_params(gens[0]), 1, 10)
     d.hidden_dim = 96
     assert _lib.lib().gsvc_generator_saved_floats(C.byref(d), 16, 0) > 0
-    assert _lib.lib().gsvc_generator_forward(C.byref(d), None, None, 16, None, None, None) == -3
+    assert _lib.lib().gsvc_generate_all_forward(C.byref(d), 1, None, None, None, 16, None, None, None, 1, None) == -3
+
+
+@pytest.mark.parametrize("share", [False, True])
+def test_chain_weight_gradients_on_a_side_stream_are_the_same_bits(monkeypatch, share):
+    """gsvc_generate_all_backward with a wgrad_stream (the dW products behind all four chain kernels, on their own stream) against
+    the same call without one, through gsvc_amd.mlp.generate_all inside gsvc_amd.schedule.backward_streams: the same kernels on the
+    same operands, so the feature gradient and every weight / bias gradient have the same bits once the scope has joined the
+    streams (they are read only after it).  M = 6001: the smallest ragged size above mlp.MIN_ROWS (odd row count, partial last 16-row block).  With a
+    wgrad_stream the two scratch buffers must not overlap: the library refuses that before it launches anything."""
+    import ctypes as C
+    from gsvc_amd import _lib, mlp, schedule
+    M = 6001
+    gens, deform, feat, cond, film = _chain_networks(M, share)
+    lin = list(deform)[0::2]
+    params = [p for net in gens for p in net.parameters()] + list(deform.parameters())
+    gs = [torch.randn(M, n, device="cuda") for n in (10, 30, 70, 30)]
+    monkeypatch.delenv("GSVC_NO_WGRAD_OVERLAP", raising=False)      # the overlap switch on
+    real_take, handed = schedule.take_wgrad_stream, []
+
+    def take():
+        handed.append(real_take())
+        return handed[-1]
+    monkeypatch.setattr(schedule, "take_wgrad_stream", take)
+
+    def run():
+        feat.grad = None
+        for p in params:
+            p.grad = None
+        outs = mlp.generate_all(gens, lin, feat, cond, film=film)
+        sum((o * g).sum() for o, g in zip(outs, gs)).backward()
+        return [feat.grad] + [p.grad for p in params]      # the live tensors: nothing reads them here
+    # the plain run's gradients stay alive to the end, so the side run's cannot land in their storage and pass on stale bits
+    plain = run()
+    assert handed == [None]
+    feat.grad = None
+    for p in params:
+        p.grad = None      # the scope arms the side stream only for parameters without a gradient
+    with schedule.backward_streams(feat.device, params):
+        side = run()
+    # read only now: leaving the scope made the current stream wait for the side stream's products
+    assert len(handed) == 2 and handed[1] is not None and handed[1].cuda_stream == schedule.wgrad_stream(feat.device).cuda_stream
+    assert len(plain) == len(side) == 1 + 3 * 14 + 10
+    for a, b in zip(plain, side):
+        assert a.data_ptr() != b.data_ptr() and torch.equal(a, b)
+    # one scratch for both network kinds and a side stream: refused on the host, nothing is launched
+    torch.cuda.synchronize()
+    L = _lib.lib()
+    plist = [p.detach() for p in params]
+    grads = [torch.empty_like(p) for p in plist]
+    nets, dd, film_p, Mf, gds, gd = mlp._chain_desc(plist, (1, 2, 0), film, grads)
+    saved = [torch.empty(int(L.gsvc_generator_saved_floats(C.byref(nets[g]), M, Mf)), device="cuda") for g in range(3)]
+    saved.append(torch.empty(int(L.gsvc_deform_saved_floats(C.byref(dd), M)), device="cuda"))
+    floats = sum((int(L.gsvc_generator_scratch_floats(C.byref(nets[g]), M, Mf)) + 3) // 4 * 4 for g in range(3))
+    scratch = torch.empty(max(floats, int(L.gsvc_deform_scratch_floats(C.byref(dd), M))), device="cuda")
+    gfeat = [torch.empty(M, 50, device="cuda") for _ in range(4)]
+    x, cnd = feat.detach(), cond.contiguous()
+    rc = L.gsvc_generate_all_backward(nets, 3, C.byref(dd), x.data_ptr(), cnd.data_ptr(), M, film_p, mlp._ptr_array(saved), mlp._ptr_array(gs[:3]),
+                                      mlp._ptr_array(gs), scratch.data_ptr(), scratch.data_ptr(), gfeat[3].data_ptr(), mlp._ptr_array(gfeat[:3]),
+                                      gds, C.byref(gd), _lib.current_stream(x.device), schedule.wgrad_stream(x.device).cuda_stream)
+    assert rc == -1 and b"overlap" in L.gsvc_last_error()      # GSVC_E_INVALID
 
 
 def test_entropy_sub_networks_as_one_function_match_torch():

@@ -1362,11 +1362,11 @@ def test_deterministic_mode_computes_the_default_modes_gradients(monkeypatch):
 @pytest.mark.parametrize("batched", [True, False])
 def test_weight_gradients_on_their_own_stream_are_the_same_gradients(monkeypatch, batched):
     """In a GPU-bound step's backward (gsvc_amd.schedule.backward_streams) the generators' / mlp_deform's weight-gradient products run
-    on a side stream behind the chain kernels (gsvc_set_wgrad_stream, taken by mlp._GenerateAll.backward) while the step's stream
+    on a side stream behind the chain kernels (gsvc_generate_all_backward's wgrad_stream, taken by mlp._GenerateAll.backward) while the step's stream
     carries the feature gradient on.  The same kernels on the same operands: under GSVC_DETERMINISTIC=1 every parameter's gradient
     has the SAME BITS with and without the side stream, in every phase, step after step.  The steps are made GPU-bound by the row
-    threshold (0), the model has the production widths (the chain kernels exist for those only), and a spy on the library's
-    gsvc_set_wgrad_stream shows the stream taken once in every batched step — and never in the per-render form, which has no batch
+    threshold (0), the model has the production widths (the chain kernels exist for those only), and a spy on the wgrad_stream argument
+    of the library's gsvc_generate_all_backward shows the stream taken once in every batched step — and never in the per-render form, which has no batch
     and so no side stream at all."""
     import os
     from gsvc_amd import _lib, schedule, switches
@@ -1378,14 +1378,14 @@ def test_weight_gradients_on_their_own_stream_are_the_same_gradients(monkeypatch
     monkeypatch.setenv("GSVC_DETERMINISTIC", "1")
     switches.reload()
     L = _lib.lib()
-    real_set = L.gsvc_set_wgrad_stream
+    real_backward = L.gsvc_generate_all_backward
     taken = []
 
-    def spy(stream):
-        if stream is not None:
-            taken.append(stream)
-        return real_set(stream)
-    monkeypatch.setattr(L, "gsvc_set_wgrad_stream", spy)
+    def spy(*args):
+        if args[-1] is not None:      # wgrad_stream, the last argument
+            taken.append(args[-1])
+        return real_backward(*args)
+    monkeypatch.setattr(L, "gsvc_generate_all_backward", spy)
     try:
         res = {}
         for off in (False, True):
