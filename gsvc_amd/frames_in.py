@@ -1,0 +1,256 @@
+"""Encoder input: 8-bit RGB / YUV video files to float frames on the GPU (host side of csrc/frames_in.hip), the mirror image of
+``frames_out``.
+
+A fit reads float32 ``[3, H, W]`` pictures; a video file holds 8 bits per sample.  ``io.FrameCubeDataset`` opens one PNG per frame
+with PIL and divides by 255 on the host; here ``open_video`` hands out the bytes of a ``.y4m`` / ``.yuv`` / ``.rgb`` file,
+``frames_from_u8`` converts up to 16 uploaded frames with one HIP launch, and ``VideoFileCube`` is the dataset a ``Trainer`` or
+``report.evaluate`` takes: the file's frames either converted once and kept as float (``resident="float"``) or kept in device memory
+as they are in the file and converted one frame per fetch (``resident="u8"``: 3.1 MB instead of 24.9 MB per 1080p 4:2:0 frame).
+
+The conversion (include/gsvc_hip.h, gsvc_frames_from_u8): ``rgb24`` is ``b / 255`` (bit-equal to ``io.load_image``); the YUV layouts
+invert the BT.709 / BT.601 matrix of ``frames_out`` for limited or full range codes and clamp to [0, 1]; 4:2:0 chroma is centre
+sited (Y4M ``C420jpeg``, what ``Y4MWriter`` writes) and upsampled on the codes, ``chroma="bilinear"`` (the default; weights 9/16,
+3/16, 3/16, 1/16) or ``"nearest"``.
+
+Importing this module needs neither a GPU nor the built library; ``frames_from_u8`` and ``VideoFileCube`` do (no CPU fallback).
+"""
+from __future__ import annotations
+
+import os
+import weakref
+
+import numpy as np
+
+from . import _lib
+from .frames_out import LAYOUTS, MATRICES, MAX_BATCH, RANGES, FrameFormat, frame_bytes, read_y4m
+
+CHROMAS = {"nearest": 0, "bilinear": 1}                      # the GSVC_FRAMES_CHROMA_* enums of include/gsvc_hip.h
+
+
+def _chroma_id(chroma: str) -> int:
+    if chroma not in CHROMAS:
+        raise ValueError(f"unknown chroma mode {chroma!r} (one of {', '.join(CHROMAS)})")
+    return CHROMAS[chroma]
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# device side
+# ----------------------------------------------------------------------------------------------------------------------------
+def frames_from_u8(frames_u8, H: int, W: int, fmt: FrameFormat = FrameFormat(), chroma: str = "bilinear", out=None):
+    """uint8 CUDA frames ``[n, >= frame_bytes]`` with contiguous rows (or one flat frame) -> float32 ``[n, 3, H, W]`` RGB on their
+    device, one launch per 16 frames on the current stream; nothing synchronises.  Bytes of a row past the frame are not read;
+    ``fmt.rounding`` is ignored.  ``out``: a float32 CUDA tensor ``[n, 3, H, W]`` whose images are contiguous (it is returned)."""
+    import ctypes as C
+
+    import torch
+    cid = _chroma_id(chroma)
+    if not isinstance(frames_u8, torch.Tensor):
+        raise ValueError(f"frames_from_u8: frames must be a uint8 tensor (got {type(frames_u8).__name__})")
+    if not frames_u8.is_cuda:
+        raise _lib.GsvcError("frames_from_u8 runs on the HIP kernels of csrc/frames_in.hip; CPU tensors are not supported")
+    H, W = int(H), int(W)
+    nbytes = frame_bytes(H, W, fmt)
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() not in (1, 2):
+        raise ValueError(f"frames_from_u8: frames must be uint8 [n, >= {nbytes}] or one flat frame (got {frames_u8.dtype} "
+                         f"{tuple(frames_u8.shape)})")
+    if frames_u8.dim() == 1:
+        frames_u8 = frames_u8.unsqueeze(0)
+    n = int(frames_u8.shape[0])
+    if n < 1 or frames_u8.shape[1] < nbytes or frames_u8.stride(1) != 1 or (n > 1 and frames_u8.stride(0) < nbytes):
+        raise ValueError(f"frames_from_u8: a {fmt.layout} frame of {H} x {W} has {nbytes} bytes; frames must be [n >= 1, >= {nbytes}] "
+                         f"with contiguous rows (got {tuple(frames_u8.shape)}, strides {tuple(frames_u8.stride())})")
+    dev = frames_u8.device
+    if out is None:
+        out = torch.empty((n, 3, H, W), dtype=torch.float32, device=dev)
+    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != (n, 3, H, W)
+          or not out[0].is_contiguous()):
+        raise ValueError(f"frames_from_u8: out must be float32 [{n}, 3, {H}, {W}] on {dev} with contiguous images")
+    L = _lib.lib()
+    stride = int(frames_u8.stride(0)) if n > 1 else max(int(frames_u8.stride(0)), nbytes)
+    base, obase, ostride = frames_u8.data_ptr(), out.data_ptr(), int(out.stride(0)) * 4
+    with torch.cuda.device(dev):
+        stream = _lib.current_stream(dev)
+        for i in range(0, n, MAX_BATCH):
+            m = min(MAX_BATCH, n - i)
+            ptrs = (C.c_void_p * m)(*[obase + (i + k) * ostride for k in range(m)])
+            _lib.check(L.gsvc_frames_from_u8(base + i * stride, stride, m, H, W, LAYOUTS[fmt.layout], MATRICES[fmt.matrix],
+                                             RANGES[fmt.range], cid, ptrs, stream), "gsvc_frames_from_u8")
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# files
+# ----------------------------------------------------------------------------------------------------------------------------
+def open_video(path, W: int | None = None, H: int | None = None, fmt: FrameFormat | None = None):
+    """``(header, frames)`` of a video file of 8-bit frames; frames = uint8 array ``[T, frame_bytes]``, header = {"W", "H", "frames",
+    "frame_bytes", "fmt": the FrameFormat of the payload, ...}.
+
+    ``.y4m``: read with ``frames_out.read_y4m`` (its header's fields are kept); the file's size, layout and ``XCOLORRANGE`` win over
+    ``W``, ``H`` and ``fmt``, which supplies the matrix (Y4M has no field for it) and the range of a file that does not state one.
+    ``.yuv`` / ``.rgb``: frame payloads back to back (``RawWriter``), memory-mapped; ``W`` and ``H`` are required and a file whose
+    size is not a whole number of frames is refused.  ``fmt`` None: what ``open_sink`` uses for the extension — yuv420p (BT.709,
+    limited range) for ``.y4m`` / ``.yuv``, rgb24 for ``.rgb``."""
+    path = str(path)
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".y4m":
+        hdr, frames = read_y4m(path)
+        base = fmt or FrameFormat("yuv420p")
+        if hdr["range"] not in (None, "limited", "full"):
+            raise ValueError(f"{path}: unknown XCOLORRANGE={hdr['range']}")
+        used = FrameFormat(hdr["layout"], base.matrix, hdr["range"] or base.range, base.rounding)
+        hdr = dict(hdr, frames=int(frames.shape[0]), fmt=used)
+        return hdr, frames
+    if ext in (".yuv", ".rgb"):
+        if W is None or H is None:
+            raise ValueError(f"{path}: a raw {ext} file does not say its size: open_video(path, W, H)")
+        used = fmt or FrameFormat("yuv420p" if ext == ".yuv" else "rgb24")
+        nbytes = frame_bytes(H, W, used)
+        size = os.path.getsize(path)
+        if size == 0 or size % nbytes:
+            raise ValueError(f"{path}: {size} bytes are not a whole number of {used.layout} frames of {int(W)} x {int(H)} "
+                             f"({nbytes} bytes each)")
+        frames = np.memmap(path, dtype=np.uint8, mode="r", shape=(size // nbytes, nbytes))
+        return {"W": int(W), "H": int(H), "layout": used.layout, "range": used.range, "frame_bytes": nbytes,
+                "frames": size // nbytes, "fmt": used}, frames
+    raise ValueError(f"{path}: open_video reads .y4m, .yuv and .rgb files")
+
+
+class VideoFileCube:
+    """The frames of a video file as the dataset of a fit, addressed like ``io.FrameCubeDataset`` and ``frame.SyntheticFrameCube``
+    (``dataset[i]`` is frame i with its picture kept transposed ``[3, W, H]`` and its camera at ``z = (i - T/2) / scale``;
+    ``get_optical_flow(i)`` the flow between frames i and i + 1, from ``optical_flow_dir`` through ``io.load_flow``).
+
+    The 8-bit frames are uploaded in chunks of up to 16 through one pinned staging buffer and converted on the device
+    (``frames_from_u8``); no float arithmetic on pixels runs on the host.
+      ``resident="float"``  every frame is converted once and kept as float32: fetching a frame launches nothing.
+      ``resident="u8"``     the video stays in device memory as it is in the file; ``get_z_frame`` converts the one frame it hands
+                            out with one launch on the current stream, into a tensor of its own that nothing writes again.  A reader on
+                            ANOTHER stream calls ``ready(i)`` first (``Trainer`` does, for its two frames, before the image losses):
+                            the current stream then waits for the conversions of frame i that are still held by a ``Frame``, and
+                            their tensors are recorded on it, so that the allocator does not hand their memory out under the reader.
+                            Two limits: a conversion is remembered through the tensor its ``Frame`` carries — a reader that keeps
+                            only another view of the picture must order itself —, and every fetch converts and allocates 12 H W
+                            bytes, also one whose picture is never read (a batched ``Trainer`` step fetches its pair twice: four
+                            conversions per step where two are read)."""
+
+    def __init__(self, path, optical_flow_dir=None, W: int | None = None, H: int | None = None, fmt: FrameFormat | None = None,
+                 chroma: str = "bilinear", device="cuda", resident: str = "float"):
+        import pathlib
+
+        import torch
+        if resident not in ("float", "u8"):
+            raise ValueError(f"VideoFileCube: resident must be 'float' or 'u8' (got {resident!r})")
+        _chroma_id(chroma)
+        self.path, self.chroma, self.resident = str(path), chroma, resident
+        self.header, frames = open_video(path, W, H, fmt)
+        self.fmt = self.header["fmt"]
+        self.height, self.width, self.len = int(self.header["H"]), int(self.header["W"]), int(frames.shape[0])
+        if self.len < 1:
+            raise ValueError(f"{self.path}: no frames")
+        self.scale = max(self.height, self.width, self.len) / 2
+        self.x_min = -self.width / 2 / self.scale
+        self.y_min = -self.height / 2 / self.scale
+        self.z_min = -self.len / 2 / self.scale
+        self.optical_flow_paths = sorted(pathlib.Path(optical_flow_dir).iterdir()) if optical_flow_dir is not None else []
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.GsvcError("VideoFileCube converts its frames with the HIP kernels of csrc/frames_in.hip; it needs a CUDA device")
+        self._views, self._fetched = {}, {}
+        self._upload(frames)
+        from .io import load_flow
+        self.prefetched_of = [load_flow(p).to(self.device) for p in self.optical_flow_paths]
+
+    def _upload(self, frames):
+        import torch
+        T, H, W, nbytes = self.len, self.height, self.width, int(self.header["frame_bytes"])
+        chunk = min(MAX_BATCH, T)
+        staging = torch.empty((chunk, nbytes), dtype=torch.uint8, pin_memory=True)
+        host = staging.numpy()
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            if self.resident == "u8":
+                self._u8, self._images = torch.empty((T, nbytes), dtype=torch.uint8, device=self.device), None
+                on_dev = None
+            else:
+                self._u8, self._images = None, torch.empty((T, 3, H, W), dtype=torch.float32, device=self.device)
+                on_dev = torch.empty((chunk, nbytes), dtype=torch.uint8, device=self.device)
+            for i in range(0, T, chunk):
+                m = min(chunk, T - i)
+                np.copyto(host[:m], frames[i:i + m])
+                dst = self._u8[i:i + m] if on_dev is None else on_dev[:m]
+                dst.copy_(staging[:m], non_blocking=True)
+                if on_dev is not None:
+                    frames_from_u8(dst, H, W, self.fmt, self.chroma, out=self._images[i:i + m])
+                stream.synchronize()          # the staging buffer is free again; after the last chunk: every stream may read the video
+
+    def __len__(self):
+        return self.len
+
+    @property
+    def len_z_frames(self):
+        return self.len
+
+    @property
+    def frame_num(self):
+        return self.len
+
+    @property
+    def frame_height(self):
+        return self.height
+
+    @property
+    def frame_width(self):
+        return self.width
+
+    def _picture(self, image_id):
+        if self._images is not None:
+            return self._images[image_id].permute(0, 2, 1)
+        import torch
+        img = frames_from_u8(self._u8[image_id:image_id + 1], self.height, self.width, self.fmt, self.chroma)[0].permute(0, 2, 1)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(self.device))
+        live = [(r, ev) for r, ev in self._fetched.get(image_id, ()) if r() is not None]
+        self._fetched[image_id] = live + [(weakref.ref(img), done)]
+        return img
+
+    def ready(self, image_id):
+        """Order the current stream behind the conversions of frame ``image_id`` whose pictures are still in use, and tell the
+        allocator that this stream reads them.  Nothing to do for ``resident="float"``: those pictures were complete before the
+        constructor returned."""
+        if self._images is not None:
+            return
+        import torch
+        cur = torch.cuda.current_stream(self.device)
+        live = []
+        for r, ev in self._fetched.get(image_id, ()):
+            img = r()
+            if img is not None:
+                cur.wait_event(ev)
+                img.record_stream(cur)
+                live.append((r, ev))
+        self._fetched[image_id] = live
+
+    def get_z_frame(self, image_id, load_image=True):
+        from .frame import Frame, make_view_matrix
+        image_id = int(image_id)
+        if not 0 <= image_id < self.len:
+            raise IndexError(f"frame {image_id} of {self.len}")
+        z = (image_id - self.len / 2) / self.scale
+        if image_id not in self._views:
+            self._views[image_id] = make_view_matrix(z=z, plane="xy")
+        vm, vms, cam = self._views[image_id]
+        img = self._picture(image_id) if load_image else None
+        return Frame(image_id=image_id, plane="xy", image=img, x_min=self.x_min, y_min=self.y_min, z=z, image_width=self.width,
+                     image_height=self.height, view_matrix=vm, view_matrix_s=vms, scale=self.scale, cam_pos=cam)
+
+    def get_dummy_frame(self, image_id):
+        return self.get_z_frame(image_id, load_image=False)
+
+    def __getitem__(self, idx):
+        return self.get_z_frame(idx)
+
+    def get_optical_flow(self, idx):
+        if not self.prefetched_of:
+            raise RuntimeError(f"{self.path}: a video file holds no optical flow: the fit needs optical_lambda = 0, or flow files "
+                               "(VideoFileCube(path, optical_flow_dir=...))")
+        return self.prefetched_of[idx]

@@ -904,6 +904,33 @@ int64_t gsvc_frames_u8_bytes(int32_t H, int32_t W, int32_t layout);
 int gsvc_frames_to_u8(const float *const *images_host, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t matrix, int32_t range,
                       int32_t rounding, uint8_t *out, int64_t out_stride, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * [INTERNAL] Encoder input: float images from 8-bit frames, the mirror image of gsvc_frames_to_u8 (replaces the per-file PIL load +
+ * ToTensor of reference frame_cube/frame.py:141-152; csrc/frames_in.hip).  One launch converts n (1 .. 16) 8-bit frames of H x W —
+ * frame k starts at in + k * in_stride, any alignment — into n float32 images [3, H, W] (RGB, separate allocations, each base 4-byte
+ * aligned).  Sample codes are b, y8, cb8, cr8 in 0 .. 255; every float operation below is one float32 operation.
+ *   layout      GSVC_FRAMES_RGB24, interleaved [H, W, 3]: c = b / 255, an IEEE float32 division (not a multiply by a reciprocal: 126 of
+ *               the 256 codes differ between the two) = torch.uint8 -> float32 -> div(255).
+ *               GSVC_FRAMES_YUV444P / _YUV420P, planar Y, U (Cb), V (Cr), the layouts of gsvc_frames_to_u8:
+ *                 R = Y + 2 (1 - Kr) Cr,  B = Y + 2 (1 - Kb) Cb,  G = Y - (2 Kr (1 - Kr) / Kg) Cr - (2 Kb (1 - Kb) / Kg) Cb,
+ *               each then clamped to [0, 1].  The four constants are formed in double on the host and rounded once to float; in the
+ *               kernel R = fma(r_cr, Cr, Y), B = fma(b_cb, Cb, Y), G = fma(-g_cb, Cb, fma(-g_cr, Cr, Y)).
+ *   matrix      GSVC_FRAMES_BT709 (Kr 0.2126, Kb 0.0722) or GSVC_FRAMES_BT601 (0.299, 0.114); Kg = 1 - Kr - Kb; ignored for RGB24
+ *   range       GSVC_FRAMES_LIMITED: Y = (y8 - 16) / 219, C = (c8 - 128) / 224.  GSVC_FRAMES_FULL: Y = y8 / 255, C = (c8 - 128) / 255
+ *               (divisions).  Ignored for RGB24.
+ *   chroma      4:2:0 only; the chroma samples are centre sited (Y4M C420jpeg) and are upsampled on the CODES, before the affine map
+ *               (exact in float32: every interpolated code is a multiple of 1/16 below 256).
+ *               GSVC_FRAMES_CHROMA_NEAREST: each chroma sample serves its 2x2 block.
+ *               GSVC_FRAMES_CHROMA_BILINEAR, per axis: luma column x = 2 j takes 0.25 c[j - 1] + 0.75 c[j], column x = 2 j + 1 takes
+ *               0.75 c[j] + 0.25 c[j + 1], indices clamped to [0, W / 2 - 1]; rows likewise, so the 2-D weights are 9/16, 3/16, 3/16,
+ *               1/16 (= bilinear interpolation at scale 2 with half-pixel centres, align_corners = False).
+ * images_host: host array of n device pointers (they travel in the kernel arguments: no upload).  in_stride >= the frame's bytes
+ * (gsvc_frames_u8_bytes); H and W even for 4:2:0.  Nothing synchronises; every element of the n images is written, nothing else.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { GSVC_FRAMES_CHROMA_NEAREST = 0, GSVC_FRAMES_CHROMA_BILINEAR = 1 };
+int gsvc_frames_from_u8(const uint8_t *in, int64_t in_stride, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t matrix,
+                        int32_t range, int32_t chroma, float *const *images_host, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

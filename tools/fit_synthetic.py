@@ -21,6 +21,8 @@ built on:
 
 usage: python tools/fit_synthetic.py [--steps 2000] [--height 1080 --width 1920 --frames 64 --anchors 100000] [--json out.json]
                                      [--write-decoded out.y4m]
+       python tools/fit_synthetic.py --video clip.y4m [--flow-dir flows/] [--video-resident u8] ...      (the same chain on a video file: its
+                                     frame count and size replace --frames / --height / --width; raw files: --video-size WxH)
 """
 import argparse
 import copy
@@ -53,6 +55,14 @@ def main(argv=None):
     ap.add_argument("--lpips-lin-weights", default=None)
     ap.add_argument("--write-decoded", default=None, metavar="PATH",
                     help="write the decoded 8-bit-MLP model's frames as 8-bit video: .y4m / .yuv (yuv420p), .rgb (rgb24), else a directory of PNGs")
+    ap.add_argument("--video", default=None, metavar="PATH",
+                    help="fit this 8-bit video file (.y4m, or raw .yuv / .rgb with --video-size) instead of the synthetic frames")
+    ap.add_argument("--video-size", default=None, metavar="WxH", help="frame size of a raw --video file")
+    ap.add_argument("--video-format", default=None, metavar="LAYOUT[,MATRIX[,RANGE]]",
+                    help="e.g. yuv420p,bt601,full (default: yuv420p,bt709,limited; rgb24 for .rgb; a .y4m file's own layout and range win)")
+    ap.add_argument("--flow-dir", default=None, metavar="DIR", help="optical-flow files of --video, one per frame pair (none: optical_lambda = 0)")
+    ap.add_argument("--video-resident", choices=("float", "u8"), default="float",
+                    help="keep the video on the device as float32 pictures, or as the file's bytes (converted one frame per fetch)")
     args = ap.parse_args(argv)
 
     from gsvc_amd.arguments import cfg_20240919
@@ -75,7 +85,17 @@ def main(argv=None):
     rank, world, _ = gdist.init_from_env(os.environ.get("GSVC_DIST_BACKEND") or None)
     H, W, T, N = args.height, args.width, args.frames, args.steps
     mp_, opt, pipe = cfg_20240919()
-    cube = SyntheticFrameCube(H, W, T, seed=1234, device=dev).materialize()
+    if args.video:
+        from gsvc_amd.frames_in import VideoFileCube
+        from gsvc_amd.frames_out import FrameFormat
+        vw, vh = (int(v) for v in args.video_size.lower().split("x")) if args.video_size else (None, None)
+        vfmt = FrameFormat(*args.video_format.split(",")) if args.video_format else None
+        cube = VideoFileCube(args.video, optical_flow_dir=args.flow_dir, W=vw, H=vh, fmt=vfmt, device=dev, resident=args.video_resident)
+        H, W, T = cube.height, cube.width, cube.len_z_frames          # the file says what is fitted
+        if args.flow_dir is None:
+            opt.optical_lambda = 0.0
+    else:
+        cube = SyntheticFrameCube(H, W, T, seed=1234, device=dev).materialize()
     mp_.threshold = args.slab_frames / 2.0 / cube.scale
     s = N / 40_000.0
     opt.iterations, opt.lmbda = N, args.lmbda
@@ -108,6 +128,9 @@ def main(argv=None):
                                                                     opt.entropy_constrained_train_total, opt.ste_entropy_constrained_train_total],
                       "densify": [opt.start_stat, opt.update_from, opt.update_interval, opt.update_until, opt.pause_densification]},
            "phases": []}
+    if args.video:
+        log["video"] = {"path": args.video, "frames": T, "W": W, "H": H, "layout": cube.fmt.layout, "matrix": cube.fmt.matrix,
+                        "range": cube.fmt.range, "chroma": cube.chroma, "resident": cube.resident, "optical_lambda": opt.optical_lambda}
     eval_ids = [int(round(i)) for i in np.linspace(0, T - 1, args.eval_frames)]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -232,7 +255,7 @@ def main(argv=None):
         if args.write_decoded:
             from gsvc_amd.frames_out import open_sink, write_video
             sink, fmt = open_sink(args.write_decoded, W, H)
-            log["decoded_video"] = dict(write_video([cube[i] for i in range(T)], dec_q, pipe, bg, sink, fmt=fmt), path=args.write_decoded,
+            log["decoded_video"] = dict(write_video([cube.get_dummy_frame(i) if args.video else cube[i] for i in range(T)], dec_q, pipe, bg, sink, fmt=fmt), path=args.write_decoded,
                                         layout=fmt.layout)
         log["total_bytes"] = int(total_bytes)
         log["bpp"] = 8.0 * total_bytes / (H * W * T)
