@@ -6,8 +6,9 @@
 // rule reproduced: the gradient passes only where the un-clamped likelihood is >= 2^-16.
 //
 // HBM-bound elementwise work: x, mean, scale are read once with 16-byte loads where the row length allows,
-// the per-row Q is a broadcast, bits are optionally written, and the (weighted) sum is reduced per wave and
-// added with one float atomic per workgroup.
+// the per-row Q is a broadcast, bits are optionally written, and the (weighted) sum is accumulated in double:
+// one partial per workgroup (a float pair) in the caller's scratch, added up in fixed order by a one-workgroup
+// second stage and rounded to float once — the same bits every run, whatever order the workgroups finish in.
 #include "common.h"
 
 namespace gsvc {
@@ -23,26 +24,30 @@ __device__ __forceinline__ float normal_cdf(float v, float mu, float inv_sigma)
     return 0.5f * (1.0f + erff((v - mu) * inv_sigma * INV_SQRT2));
 }
 
-__device__ __forceinline__ float block_sum_256(float v, float *smem)
+constexpr int RATE_FWD_BLOCKS = 2048;
+
+__device__ __forceinline__ double block_sum_256d(double v, double *smem)
 {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane == 0) smem[wave] = v;
     __syncthreads();
-    return smem[0] + smem[1] + smem[2] + smem[3];
+    return (smem[0] + smem[1]) + (smem[2] + smem[3]);
 }
 
+// SUM: the workgroup's (weighted) sum goes to part[2 * blockIdx.x] as a float pair (high part, remainder)
+template <bool SUM>
 __global__ void __launch_bounds__(256) k_rate_fwd(const float *__restrict__ x, const float *__restrict__ mean,
                                                   const float *__restrict__ scale, const float *__restrict__ Q,
                                                   float Q_scalar, const float *__restrict__ weight,
                                                   const float *__restrict__ x_lo, const float *__restrict__ x_hi,
                                                   int bounds_per_row, long long total, int c, float *__restrict__ bits,
-                                                  float *__restrict__ bits_sum)
+                                                  float *__restrict__ part)
 {
-    __shared__ float smem[4];
+    __shared__ double smem[4];
     float lo = (x_lo && !bounds_per_row) ? *x_lo : -INFINITY, hi = (x_hi && !bounds_per_row) ? *x_hi : INFINITY;
-    float acc = 0.f;
+    double acc = 0.0;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const long long row = i / c;
         const float q = Q ? Q[row] : Q_scalar;
@@ -54,12 +59,26 @@ __global__ void __launch_bounds__(256) k_rate_fwd(const float *__restrict__ x, c
         const float lik = fmaxf(upper - lower, LOW_BOUND);
         const float b = -log2f(lik);
         if (bits) bits[i] = b;
-        acc += weight ? b * weight[i] : b;
+        if (SUM) acc += weight ? (double)b * (double)weight[i] : (double)b;
     }
-    if (bits_sum) {
-        const float s = block_sum_256(acc, smem);
-        if (threadIdx.x == 0) atomicAdd(bits_sum, s);
+    if (SUM) {
+        const double s = block_sum_256d(acc, smem);
+        if (threadIdx.x == 0) {
+            const float h = (float)s;
+            part[2 * blockIdx.x] = h;
+            part[2 * blockIdx.x + 1] = (float)(s - (double)h);
+        }
     }
+}
+
+// second stage, one workgroup: the partials in fixed order, in double, ADDED to *bits_sum with one float rounding
+__global__ void __launch_bounds__(256) k_rate_fwd_sum(const float *__restrict__ part, int blocks, float *__restrict__ bits_sum)
+{
+    __shared__ double smem[4];
+    double acc = 0.0;
+    for (int b = threadIdx.x; b < blocks; b += 256) acc += (double)part[2 * b] + (double)part[2 * b + 1];
+    const double s = block_sum_256d(acc, smem);
+    if (threadIdx.x == 0) *bits_sum = (float)((double)*bits_sum + s);
 }
 
 // one workgroup per group of rows so the per-row dQ reduces on chip: each wave owns whole rows
@@ -484,18 +503,28 @@ __global__ void __launch_bounds__(256) k_training_statis(const long long *__rest
 
 using namespace gsvc;
 
+extern "C" int64_t gsvc_rate_forward_scratch_floats(void) { return 2 * RATE_FWD_BLOCKS; }
+
 extern "C" int gsvc_rate_forward(const float *x, const float *mean, const float *scale, const float *Q, float Q_scalar,
                                  const float *weight, const float *x_lo, const float *x_hi, int32_t bounds_per_row,
-                                 int64_t n, int64_t c, float *bits, float *bits_sum, void *stream)
+                                 int64_t n, int64_t c, float *bits, float *bits_sum, float *scratch, void *stream)
 {
     GSVC_REQUIRE(n >= 0 && c >= 0 && c < (1 << 30), "rate_forward: bad shape");
     if (n == 0 || c == 0) return GSVC_OK;
     GSVC_REQUIRE(x && mean && scale, "rate_forward: NULL input");
+    GSVC_REQUIRE(!bits_sum || scratch, "rate_forward: bits_sum needs scratch (gsvc_rate_forward_scratch_floats)");
     const long long total = (long long)n * c;
     long long blocks = (total + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    { ProfScope _prof("k_rate_fwd", (hipStream_t)stream); hipLaunchKernelGGL(k_rate_fwd, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, mean, scale, Q, Q_scalar,
-                       weight, x_lo, x_hi, (int)bounds_per_row, total, (int)c, bits, bits_sum); }
+    if (blocks > RATE_FWD_BLOCKS) blocks = RATE_FWD_BLOCKS;
+    { ProfScope _prof("k_rate_fwd", (hipStream_t)stream);
+      if (bits_sum) {
+          hipLaunchKernelGGL(k_rate_fwd<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, mean, scale, Q, Q_scalar,
+                             weight, x_lo, x_hi, (int)bounds_per_row, total, (int)c, bits, scratch);
+          hipLaunchKernelGGL(k_rate_fwd_sum, dim3(1), dim3(256), 0, (hipStream_t)stream, scratch, (int)blocks, bits_sum);
+      } else {
+          hipLaunchKernelGGL(k_rate_fwd<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, x, mean, scale, Q, Q_scalar,
+                             weight, x_lo, x_hi, (int)bounds_per_row, total, (int)c, bits, nullptr);
+      } }
     return check_launch("rate_forward");
 }
 

@@ -48,7 +48,7 @@ class _GaussianBits(torch.autograd.Function):
         bits = torch.empty_like(x)
         q = Q_rows.contiguous() if Q_rows is not None else None
         _lib.check(_lib.lib().gsvc_rate_forward(_lib.ptr(x), _lib.ptr(mean), _lib.ptr(scale), _lib.ptr(q), float(Q_scalar),
-                                                None, _lib.ptr(x_lo), _lib.ptr(x_hi), int(per_row), n, c, _lib.ptr(bits), None,
+                                                None, _lib.ptr(x_lo), _lib.ptr(x_hi), int(per_row), n, c, _lib.ptr(bits), None, None,
                                                 _lib.current_stream(x.device)), "gsvc_rate_forward")
         ctx.save_for_backward(x, mean, scale, q, x_lo, x_hi)
         ctx.Q_scalar = float(Q_scalar)

@@ -310,10 +310,12 @@ int gsvc_grid_forward_packed(const float *inputs, const uint8_t *table_bits, con
  * NULL disables; device scalars, or one pair per row [n] when bounds_per_row != 0 — used when several renders
  * are batched into one call).  x, mean, scale: [n,c];  Q: [n] (per row) or NULL with Q_scalar.
  * row_weight: [n,c] multiplier folded into the sum (the offsets mask) or NULL.
- * Outputs: bits[n,c] (may be NULL) and bits_sum[1] (double precision accumulate, float result, ADDED to). */
+ * Outputs: bits[n,c] (may be NULL) and bits_sum[1] (may be NULL; double precision accumulate in a fixed order, float result,
+ * ADDED to what it held).  scratch: gsvc_rate_forward_scratch_floats() floats, needed (and written) only with bits_sum. */
+int64_t gsvc_rate_forward_scratch_floats(void);
 int gsvc_rate_forward(const float *x, const float *mean, const float *scale, const float *Q, float Q_scalar,
                       const float *weight, const float *x_lo, const float *x_hi, int32_t bounds_per_row, int64_t n,
-                      int64_t c, float *bits, float *bits_sum, void *stream);
+                      int64_t c, float *bits, float *bits_sum, float *scratch, void *stream);
 
 /* d(sum(weight*bits)*gscale)/d{x, mean, scale, Q[n], weight}; any output pointer may be NULL.
  * Low_bound rule: gradient passes only where the likelihood >= 2^-16 (reference entropy_models.py:166-175,
