@@ -16,7 +16,9 @@
 //     kernels — and the backward needs them anyway.
 //   * the forward leaves behind exactly what the backward and the weight gradients read (pre-activations, activations); the
 //     backward chain writes the gradient operand of every layer's dW = G^T X, which the row-split kernels of linear_wgrad.hip
-//     then form (one batched slot reduce per network).
+//     then form (one batched slot reduce per network).  Where the two views of a frame share the FiLM rows, the generators'
+//     backward takes the two chain rows behind a FiLM row together and writes d gamma / d beta once, summed, per FiLM row:
+//     the per-view rows existed only to be added up (trunk_bwd_paired_body).
 //   * the last k-group of a layer issues only the MFMA steps that carry a valid k (K = 66, 50: 2 of 4).
 //
 // Instantiated for the production widths (feat 50, condition 66, hidden 100, K = 10 offsets: outputs 10 / 30 / 70 / 30);
@@ -146,7 +148,8 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t whole_rsrc(const float *base, 
     return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(((uintptr_t)hi << 32) | lo), 0, bytes, 0x00020000);
 }
 
-// Tile-layout LOADS of a row-major [rows][N] matrix where lane (fr, kq) reads row `row` (its own: -1 = none, zeros)
+// Tile-layout access to a row-major [rows][N] matrix where lane (fr, kq) reads / writes row `row` (its own: -1 = none: loads give
+// zeros, stores are dropped; so does a row past `rows`, by the descriptor's range check)
 template <int N>
 struct RowTiles {
     __amdgpu_buffer_rsrc_t r;
@@ -164,6 +167,11 @@ struct RowTiles {
         float v[4];
         ws_load4(r, ok ? off + 64 * t : BUF_OOB, ok ? c00 + 16 * t : N, N, cl_sv(N), v);
         return (v4f){v[0], v[1], v[2], v[3]};
+    }
+    __device__ __forceinline__ void store(int t, v4f x) const
+    {
+        const float v[4] = {x[0], x[1], x[2], x[3]};
+        ws_store4(r, ok ? off + 64 * t : BUF_OOB, ok ? c00 + 16 * t : N, N, cl_sv(N), v);
     }
 };
 
@@ -365,15 +373,13 @@ __device__ __forceinline__ void film_fwd_body(int blk, int nblk, const float *__
 }
 
 // backward through the second layers and the ReLUs: gcg = (ggamma Wg1) * [cg > 0], gcb likewise (the first layers' dW
-// operands; the condition itself — frame time and z embedding of detached anchors — needs no gradient)
+// operands; the condition itself — frame time and z embedding of detached anchors — needs no gradient).  One row per FiLM row:
+// with shared FiLM rows ggamma / gbeta arrive as the two views' sums (trunk_bwd_paired_body)
 template <int COND, int HID, int CHAIN_THREADS>
 __device__ __forceinline__ void film_bwd_body(int blk, int nblk, const float *__restrict__ ggamma, const float *__restrict__ gbeta,
                                                                  const float *__restrict__ cg, const float *__restrict__ cb,
                                                                  const float *__restrict__ Wg1, const float *__restrict__ Wb1,
-                                                                 float *__restrict__ gcg, float *__restrict__ gcb, long long M,
-                                                                 const int *__restrict__ src_a, const int *__restrict__ src_b,
-                                                                 long long src_rows, float *__restrict__ ggamma_sum,
-                                                                 float *__restrict__ gbeta_sum)
+                                                                 float *__restrict__ gcg, float *__restrict__ gcb, long long M)
 {
     extern __shared__ float lds[];
     constexpr int LD = cl_ld(HID), NT = cl_kg(COND), IMG = NT * 16 * LD;
@@ -385,30 +391,11 @@ __device__ __forceinline__ void film_bwd_body(int blk, int nblk, const float *__
     __syncthreads();
     long long rb, RB, stride;
     row_blocks<CHAIN_THREADS / 64>(M, L, blk, nblk, rb, RB, stride);
-    // src_a / src_b (shared FiLM rows): this kernel's row q is a (frame, anchor); ggamma / gbeta hold one row per (view, anchor) —
-    // the frame's two opposite views — and the row's gradient is the sum of the two (either may be absent: -1).  The sums are
-    // written out: they are the G operands of the second layers' weight gradients.
-    v4f g[2][cl_kg(HID)], t2[2][cl_kg(HID)];
-    int ra = -1, rb2 = -1, ra_n = -1, rb_n = -1;
-    // the (summed) gradients of a block are requested one block ahead — network by network, as soon as this block's have been
-    // summed into the product's operand —, the map entries two blocks ahead
-    auto fetch = [&](int net, long long b, int a_row, int b_row) {
-        const float *src = net ? gbeta : ggamma;
-        if (src_a) {
-            load_frags_row<HID>(g[net], src, src_rows, a_row, L);
-            load_frags_row<HID>(t2[net], src, src_rows, b_row, L);
-        } else {
-            load_frags<HID>(g[net], src, b, RB, M, L);
-        }
-    };
-    if (src_a) {
-        ra = map_row(src_a, rb, RB, M, L);
-        rb2 = map_row(src_b, rb, RB, M, L);
-        ra_n = map_row(src_a, rb + stride, RB, M, L);
-        rb_n = map_row(src_b, rb + stride, RB, M, L);
-    }
-    fetch(0, rb, ra, rb2);
-    fetch(1, rb, ra, rb2);
+    // the gradients of a block are requested one block ahead — network by network, as soon as this block's have been handed to the
+    // product as its operand
+    v4f g[2][cl_kg(HID)];
+    load_frags<HID>(g[0], ggamma, rb, RB, M, L);
+    load_frags<HID>(g[1], gbeta, rb, RB, M, L);
     for (; rb < RB; rb += stride) {
         v4f m[2][NT];      // the ReLU outputs (masks) of this block
         {
@@ -421,21 +408,12 @@ __device__ __forceinline__ void film_bwd_body(int blk, int nblk, const float *__
         for (int net = 0; net < 2; net++) {
             v4f cur[cl_kg(HID)];
 #pragma unroll
-            for (int i = 0; i < cl_kg(HID); i++) cur[i] = src_a ? g[net][i] + t2[net][i] : g[net][i];
-            fetch(net, rb + stride, ra_n, rb_n);
+            for (int i = 0; i < cl_kg(HID); i++) cur[i] = g[net][i];
+            load_frags<HID>(g[net], net ? gbeta : ggamma, rb + stride, RB, M, L);
             __builtin_amdgcn_sched_barrier(0);
-            if (src_a) {
-                const Tiles<HID> ts(net ? gbeta_sum : ggamma_sum, rb, RB, M, L);
-#pragma unroll
-                for (int t = 0; t < cl_kg(HID); t++) ts.store(t, cur[t]);
-            }
             v4f acc[NT];
             init_zero(acc);
             chain_mm<HID, NT, LD>(acc, cur, lds + net * IMG, L);
-            if (net == 1 && src_a) {
-                ra_n = map_row(src_a, rb + 2 * stride, RB, M, L);
-                rb_n = map_row(src_b, rb + 2 * stride, RB, M, L);
-            }
             const Tiles<COND> to(net ? gcb : gcg, rb, RB, M, L);
 #pragma unroll
             for (int t = 0; t < NT; t++) {
@@ -567,8 +545,7 @@ __device__ __forceinline__ void trunk_bwd_body(int blk, int nblk, const float *_
                                                              const float *__restrict__ feat, TrunkW w, float *__restrict__ go,
                                                              float *__restrict__ gbeta, float *__restrict__ ggamma,
                                                              float *__restrict__ gh, float *__restrict__ gz1,
-                                                             float *__restrict__ gfeat, int accumulate, long long M,
-                                                             const int *__restrict__ film_row, long long film_rows)
+                                                             float *__restrict__ gfeat, int accumulate, long long M)
 {
     extern __shared__ float lds[];
     using S = TrunkBwdLds<FEAT, HID, OUT>;
@@ -593,7 +570,6 @@ __device__ __forceinline__ void trunk_bwd_body(int blk, int nblk, const float *_
 #pragma unroll
         for (int t = 0; t < NTO; t++) { g0[t] = tg.load(t); yv[t] = ty.load(t); }
     }
-    int fr_next = film_row ? map_row(film_row, rb, RB, M, L) : -1;
     for (; rb < RB; rb += stride) {
         // everything this block reads later (h, gamma, z1, the running feature gradient) is requested up front and lands while
         // the products run; the next block's (gy, y) are requested once this block's have been consumed
@@ -602,17 +578,9 @@ __device__ __forceinline__ void trunk_bwd_body(int blk, int nblk, const float *_
             const Tiles<HID> th(h, rb, RB, M, L);
 #pragma unroll
             for (int t = 0; t < S::NTH; t++) hh[t] = th.load(t);
-            if (film_row) {
-                const int fr_ = fr_next;
-                fr_next = map_row(film_row, rb + stride, RB, M, L);
-                const RowTiles<HID> tg(gamma, film_rows, fr_, L);
+            const Tiles<HID> tg(gamma, rb, RB, M, L);
 #pragma unroll
-                for (int t = 0; t < S::NTH; t++) gg[t] = tg.load(t);
-            } else {
-                const Tiles<HID> tg(gamma, rb, RB, M, L);
-#pragma unroll
-                for (int t = 0; t < S::NTH; t++) gg[t] = tg.load(t);
-            }
+            for (int t = 0; t < S::NTH; t++) gg[t] = tg.load(t);
             const Tiles<FEAT> tf(gfeat, accumulate ? rb : RB, RB, M, L);      // empty descriptor (zeros) when not accumulating
 #pragma unroll
             for (int t = 0; t < S::NTF; t++) pf[t] = tf.load(t);
@@ -679,6 +647,158 @@ __device__ __forceinline__ void trunk_bwd_body(int blk, int nblk, const float *_
     }
 }
 
+// The same backward with shared FiLM rows (gsvc_film_rows): a wave walks 16-row blocks of FiLM rows and takes the two chain rows
+// behind each one — src_a[q], then src_b[q], -1 = none: operands read as zeros, stores are dropped — through the chain as two
+// gathered sub-blocks.  Every per-row tensor is addressed by the lane's chain row; gamma is read once per FiLM block, and what
+// leaves for the FiLM networks is the SUM of the two views' d gamma / d beta, one row per FiLM row (the first sub-block's two tiles
+// wait in registers for the second's): per-view rows of them never exist.  Every output of a chain row is what trunk_bwd_body
+// gives it — the same operands in the same order; only the order in which rows are visited differs — and the sums are a_side +
+// b_side with an absent side +0.0, as the FiLM backward used to form them from the per-view rows.  A sub-block carries its holes
+// through the MFMAs (M / (2 Mf) of the products are of real rows).  Needs every chain row named exactly once by src_a / src_b.
+template <int FEAT, int HID, int OUT, int CHAIN_THREADS>
+__device__ __forceinline__ void trunk_bwd_paired_body(int blk, int nblk, const float *__restrict__ gy, const float *__restrict__ y, int act,
+                                                                    const float *__restrict__ h, const float *__restrict__ gamma,
+                                                                    const float *__restrict__ feat, TrunkW w, float *__restrict__ go,
+                                                                    float *__restrict__ gbeta_sum, float *__restrict__ ggamma_sum,
+                                                                    float *__restrict__ gh, float *__restrict__ gz1,
+                                                                    float *__restrict__ gfeat, int accumulate, long long M,
+                                                                    const int *__restrict__ src_a, const int *__restrict__ src_b,
+                                                                    long long film_rows)
+{
+    extern __shared__ float lds[];
+    using S = TrunkBwdLds<FEAT, HID, OUT>;
+    const Lane L;
+    zero_lds(lds, S::FLOATS, L.tid, CHAIN_THREADS);
+    __syncthreads();
+    stage_block<true>(w.W3, HID, OUT, 0, HID, lds + S::o_w3, S::LD3, 0, L.tid, CHAIN_THREADS);
+    stage_block<true>(w.W2, HID, HID, 0, HID, lds + S::o_w2, S::LDH, 0, L.tid, CHAIN_THREADS);
+    stage_block<true>(w.W1, FEAT, HID, 0, FEAT, lds + S::o_w1, S::LDH, 0, L.tid, CHAIN_THREADS);
+    stage_block<false>(w.W1, FEAT, HID, 0, FEAT, lds + S::o_w1f, S::LD1, 0, L.tid, CHAIN_THREADS);
+    float *sb1 = lds + S::o_b1;
+    stage_bias(w.b1, HID, sb1, S::NTH * 16, L.tid, CHAIN_THREADS);
+    __syncthreads();
+    long long qb, QB, stride;
+    row_blocks<CHAIN_THREADS / 64>(film_rows, L, blk, nblk, qb, QB, stride);
+    constexpr int NTO = cl_kg(OUT);
+    // the lane's chain row of a FiLM block's side (a row outside [0, M) counts as none)
+    auto side_row = [&](const int *__restrict__ map, long long b) {
+        const int r = map_row(map, b, QB, film_rows, L);
+        return (unsigned)r < (unsigned)M ? r : -1;
+    };
+    // sub-blocks in the order they are visited: (qb, a), (qb, b), (qb + stride, a), ...; row = this one's, row_n = the next one's,
+    // ra_n / rb_n = the next FiLM block's map entries (they travel one FiLM block ahead)
+    int row = side_row(src_a, qb), row_n = side_row(src_b, qb);
+    int ra_n = side_row(src_a, qb + stride), rb_n = side_row(src_b, qb + stride);
+    v4f f[cl_kg(FEAT)];
+    load_frags_row<FEAT>(f, feat, M, row, L);
+    v4f g0[NTO], yv[NTO];
+    {
+        const RowTiles<OUT> tg(gy, M, row, L), ty(y, M, row, L);
+#pragma unroll
+        for (int t = 0; t < NTO; t++) { g0[t] = tg.load(t); yv[t] = ty.load(t); }
+    }
+    v4f keep_b[S::NTH], keep_g[S::NTH];      // the a side's d beta / d gamma of this FiLM block
+    init_zero(keep_b);
+    init_zero(keep_g);
+    for (; qb < QB; qb += stride) {
+        v4f gg[S::NTH];      // gamma of the FiLM block: one read serves both sides
+        {
+            const Tiles<HID> tg(gamma, qb, QB, film_rows, L);
+#pragma unroll
+            for (int t = 0; t < S::NTH; t++) gg[t] = tg.load(t);
+        }
+#pragma unroll 1
+        for (int side = 0; side < 2; side++) {
+            // h of this sub-block is requested up front and lands while the first product runs.  The kept tiles cost 56 registers:
+            // the running feature gradient, the next feature rows and the next sub-block's (gy, y) are requested where registers
+            // are free for them — (gy, y) only before the last product (requested before the second, the kernel spilled)
+            v4f hh[S::NTH];
+            {
+                const RowTiles<HID> th(h, M, row, L);
+#pragma unroll
+                for (int t = 0; t < S::NTH; t++) hh[t] = th.load(t);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            v4f go_[NTO];
+            {
+                const RowTiles<OUT> to(go, M, row, L);
+#pragma unroll
+                for (int t = 0; t < NTO; t++) {
+                    go_[t] = g0[t];
+                    if (act != CH_ACT_NONE) {
+#pragma unroll
+                        for (int i = 0; i < 4; i++)
+                            go_[t][i] = act == CH_ACT_TANH ? g0[t][i] * (1.0f - yv[t][i] * yv[t][i]) : g0[t][i] * ((1.0f - yv[t][i]) * yv[t][i]);
+                    }
+                    to.store(t, go_[t]);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            v4f gx[S::NTH];
+            init_zero(gx);
+            chain_mm<OUT, S::NTH, S::LD3>(gx, go_, lds + S::o_w3, L);
+            {
+#pragma clang fp contract(off)      // d gamma is a rounded product before it meets the other side's: the bits of the per-view rows
+                // the sums leave with the b side (an empty descriptor drops the a side's stores)
+                const Tiles<HID> ob(gbeta_sum, side ? qb : QB, QB, film_rows, L), og(ggamma_sum, side ? qb : QB, QB, film_rows, L);
+                const RowTiles<HID> oh(gh, M, row, L);
+#pragma unroll
+                for (int t = 0; t < S::NTH; t++) {
+                    v4f dg;
+#pragma unroll
+                    for (int i = 0; i < 4; i++) dg[i] = gx[t][i] * hh[t][i];
+                    ob.store(t, keep_b[t] + gx[t]);
+                    og.store(t, keep_g[t] + dg);
+                    keep_b[t] = gx[t];
+                    keep_g[t] = dg;
+#pragma unroll
+                    for (int i = 0; i < 4; i++) gx[t][i] = gx[t][i] * gg[t][i];
+                    oh.store(t, gx[t]);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            v4f ga[S::NTH];
+            init_zero(ga);
+            chain_mm<HID, S::NTH, S::LDH>(ga, gx, lds + S::o_w2, L);
+            v4f pf[S::NTF];
+            {
+                const RowTiles<FEAT> tf(gfeat, M, accumulate ? row : -1, L);      // zeros when not accumulating
+#pragma unroll
+                for (int t = 0; t < S::NTF; t++) pf[t] = tf.load(t);
+            }
+            // z1 of this sub-block, as the forward formed it; the next sub-block's feature rows are requested behind it
+            v4f zz[S::NTH];
+            init_bias(zz, sb1, L);
+            chain_mm<FEAT, S::NTH, S::LD1>(zz, f, lds + S::o_w1f, L);
+            load_frags_row<FEAT>(f, feat, M, row_n, L);
+            {
+                const RowTiles<HID> oz(gz1, M, row, L);
+#pragma unroll
+                for (int t = 0; t < S::NTH; t++) {
+                    const v4f d = v_gelu_grad(zz[t]);
+#pragma unroll
+                    for (int i = 0; i < 4; i++) ga[t][i] *= d[i];
+                    oz.store(t, ga[t]);
+                }
+            }
+            {
+                const RowTiles<OUT> tg(gy, M, row_n, L), ty(y, M, row_n, L);
+#pragma unroll
+                for (int t = 0; t < NTO; t++) { g0[t] = tg.load(t); yv[t] = ty.load(t); }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            chain_mm<HID, S::NTF, S::LDH>(pf, ga, lds + S::o_w1, L);      // on top of the running sum (or zeros)
+            const RowTiles<FEAT> of(gfeat, M, row, L);
+#pragma unroll
+            for (int t = 0; t < S::NTF; t++) of.store(t, pf[t]);
+            row = row_n;
+            row_n = side ? rb_n : ra_n;
+        }
+        ra_n = side_row(src_a, qb + 2 * stride);
+        rb_n = side_row(src_b, qb + 2 * stride);
+    }
+}
+
 // ---- one launch for up to MAX_NETS generators (workgroup b serves network b % n) ----------------------------------------------
 struct FilmFwdBatch {
     int n;
@@ -697,9 +817,6 @@ struct FilmBwdBatch {
     int n;
     const float *ggamma[MAX_NETS], *gbeta[MAX_NETS], *cg[MAX_NETS], *cb[MAX_NETS], *Wg1[MAX_NETS], *Wb1[MAX_NETS];
     float *gcg[MAX_NETS], *gcb[MAX_NETS];
-    const int *src_a, *src_b;      // shared FiLM rows: the two (view, anchor) rows behind every (frame, anchor) row; NULL = one to one
-    long long src_rows;
-    float *ggamma_sum[MAX_NETS], *gbeta_sum[MAX_NETS];
 };
 template <int COND, int HID, int CHAIN_THREADS>
 __global__ void __launch_bounds__(CHAIN_THREADS) k_film_nets_bwd(FilmBwdBatch b, long long M)
@@ -707,8 +824,7 @@ __global__ void __launch_bounds__(CHAIN_THREADS) k_film_nets_bwd(FilmBwdBatch b,
     const NetOfBlock nb(b.n);
     film_bwd_body<COND, HID, CHAIN_THREADS>(nb.blk, nb.nblk, pick(b.ggamma, nb.net), pick(b.gbeta, nb.net), pick(b.cg, nb.net),
                                             pick(b.cb, nb.net), pick(b.Wg1, nb.net), pick(b.Wb1, nb.net), pick(b.gcg, nb.net),
-                                            pick(b.gcb, nb.net), M, b.src_a, b.src_b, b.src_rows, pick(b.ggamma_sum, nb.net),
-                                            pick(b.gbeta_sum, nb.net));
+                                            pick(b.gcb, nb.net), M);
 }
 
 struct TrunkFwdBatch {
@@ -741,8 +857,9 @@ struct TrunkBwdBatch {
     TrunkW w[MAX_NETS];
     const float *gy[MAX_NETS], *y[MAX_NETS], *h[MAX_NETS], *gamma[MAX_NETS];
     const float *feat;             // the generators' shared input: z1 is formed from it again
+    // gbeta / ggamma: one row per FiLM row — per chain row without shared FiLM rows, the two views' sums with them
     float *go[MAX_NETS], *gbeta[MAX_NETS], *ggamma[MAX_NETS], *gh[MAX_NETS], *gz1[MAX_NETS], *gfeat[MAX_NETS];
-    const int *film_row;
+    const int *src_a, *src_b;      // shared FiLM rows: the two chain rows behind every FiLM row; NULL = one to one
     long long film_rows;
 };
 template <int FEAT, int HID, int CHAIN_THREADS>
@@ -752,7 +869,24 @@ __global__ void __launch_bounds__(CHAIN_THREADS) k_trunk_bwd(TrunkBwdBatch b, lo
     const int i = nb.net;
 #define GSVC_TRUNK_BWD(OUT) trunk_bwd_body<FEAT, HID, OUT, CHAIN_THREADS>(nb.blk, nb.nblk, pick(b.gy, i), pick(b.y, i), pick(b.act, i), pick(b.h, i), \
         pick(b.gamma, i), b.feat, pick(b.w, i), pick(b.go, i), pick(b.gbeta, i), pick(b.ggamma, i), pick(b.gh, i), pick(b.gz1, i), \
-        pick(b.gfeat, i), pick(b.accumulate, i), M, b.film_row, b.film_rows)
+        pick(b.gfeat, i), pick(b.accumulate, i), M)
+    switch (pick(b.out, i)) {
+        case 10: GSVC_TRUNK_BWD(10); break;
+        case 30: GSVC_TRUNK_BWD(30); break;
+        default: GSVC_TRUNK_BWD(70); break;
+    }
+#undef GSVC_TRUNK_BWD
+}
+
+// shared FiLM rows: a kernel of its own (both bodies in one kernel made the compiler spill either)
+template <int FEAT, int HID, int CHAIN_THREADS>
+__global__ void __launch_bounds__(CHAIN_THREADS) k_trunk_bwd_paired(TrunkBwdBatch b, long long M)
+{
+    const NetOfBlock nb(b.n);
+    const int i = nb.net;
+#define GSVC_TRUNK_BWD(OUT) trunk_bwd_paired_body<FEAT, HID, OUT, CHAIN_THREADS>(nb.blk, nb.nblk, pick(b.gy, i), pick(b.y, i), pick(b.act, i), pick(b.h, i), \
+        pick(b.gamma, i), b.feat, pick(b.w, i), pick(b.go, i), pick(b.gbeta, i), pick(b.ggamma, i), pick(b.gh, i), pick(b.gz1, i), \
+        pick(b.gfeat, i), pick(b.accumulate, i), M, b.src_a, b.src_b, b.film_rows)
     switch (pick(b.out, i)) {
         case 10: GSVC_TRUNK_BWD(10); break;
         case 30: GSVC_TRUNK_BWD(30); break;
@@ -1202,17 +1336,15 @@ struct GenSaved {
 };
 constexpr long long GEN_SAVED_PER_ROW = 3 * HID, GEN_SAVED_PER_FILM_ROW = 2 * COND + 2 * HID;
 
-// backward scratch of a generator: go [OUT], gbeta, ggamma, gh, gz1 [HID] per chain row; gcg, gcb [COND] and (shared FiLM rows)
-// the two views' summed gbeta / ggamma [HID] per FiLM row; then the wgrad partial sums
+// backward scratch of a generator: go [OUT], gh, gz1 [HID] per chain row; gbeta, ggamma [HID] and gcg, gcb [COND] per FiLM row (with
+// shared FiLM rows gbeta / ggamma are the two views' sums: per-view rows of them do not exist); then the wgrad partial sums
 struct GenScratch {
-    float *go, *gbeta, *ggamma, *gh, *gz1, *gcg, *gcb, *gbeta_sum, *ggamma_sum, *wg;
-    GenScratch(float *base, long long M, long long Mf, int out, bool shared)
+    float *go, *gh, *gz1, *gbeta, *ggamma, *gcg, *gcb, *wg;
+    GenScratch(float *base, long long M, long long Mf, int out)
     {
         float *cur = base;
-        go = take(cur, M * out); gbeta = take(cur, M * HID); ggamma = take(cur, M * HID); gh = take(cur, M * HID);
-        gz1 = take(cur, M * HID); gcg = take(cur, Mf * COND); gcb = take(cur, Mf * COND);
-        gbeta_sum = shared ? take(cur, Mf * HID) : gbeta;
-        ggamma_sum = shared ? take(cur, Mf * HID) : ggamma;
+        go = take(cur, M * out); gh = take(cur, M * HID); gz1 = take(cur, M * HID);
+        gbeta = take(cur, Mf * HID); ggamma = take(cur, Mf * HID); gcg = take(cur, Mf * COND); gcb = take(cur, Mf * COND);
         wg = cur;
     }
 };
@@ -1325,9 +1457,8 @@ int generators_backward(const gsvc_generator_net *nets, int n, const float *feat
     FilmBwdBatch fb;
     tb.n = fb.n = n;
     tb.feat = feat;
-    tb.film_row = fr.row_of;
+    tb.src_a = fr.src_a; tb.src_b = fr.src_b;
     tb.film_rows = fr.rows;
-    fb.src_a = fr.src_a; fb.src_b = fr.src_b; fb.src_rows = M;
     float *sbase[MAX_NETS];
     {
         float *cur = scratch;
@@ -1340,13 +1471,13 @@ int generators_backward(const gsvc_generator_net *nets, int n, const float *feat
         const int j = i < n ? i : 0;
         const gsvc_generator_net &g = nets[j];
         const GenSaved sv(const_cast<float *>(saved[j]), M, fr.rows);
-        const GenScratch sc(sbase[j], M, fr.rows, g.out_dim, fr.shared);
+        const GenScratch sc(sbase[j], M, fr.rows, g.out_dim);
         tb.out[i] = g.out_dim; tb.act[i] = g.out_act; tb.accumulate[i] = 0;
         tb.w[i] = TrunkW{g.W1, g.b1, g.W2, g.b2, g.W3, g.b3};
         tb.gy[i] = gy[j]; tb.y[i] = y[j]; tb.h[i] = sv.h; tb.gamma[i] = sv.gamma;
         tb.go[i] = sc.go; tb.gbeta[i] = sc.gbeta; tb.ggamma[i] = sc.ggamma; tb.gh[i] = sc.gh; tb.gz1[i] = sc.gz1; tb.gfeat[i] = gfeat[j];
         fb.ggamma[i] = sc.ggamma; fb.gbeta[i] = sc.gbeta; fb.cg[i] = sv.cg; fb.cb[i] = sv.cb; fb.Wg1[i] = g.Wg1; fb.Wb1[i] = g.Wb1;
-        fb.gcg[i] = sc.gcg; fb.gcb[i] = sc.gcb; fb.ggamma_sum[i] = sc.ggamma_sum; fb.gbeta_sum[i] = sc.gbeta_sum;
+        fb.gcg[i] = sc.gcg; fb.gcb[i] = sc.gcb;
         if (i >= n) continue;
         const gsvc_generator_grads &gr = grads[i];
         float *ws = sc.wg;
@@ -1354,11 +1485,14 @@ int generators_backward(const gsvc_generator_net *nets, int n, const float *feat
         jobs.add(sc.gh, sv.a1, gr.W2, gr.b2, HID, HID, M, ws);
         jobs.add(sc.go, sv.x3, gr.W3, gr.b3, g.out_dim, HID, M, ws);
         jobs.add(sc.gcg, fr.cond, gr.Wg0, gr.bg0, COND, COND, fr.rows, ws);
-        jobs.add(sc.ggamma_sum, sv.cg, gr.Wg1, gr.bg1, HID, COND, fr.rows, ws);
+        jobs.add(sc.ggamma, sv.cg, gr.Wg1, gr.bg1, HID, COND, fr.rows, ws);
         jobs.add(sc.gcb, fr.cond, gr.Wb0, gr.bb0, COND, COND, fr.rows, ws);
-        jobs.add(sc.gbeta_sum, sv.cb, gr.Wb1, gr.bb1, HID, COND, fr.rows, ws);
+        jobs.add(sc.gbeta, sv.cb, gr.Wb1, gr.bb1, HID, COND, fr.rows, ws);
     }
-    chain_launch("k_trunk_bwd", &k_trunk_bwd<FEAT, HID, CHAIN_T>, TrunkBwdLds<FEAT, HID, 70>::FLOATS * 4, M * n, n, s, tb, M);
+    if (fr.shared)      // the trunk walks FiLM rows, two gathered sub-blocks each
+        chain_launch("k_trunk_bwd", &k_trunk_bwd_paired<FEAT, HID, CHAIN_T>, TrunkBwdLds<FEAT, HID, 70>::FLOATS * 4, fr.rows * n, n, s, tb, M);
+    else
+        chain_launch("k_trunk_bwd", &k_trunk_bwd<FEAT, HID, CHAIN_T>, TrunkBwdLds<FEAT, HID, 70>::FLOATS * 4, M * n, n, s, tb, M);
     chain_launch("k_film_nets_bwd", &k_film_nets_bwd<COND, HID, CHAIN_T>, (size_t)2 * cl_kg(COND) * 16 * cl_ld(HID) * 4, fr.rows * n, n, s, fb,
                  fr.rows);
     return check_launch("generators_backward");
@@ -1461,7 +1595,7 @@ extern "C" int64_t gsvc_generator_scratch_floats(const gsvc_generator_net *n, in
 {
     if (!n || M < 0 || film_rows < 0) return -1;
     const int64_t Mf = film_rows > 0 ? film_rows : M;
-    return (int64_t)(n->out_dim + 4 * HID) * M + (int64_t)(2 * COND + (film_rows > 0 ? 2 * HID : 0)) * Mf + gen_wgrad_floats(n->out_dim) + 96;
+    return (int64_t)(n->out_dim + 2 * HID) * M + (int64_t)(2 * COND + 2 * HID) * Mf + gen_wgrad_floats(n->out_dim) + 96;
 }
 
 extern "C" int64_t gsvc_generator_inference_floats(const gsvc_generator_net *n, int64_t M, int64_t film_rows)

@@ -801,6 +801,12 @@ typedef struct gsvc_generator_grads {
  *   rows      number of FiLM rows;  cond [rows, cond_dim] their condition
  *   row_of    [M] int32: chain row (view, anchor) -> its FiLM row
  *   src_a/_b  [rows] int32: the (up to) two chain rows of a FiLM row, -1 = that view does not see the anchor
+ * Precondition: every chain row r is named exactly once, by src_a[row_of[r]] or by src_b[row_of[r]] (gsvc_film_row_maps leaves the
+ * maps so).  The backward relies on it: with shared rows k_trunk_bwd walks the FiLM rows and takes the two chain rows behind each
+ * one through the chain together (a chain row nobody names gets no gradient written, one named twice is written twice), hands the
+ * FiLM networks the two views' SUMMED d gamma / d beta, one row per FiLM row, and the scratch holds no per-view rows of them:
+ * gsvc_generator_scratch_floats is (out + 2 hidden) M + (2 cond + 2 hidden) rows floats + the weight gradients' partial sums.
+ * src_a / src_b increase within a view, so the gathered accesses stay nearly contiguous.
  * NULL (or rows = 0): one FiLM row per chain row, conditions = cond.  The sizes below take the FiLM row count (0 = M). */
 typedef struct gsvc_film_rows {
     int64_t rows;
