@@ -261,6 +261,11 @@ _SIGNATURES = {
                                     _vp, _i64, _vp]),
     "gsvc_frames_from_u8": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                       C.POINTER(C.c_void_p), _vp]),
+    "gsvc_frames_bytes": (_i64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "gsvc_frames_to_u16": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, _vp, _i64, _vp]),
+    "gsvc_frames_from_u16": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.POINTER(C.c_void_p), _vp]),
 }
 
 

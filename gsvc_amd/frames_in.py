@@ -1,5 +1,5 @@
-"""Encoder input: 8-bit RGB / YUV video files to float frames on the GPU (host side of csrc/frames_in.hip), the mirror image of
-``frames_out``.
+"""Encoder input: 8-bit RGB / YUV and 10 / 12 / 16-bit planar YUV video files to float frames on the GPU (host side of
+csrc/frames_in.hip), the mirror image of ``frames_out``.
 
 A fit reads float32 ``[3, H, W]`` pictures; a video file holds 8 bits per sample.  ``io.FrameCubeDataset`` opens one PNG per frame
 with PIL and divides by 255 on the host; here ``open_video`` hands out the bytes of a ``.y4m`` / ``.yuv`` / ``.rgb`` file,
@@ -10,7 +10,8 @@ as they are in the file and converted one frame per fetch (``resident="u8"``: 3.
 The conversion (include/gsvc_hip.h, gsvc_frames_from_u8): ``rgb24`` is ``b / 255`` (bit-equal to ``io.load_image``); the YUV layouts
 invert the BT.709 / BT.601 matrix of ``frames_out`` for limited or full range codes and clamp to [0, 1]; 4:2:0 chroma is centre
 sited (Y4M ``C420jpeg``, what ``Y4MWriter`` writes) and upsampled on the codes, ``chroma="bilinear"`` (the default; weights 9/16,
-3/16, 3/16, 1/16) or ``"nearest"``.
+3/16, 3/16, 1/16) or ``"nearest"``.  Deep frames (``fmt.depth`` 10 / 12 / 16: little-endian 16-bit samples in the same flat ``uint8``
+buffers, twice the bytes; gsvc_frames_from_u16) go through the same formulas with the constants of their depth.
 
 Importing this module needs neither a GPU nor the built library; ``frames_from_u8`` and ``VideoFileCube`` do (no CPU fallback).
 """
@@ -38,7 +39,9 @@ def _chroma_id(chroma: str) -> int:
 # ----------------------------------------------------------------------------------------------------------------------------
 def frames_from_u8(frames_u8, H: int, W: int, fmt: FrameFormat = FrameFormat(), chroma: str = "bilinear", out=None):
     """uint8 CUDA frames ``[n, >= frame_bytes]`` with contiguous rows (or one flat frame) -> float32 ``[n, 3, H, W]`` RGB on their
-    device, one launch per 16 frames on the current stream; nothing synchronises.  Bytes of a row past the frame are not read;
+    device, one launch per 16 frames on the current stream; nothing synchronises.  The ``_u8`` of the name means "a buffer of bytes":
+    a deep format (``fmt.depth`` above 8) reads little-endian 16-bit samples from it; the frames must then start at even addresses
+    (an even base and row stride).  Bytes of a row past the frame are not read;
     ``fmt.rounding`` is ignored.  ``out``: a float32 CUDA tensor ``[n, 3, H, W]`` whose images are contiguous (it is returned)."""
     import ctypes as C
 
@@ -57,7 +60,7 @@ def frames_from_u8(frames_u8, H: int, W: int, fmt: FrameFormat = FrameFormat(), 
         frames_u8 = frames_u8.unsqueeze(0)
     n = int(frames_u8.shape[0])
     if n < 1 or frames_u8.shape[1] < nbytes or frames_u8.stride(1) != 1 or (n > 1 and frames_u8.stride(0) < nbytes):
-        raise ValueError(f"frames_from_u8: a {fmt.layout} frame of {H} x {W} has {nbytes} bytes; frames must be [n >= 1, >= {nbytes}] "
+        raise ValueError(f"frames_from_u8: a {fmt.name} frame of {H} x {W} has {nbytes} bytes; frames must be [n >= 1, >= {nbytes}] "
                          f"with contiguous rows (got {tuple(frames_u8.shape)}, strides {tuple(frames_u8.stride())})")
     dev = frames_u8.device
     if out is None:
@@ -67,12 +70,18 @@ def frames_from_u8(frames_u8, H: int, W: int, fmt: FrameFormat = FrameFormat(), 
         raise ValueError(f"frames_from_u8: out must be float32 [{n}, 3, {H}, {W}] on {dev} with contiguous images")
     L = _lib.lib()
     stride = int(frames_u8.stride(0)) if n > 1 else max(int(frames_u8.stride(0)), nbytes)
+    if fmt.depth > 8 and n == 1:
+        stride += stride & 1          # (one frame: the stride addresses nothing)
     base, obase, ostride = frames_u8.data_ptr(), out.data_ptr(), int(out.stride(0)) * 4
     with torch.cuda.device(dev):
         stream = _lib.current_stream(dev)
         for i in range(0, n, MAX_BATCH):
             m = min(MAX_BATCH, n - i)
             ptrs = (C.c_void_p * m)(*[obase + (i + k) * ostride for k in range(m)])
+            if fmt.depth > 8:
+                _lib.check(L.gsvc_frames_from_u16(base + i * stride, stride, m, H, W, LAYOUTS[fmt.layout], MATRICES[fmt.matrix],
+                                                  RANGES[fmt.range], cid, fmt.depth, ptrs, stream), "gsvc_frames_from_u16")
+                continue
             _lib.check(L.gsvc_frames_from_u8(base + i * stride, stride, m, H, W, LAYOUTS[fmt.layout], MATRICES[fmt.matrix],
                                              RANGES[fmt.range], cid, ptrs, stream), "gsvc_frames_from_u8")
     return out
@@ -82,10 +91,11 @@ def frames_from_u8(frames_u8, H: int, W: int, fmt: FrameFormat = FrameFormat(), 
 # files
 # ----------------------------------------------------------------------------------------------------------------------------
 def open_video(path, W: int | None = None, H: int | None = None, fmt: FrameFormat | None = None):
-    """``(header, frames)`` of a video file of 8-bit frames; frames = uint8 array ``[T, frame_bytes]``, header = {"W", "H", "frames",
-    "frame_bytes", "fmt": the FrameFormat of the payload, ...}.
+    """``(header, frames)`` of a video file of 8-bit or deep (10 / 12 / 16-bit, two bytes per sample) frames; frames = uint8 array
+    ``[T, frame_bytes]``, header = {"W", "H", "frames", "frame_bytes", "depth", "fmt": the FrameFormat of the payload, ...}.  The depth
+    of a ``.y4m`` file comes from the file (``C420p10``, ...), that of a raw file from ``fmt``.
 
-    ``.y4m``: read with ``frames_out.read_y4m`` (its header's fields are kept); the file's size, layout and ``XCOLORRANGE`` win over
+    ``.y4m``: read with ``frames_out.read_y4m`` (its header's fields are kept); the file's size, layout, depth and ``XCOLORRANGE`` win over
     ``W``, ``H`` and ``fmt``, which supplies the matrix (Y4M has no field for it) and the range of a file that does not state one.
     ``.yuv`` / ``.rgb``: frame payloads back to back (``RawWriter``), memory-mapped; ``W`` and ``H`` are required and a file whose
     size is not a whole number of frames is refused.  ``fmt`` None: what ``open_sink`` uses for the extension — yuv420p (BT.709,
@@ -97,7 +107,7 @@ def open_video(path, W: int | None = None, H: int | None = None, fmt: FrameForma
         base = fmt or FrameFormat("yuv420p")
         if hdr["range"] not in (None, "limited", "full"):
             raise ValueError(f"{path}: unknown XCOLORRANGE={hdr['range']}")
-        used = FrameFormat(hdr["layout"], base.matrix, hdr["range"] or base.range, base.rounding)
+        used = FrameFormat(hdr["layout"], base.matrix, hdr["range"] or base.range, base.rounding, hdr["depth"])
         hdr = dict(hdr, frames=int(frames.shape[0]), fmt=used)
         return hdr, frames
     if ext in (".yuv", ".rgb"):
@@ -107,10 +117,10 @@ def open_video(path, W: int | None = None, H: int | None = None, fmt: FrameForma
         nbytes = frame_bytes(H, W, used)
         size = os.path.getsize(path)
         if size == 0 or size % nbytes:
-            raise ValueError(f"{path}: {size} bytes are not a whole number of {used.layout} frames of {int(W)} x {int(H)} "
+            raise ValueError(f"{path}: {size} bytes are not a whole number of {used.name} frames of {int(W)} x {int(H)} "
                              f"({nbytes} bytes each)")
         frames = np.memmap(path, dtype=np.uint8, mode="r", shape=(size // nbytes, nbytes))
-        return {"W": int(W), "H": int(H), "layout": used.layout, "range": used.range, "frame_bytes": nbytes,
+        return {"W": int(W), "H": int(H), "layout": used.layout, "range": used.range, "depth": used.depth, "frame_bytes": nbytes,
                 "frames": size // nbytes, "fmt": used}, frames
     raise ValueError(f"{path}: open_video reads .y4m, .yuv and .rgb files")
 
@@ -120,7 +130,7 @@ class VideoFileCube:
     (``dataset[i]`` is frame i with its picture kept transposed ``[3, W, H]`` and its camera at ``z = (i - T/2) / scale``;
     ``get_optical_flow(i)`` the flow between frames i and i + 1, from ``optical_flow_dir`` through ``io.load_flow``).
 
-    The 8-bit frames are uploaded in chunks of up to 16 through one pinned staging buffer and converted on the device
+    The frames (8-bit, or deep: ``resident="u8"`` then means "as the file's bytes", 6.2 MB per 1080p 4:2:0 frame) are uploaded in chunks of up to 16 through one pinned staging buffer and converted on the device
     (``frames_from_u8``); no float arithmetic on pixels runs on the host.
       ``resident="float"``  every frame is converted once and kept as float32: fetching a frame launches nothing.
       ``resident="u8"``     the video stays in device memory as it is in the file; ``get_z_frame`` converts the one frame it hands

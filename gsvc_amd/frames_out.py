@@ -1,4 +1,5 @@
-"""Decoder output: 8-bit RGB / YUV frames from the render loop, to host memory and to files (host side of csrc/frames_out.hip).
+"""Decoder output: 8-bit RGB / YUV frames and 10 / 12 / 16-bit planar YUV frames from the render loop, to host memory and to files
+(host side of csrc/frames_out.hip).
 
 ``render_frames`` yields float32 ``[3, H, W]`` images in device memory; a player, ``ffmpeg`` or a quality tool takes 8-bit frames.
 The reference converts on the host, one frame at a time (utils/report_utils.py:412-447: average the views, clamp, ``ToPILImage``,
@@ -10,6 +11,11 @@ The conversion (include/gsvc_hip.h, gsvc_frames_to_u8): clamp to [0, 1] (NaN -> 
 Y, Cb, Cr (``yuv444p`` / ``yuv420p``, BT.709 or BT.601 weights, limited or full range; 4:2:0 chroma is the mean of the 2x2 block
 taken in float: centre siting, Y4M's ``C420jpeg``); rounding ``trunc`` (what ``ToPILImage`` does; the default of ``rgb24``) or
 ``nearest`` (the default of the YUV layouts).
+
+Deep frames (``FrameFormat(depth=10 | 12 | 16)``, ``yuv444p`` / ``yuv420p`` only; gsvc_frames_to_u16): every sample is one little-endian
+16-bit word whose upper bits are zero — ffmpeg's ``yuv420p10le``, Y4M's ``C420p10``.  A frame still travels as a flat ``uint8`` buffer
+of ``frame_bytes`` (twice the 8-bit count): the ``_u8`` in ``frames_to_u8`` / ``render_frames_u8`` means "a buffer of bytes", not
+"8-bit samples", and the pinned double buffer, ``write_frames`` and the sinks carry deep frames as they carry 8-bit ones.
 
 Importing this module needs neither a GPU nor the built library; ``frames_to_u8`` and what is built on it do (no CPU fallback).
 """
@@ -29,17 +35,20 @@ LAYOUTS = {"rgb24": 0, "yuv444p": 1, "yuv420p": 2}          # the GSVC_FRAMES_* 
 MATRICES = {"bt709": 0, "bt601": 1}
 RANGES = {"limited": 0, "full": 1}
 ROUNDINGS = {"trunc": 0, "nearest": 1}
+DEPTHS = (8, 10, 12, 16)                                     # bits per sample; above 8: one little-endian 16-bit word per sample
 MAX_BATCH = 16                                               # GSVC_FRAMES_MAX_BATCH: images per launch
 
 
 @dataclass(frozen=True)
 class FrameFormat:
-    """What an 8-bit frame looks like.  ``rounding=None`` takes the layout's default: ``trunc`` for ``rgb24`` (bit-equal to the
-    reference's PNGs), ``nearest`` for YUV.  ``matrix`` and ``range`` do not apply to ``rgb24`` (always 255 c)."""
+    """What a frame looks like.  ``rounding=None`` takes the layout's default: ``trunc`` for ``rgb24`` (bit-equal to the
+    reference's PNGs), ``nearest`` for YUV.  ``matrix`` and ``range`` do not apply to ``rgb24`` (always 255 c).  ``depth``: bits per
+    sample, 8, or 10 / 12 / 16 for the planar YUV layouts (little-endian 16-bit words)."""
     layout: str = "yuv420p"
     matrix: str = "bt709"
     range: str = "limited"
     rounding: str | None = None
+    depth: int = 8
 
     def __post_init__(self):
         for what, value, table in (("layout", self.layout, LAYOUTS), ("matrix", self.matrix, MATRICES), ("range", self.range, RANGES)):
@@ -47,31 +56,61 @@ class FrameFormat:
                 raise ValueError(f"FrameFormat: unknown {what} {value!r} (one of {', '.join(table)})")
         if self.rounding is not None and self.rounding not in ROUNDINGS:
             raise ValueError(f"FrameFormat: unknown rounding {self.rounding!r} (one of {', '.join(ROUNDINGS)} or None)")
+        if isinstance(self.depth, bool) or self.depth not in DEPTHS:
+            raise ValueError(f"FrameFormat: unknown depth {self.depth!r} (one of {', '.join(str(d) for d in DEPTHS)})")
+        if self.layout == "rgb24" and self.depth != 8:
+            raise ValueError(f"FrameFormat: rgb24 frames are 8-bit (got depth {self.depth})")
 
     @property
     def rounding_used(self) -> str:
         return self.rounding if self.rounding is not None else ("trunc" if self.layout == "rgb24" else "nearest")
 
+    @property
+    def name(self) -> str:
+        """ffmpeg's spelling of layout and depth: ``yuv420p``, ``rgb24``, ``yuv444p10le``."""
+        return self.layout if self.depth == 8 else f"{self.layout}{self.depth}le"
+
+    @classmethod
+    def from_name(cls, name: str, matrix: str = "bt709", range: str = "limited", rounding: str | None = None) -> "FrameFormat":
+        """``yuv420p`` / ``yuv444p`` / ``rgb24``, or a deep spelling ``yuv4{20,44}p{10,12,16}[le]``."""
+        text = str(name)
+        if text in LAYOUTS:
+            return cls(text, matrix, range, rounding)
+        stem = text[:-2] if text.endswith("le") else text
+        for layout in ("yuv420p", "yuv444p"):
+            if stem.startswith(layout) and stem[len(layout):] in ("10", "12", "16"):
+                return cls(layout, matrix, range, rounding, int(stem[len(layout):]))
+        raise ValueError(f"FrameFormat: unknown format name {name!r} (yuv420p, yuv444p, rgb24 or yuv4{{20,44}}p{{10,12,16}}[le])")
+
 
 def frame_bytes(H: int, W: int, fmt: FrameFormat = FrameFormat()) -> int:
-    """Bytes of one frame: 3 H W (``rgb24``, ``yuv444p``) or H W 3 / 2 (``yuv420p``: one I420 frame; H and W even)."""
+    """Bytes of one frame: 3 H W (``rgb24``, ``yuv444p``) or H W 3 / 2 (``yuv420p``: one I420 frame; H and W even); twice that for
+    a deep format (``fmt.depth`` above 8: two bytes per sample)."""
     H, W = int(H), int(W)
     if H < 1 or W < 1:
         raise ValueError(f"frame_bytes: image size must be positive (got {H} x {W})")
+    per = 2 if fmt.depth > 8 else 1
     if fmt.layout == "yuv420p":
         if H % 2 or W % 2:
             raise ValueError(f"frame_bytes: yuv420p needs even H and W (got {H} x {W})")
-        return H * W * 3 // 2
-    return 3 * H * W
+        return H * W * 3 // 2 * per
+    return 3 * H * W * per
 
 
 def planes(buf, H: int, W: int, fmt: FrameFormat = FrameFormat()):
     """Views into one flat uint8 frame (numpy array or tensor): ``(rgb [H, W, 3],)`` or ``(y [H, W], u, v)`` with u, v ``[H, W]``
-    (``yuv444p``) or ``[H / 2, W / 2]`` (``yuv420p``)."""
+    (``yuv444p``) or ``[H / 2, W / 2]`` (``yuv420p``).  Deep formats: the views are little-endian uint16 (``'<u2'`` / ``torch.uint16``)
+    over the same bytes; the frame must then start at an even address."""
     n = frame_bytes(H, W, fmt)
     flat = buf.reshape(-1)
     if flat.shape[0] != n:
-        raise ValueError(f"planes: a {fmt.layout} frame of {H} x {W} has {n} bytes, got {flat.shape[0]}")
+        raise ValueError(f"planes: a {fmt.name} frame of {H} x {W} has {n} bytes, got {flat.shape[0]}")
+    if fmt.depth > 8:
+        if isinstance(flat, np.ndarray):
+            flat = flat.view("<u2")
+        else:
+            import torch
+            flat = flat.view(torch.uint16)          # (this project runs on little-endian hosts only)
     if fmt.layout == "rgb24":
         return (flat.reshape(H, W, 3),)
     ch, cw = (H // 2, W // 2) if fmt.layout == "yuv420p" else (H, W)
@@ -89,7 +128,9 @@ def rgb24_to_image(frame, H: int, W: int):
 # ----------------------------------------------------------------------------------------------------------------------------
 def frames_to_u8(images, fmt: FrameFormat = FrameFormat(), out=None):
     """float32 CUDA images ``[3, H, W]`` of one size (a sequence, or one ``[n, 3, H, W]`` tensor) -> uint8 ``[n, frame_bytes]`` on
-    their device, one launch per 16 images on the current stream; nothing synchronises.  Images that are not contiguous are made
+    their device, one launch per 16 images on the current stream; nothing synchronises.  The ``_u8`` of the name means "a buffer of
+    bytes": a deep format (``fmt.depth`` above 8) gives little-endian 16-bit samples in that buffer (``planes`` views them), and
+    ``out`` must then start at an even address with an even row stride.  Images that are not contiguous are made
     so.  ``out``: a uint8 CUDA tensor ``[n, >= frame_bytes]`` whose rows are contiguous (bytes of a row past the frame are left
     alone); the return value is its ``[:, :frame_bytes]`` view."""
     import ctypes as C
@@ -116,20 +157,42 @@ def frames_to_u8(images, fmt: FrameFormat = FrameFormat(), out=None):
         raise ValueError(f"frames_to_u8: out must be uint8 [{n}, >= {nbytes}] with contiguous rows on {first.device}")
     L = _lib.lib()
     stride = int(out.stride(0)) if n > 1 else max(int(out.stride(0)), nbytes)
+    if fmt.depth > 8 and n == 1:
+        stride += stride & 1          # (one frame: the stride addresses nothing)
     with torch.cuda.device(first.device):
         stream = _lib.current_stream(first.device)
         for i in range(0, n, MAX_BATCH):
             chunk = [img.contiguous() for img in images[i:i + MAX_BATCH]]      # (alive until the launch is enqueued on their stream)
             ptrs = (C.c_void_p * len(chunk))(*[img.data_ptr() for img in chunk])
+            if fmt.depth > 8:
+                _lib.check(L.gsvc_frames_to_u16(ptrs, len(chunk), H, W, LAYOUTS[fmt.layout], MATRICES[fmt.matrix], RANGES[fmt.range],
+                                                ROUNDINGS[fmt.rounding_used], fmt.depth, out.data_ptr() + i * stride, stride, stream),
+                           "gsvc_frames_to_u16")
+                continue
             _lib.check(L.gsvc_frames_to_u8(ptrs, len(chunk), H, W, LAYOUTS[fmt.layout], MATRICES[fmt.matrix], RANGES[fmt.range],
                                            ROUNDINGS[fmt.rounding_used], out.data_ptr() + i * stride, stride, stream),
                        "gsvc_frames_to_u8")
     return out[:, :nbytes]
 
 
+def delivered_images(images, fmt: FrameFormat = FrameFormat(), chroma: str = "bilinear"):
+    """The float pictures ``[n, 3, H, W]`` a viewer of the delivered frames sees: ``frames_from_u8(frames_to_u8(images, fmt), H, W, fmt,
+    chroma)`` — quantised to ``fmt.depth`` bits, 4:2:0 chroma subsampled and upsampled again — or, for ``rgb24``, ``rgb24_to_image`` of
+    every frame (bytes / 255).  What a codec's PSNR is taken on (``report.evaluate(delivered=fmt)``)."""
+    import torch
+    u8 = frames_to_u8(images, fmt)
+    first = images[0]
+    H, W = int(first.shape[-2]), int(first.shape[-1])
+    if fmt.layout == "rgb24":
+        return torch.stack([rgb24_to_image(fr, H, W) for fr in u8])
+    from .frames_in import frames_from_u8
+    return frames_from_u8(u8, H, W, fmt, chroma)
+
+
 def render_frames_u8(frames, pc, pipe, bg_color, fmt: FrameFormat = FrameFormat(), batch: int = 8, to_host: bool = True,
                      scaling_modifier=1.0, mode=None):
-    """The decoder's render loop with 8-bit output: a generator over ``render_frames`` that converts each render batch with one
+    """The decoder's render loop with frames of bytes as output (8-bit samples, or little-endian 16-bit samples for a deep ``fmt``): a
+    generator over ``render_frames`` that converts each render batch with one
     launch and yields one flat uint8 frame (``frame_bytes`` long; ``planes`` splits it) per video frame, in order.
 
     ``to_host=True``: a batch is copied into one of two pinned host buffers by a non-blocking copy on a stream of its own, ordered
@@ -240,7 +303,7 @@ class RawWriter(_Sink):
 
 class Y4MWriter(_Sink):
     """YUV4MPEG2 file: header ``YUV4MPEG2 W{W} H{H} F{n}:{d} Ip A1:1 C420jpeg XCOLORRANGE=LIMITED`` (``C444`` / ``FULL`` as the
-    format says), then ``FRAME\\n`` + payload per frame.  Y4M has no field for the matrix: a BT.601 file and a BT.709 file have the
+    format says; ``C420p10``, ``C444p12``, ... for a deep format), then ``FRAME\\n`` + payload per frame.  Y4M has no field for the matrix: a BT.601 file and a BT.709 file have the
     same header, and most readers guess BT.601 below 720 lines and BT.709 from there — say which one was written next to the file."""
 
     def __init__(self, path, W: int, H: int, fps=(30, 1), fmt: FrameFormat = FrameFormat()):
@@ -257,7 +320,7 @@ class Y4MWriter(_Sink):
     def write(self, frame_u8):
         a = _as_bytes_array(frame_u8)
         if a.shape[0] != self.frame_bytes:
-            raise ValueError(f"Y4MWriter: a {self.fmt.layout} frame of {self.H} x {self.W} has {self.frame_bytes} bytes, got {a.shape[0]}")
+            raise ValueError(f"Y4MWriter: a {self.fmt.name} frame of {self.H} x {self.W} has {self.frame_bytes} bytes, got {a.shape[0]}")
         self._f.write(b"FRAME\n")
         self._f.write(a.data)
         self.frames += 1
@@ -274,12 +337,16 @@ def y4m_header(W: int, H: int, fps=(30, 1), fmt: FrameFormat = FrameFormat()) ->
     if n < 1 or d < 1:
         raise ValueError(f"y4m_header: bad frame rate {fps!r}")
     chroma = {"yuv420p": "420jpeg", "yuv444p": "444"}[fmt.layout]
+    if fmt.depth > 8:
+        chroma = f"{chroma[:3]}p{fmt.depth}"
     return f"YUV4MPEG2 W{int(W)} H{int(H)} F{n}:{d} Ip A1:1 C{chroma} XCOLORRANGE={fmt.range.upper()}\n".encode("ascii")
 
 
 def read_y4m(path):
-    """``(header, frames)`` of a Y4M file of 8-bit 4:2:0 / 4:4:4 frames: header = {"W", "H", "fps": (n, d), "interlace", "aspect",
-    "chroma", "range" (None when the file does not say), "layout", "frame_bytes"}; frames = uint8 numpy ``[T, frame_bytes]``."""
+    """``(header, frames)`` of a Y4M file of 4:2:0 / 4:4:4 frames of 8 (``C420jpeg``, ``C444``, ...), 10, 12 or 16 bits (``C420p10``,
+    ``C444p12``, ...; every 4:2:0 tag is read as centre sited): header = {"W", "H", "fps": (n, d), "interlace", "aspect", "chroma",
+    "range" (None when the file does not say), "layout", "depth", "frame_bytes"}; frames = uint8 numpy ``[T, frame_bytes]``, a fresh
+    array (every frame starts at an even address)."""
     data = open(path, "rb").read()
     end = data.index(b"\n")
     fields = data[:end].decode("ascii").split(" ")
@@ -304,13 +371,16 @@ def read_y4m(path):
             hdr["chroma"] = val
         elif f.startswith("XCOLORRANGE="):
             hdr["range"] = f.split("=", 1)[1].lower()
+    deep = {f"{c}p{d}": ("yuv" + c + "p", d) for c in ("420", "444") for d in (10, 12, 16)}
     if hdr["chroma"] in ("420jpeg", "420", "420mpeg2", "420paldv"):
-        hdr["layout"] = "yuv420p"
+        hdr["layout"], hdr["depth"] = "yuv420p", 8
     elif hdr["chroma"] == "444":
-        hdr["layout"] = "yuv444p"
+        hdr["layout"], hdr["depth"] = "yuv444p", 8
+    elif hdr["chroma"] in deep:
+        hdr["layout"], hdr["depth"] = deep[hdr["chroma"]]
     else:
-        raise ValueError(f"{path}: chroma format C{hdr['chroma']} is not 8-bit 4:2:0 / 4:4:4")
-    nbytes = frame_bytes(hdr["H"], hdr["W"], FrameFormat(hdr["layout"]))
+        raise ValueError(f"{path}: chroma format C{hdr['chroma']} is not 4:2:0 / 4:4:4 of 8, 10, 12 or 16 bits")
+    nbytes = frame_bytes(hdr["H"], hdr["W"], FrameFormat(hdr["layout"], depth=hdr["depth"]))
     hdr["frame_bytes"] = nbytes
     out, pos = [], end + 1
     while pos < len(data):
@@ -402,7 +472,8 @@ def write_video(frames, pc, pipe, bg_color, sink, fmt: FrameFormat = FrameFormat
 
 def open_sink(path, W: int, H: int, fps=(30, 1), fmt: FrameFormat | None = None):
     """``(sink, format)`` for a path: ``.y4m`` -> Y4MWriter, ``.yuv`` / ``.rgb`` -> RawWriter, anything else -> a directory of PNGs.
-    ``fmt`` None: yuv420p for ``.y4m`` / ``.yuv``, rgb24 for ``.rgb`` and PNGs."""
+    ``fmt`` None: yuv420p for ``.y4m`` / ``.yuv``, rgb24 for ``.rgb`` and PNGs.  A deep ``fmt`` (``depth`` 10 / 12 / 16) is carried as it
+    is: the Y4M header says ``C420p10``, a raw file holds two bytes per sample."""
     ext = os.path.splitext(str(path))[1].lower()
     if ext == ".y4m":
         fmt = fmt or FrameFormat("yuv420p")

@@ -19,12 +19,16 @@ from .ortho_gaussian_renderer import render_frames
 
 
 @torch.no_grad()
-def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_fn=None, eight_bit: bool = False) -> dict:
+def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_fn=None, eight_bit: bool = False, delivered=None) -> dict:
     """Mean L1 / PSNR / SSIM / MS-SSIM (MS-SSIM only for frames at least 160 pixels high and large enough for 5 scales) of the
     rendered two-view frames, clamped to [0, 1], against ``dataset[i].image``; ``fps`` counts the whole loop's wall time,
     metrics excluded.  ``eight_bit=True``: the metrics are taken on what the decoder delivers — the frames quantised to 8 bits
     (``frames_out.frames_to_u8``: rgb24, truncating, as the reference's PNGs) / 255 — as a codec's PSNR is, and the result says so
-    (``"eight_bit": True``)."""
+    (``"eight_bit": True``).  ``delivered=FrameFormat(...)``: the metrics are taken on ``frames_out.delivered_images`` of the frames —
+    what a viewer of frames delivered in that format sees, at its depth and chroma subsampling — and the result records the format
+    (``"delivered": fmt.name``).  Giving both is a ValueError."""
+    if eight_bit and delivered is not None:
+        raise ValueError("evaluate: eight_bit=True and delivered= both say what is delivered; give one")
     ids = list(range(dataset.len_z_frames)) if frame_ids is None else list(frame_ids)
     frames = [dataset[i] for i in ids]
     for _ in render_frames(frames[:min(len(frames), batch)], pc, pipe, bg_color, batch=batch):      # warm-up, as the reference does
@@ -38,6 +42,9 @@ def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_
         from .frames_out import FrameFormat, frames_to_u8, rgb24_to_image
         H, W = images[0].shape[1:]
         images = [rgb24_to_image(u8, H, W) for u8 in frames_to_u8(images, FrameFormat("rgb24", rounding="trunc"))]
+    if delivered is not None and images:
+        from .frames_out import delivered_images
+        images = list(delivered_images(images, delivered).unbind(0))
     sums = {"l1": 0.0, "psnr": 0.0, "ssim": 0.0, "msssim": 0.0, "lpips": 0.0}
     n_ms = 0
     for fr, img in zip(frames, images):
@@ -55,6 +62,8 @@ def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_
            "msssim": sums["msssim"] / n_ms if n_ms else float("nan"), "lpips": sums["lpips"] / n if lpips_fn is not None else None, "fps": len(frames) / elapsed if elapsed > 0 else float("inf")}
     if eight_bit:
         out["eight_bit"] = True
+    if delivered is not None:
+        out["delivered"] = delivered.name
     return out
 
 

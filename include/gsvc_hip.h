@@ -939,6 +939,42 @@ enum { GSVC_FRAMES_CHROMA_NEAREST = 0, GSVC_FRAMES_CHROMA_BILINEAR = 1 };
 int gsvc_frames_from_u8(const uint8_t *in, int64_t in_stride, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t matrix,
                         int32_t range, int32_t chroma, float *const *images_host, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * [INTERNAL] Decoder output, deep frames: planar YUV of d = 9 .. 16 bits per sample, every sample one little-endian 16-bit word
+ * whose upper 16 - d bits are zero (ffmpeg's yuv420p10le, yuv444p12le, ...; Y4M's C420p10, C444p12, ...).  Everything not said here is
+ * as in gsvc_frames_to_u8: n, the images, the clamp of the inputs, Y / Cb / Cr, the plane order Y, U, V, the 4:2:0 chroma mean taken in
+ * float before quantisation, matrix, rounding.  A frame has twice the bytes of its 8-bit form.
+ *   range       GSVC_FRAMES_LIMITED: the 8-bit expression with both constants scaled by 2^(d - 8),
+ *                 Y_d = 2^(d - 8) (16 + 219 Y), C_d = 2^(d - 8) (128 + 224 C)
+ *               (a scaling by a power of two: the float32 value is exactly 2^(d - 8) times the 8-bit kernel's).
+ *               GSVC_FRAMES_FULL: Y_d = (2^d - 1) Y, C_d = 2^(d - 1) + (2^d - 1) C.
+ *               The value is clamped to [0, 2^d - 1]; then (uint16) v (TRUNC) or (uint16)(v + 0.5) (NEAREST).
+ * Refused with an error before any launch: GSVC_FRAMES_RGB24, a depth outside 9 .. 16, n outside 1 .. 16, an odd H or W for 4:2:0, a
+ * frame base or an out_stride that is not a multiple of 2, out_stride below the frame's bytes.  Nothing synchronises.
+ * gsvc_frames_bytes: bytes of one frame of the given depth: gsvc_frames_u8_bytes for depth 8, twice that for depth 9 .. 16; < 0 for
+ * RGB24 with a depth other than 8, for any other depth and for an invalid size or layout.
+ * ---------------------------------------------------------------------------------------------------- */
+int64_t gsvc_frames_bytes(int32_t H, int32_t W, int32_t layout, int32_t depth);
+int gsvc_frames_to_u16(const float *const *images_host, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t matrix, int32_t range,
+                       int32_t rounding, int32_t depth, uint8_t *out, int64_t out_stride, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
+ * [INTERNAL] Encoder input, deep frames: the mirror image of gsvc_frames_to_u16.  Sample codes y, cb, cr are the 16-bit words as
+ * they are in the frame (a code above 2^d - 1 is NOT masked; the result clamps).  Everything not said here is as in
+ * gsvc_frames_from_u8: n, the images, the three fused multiply-adds and the clamp, matrix, the chroma modes and their weights.
+ *   range       GSVC_FRAMES_LIMITED: Y = (y - 16 2^(d - 8)) / (219 2^(d - 8)), C = (c - 2^(d - 1)) / (224 2^(d - 8)).
+ *               GSVC_FRAMES_FULL:    Y = y / (2^d - 1),                        C = (c - 2^(d - 1)) / (2^d - 1).
+ *               IEEE float32 divisions, as in the 8-bit kernel (for a limited-range 8-bit code times 2^(d - 8) the quotients are the
+ *               same real numbers: the two kernels then give the same bits).
+ *   chroma      4:2:0 chroma is upsampled on the codes with the weights of gsvc_frames_from_u8; still exact in float32 (16 bits of
+ *               code and 4 bits of sixteenths are fewer than 24).
+ * Refused with an error before any launch: GSVC_FRAMES_RGB24, a depth outside 9 .. 16, n outside 1 .. 16, an odd H or W for 4:2:0, a
+ * frame base or an in_stride that is not a multiple of 2, in_stride below the frame's bytes (gsvc_frames_bytes).  Nothing synchronises;
+ * every element of the n images is written, nothing else.
+ * ---------------------------------------------------------------------------------------------------- */
+int gsvc_frames_from_u16(const uint8_t *in, int64_t in_stride, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t matrix,
+                         int32_t range, int32_t chroma, int32_t depth, float *const *images_host, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

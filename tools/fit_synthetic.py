@@ -37,6 +37,15 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def _frame_format(text):
+    """LAYOUT[,MATRIX[,RANGE]] -> FrameFormat; LAYOUT in ffmpeg's spelling (yuv420p, yuv444p10le, rgb24, ...)."""
+    from gsvc_amd.frames_out import FrameFormat
+    name, *rest = text.split(",")
+    if len(rest) > 2:
+        raise SystemExit(f"a frame format is LAYOUT[,MATRIX[,RANGE]] (got {text!r})")
+    return FrameFormat.from_name(name, **dict(zip(("matrix", "range"), rest)))
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=2000)
@@ -54,12 +63,16 @@ def main(argv=None):
     ap.add_argument("--lpips-weights", default=None, help="backbone (+ --lpips-lin-weights) file for gsvc_amd.lpips.LPIPS")
     ap.add_argument("--lpips-lin-weights", default=None)
     ap.add_argument("--write-decoded", default=None, metavar="PATH",
-                    help="write the decoded 8-bit-MLP model's frames as 8-bit video: .y4m / .yuv (yuv420p), .rgb (rgb24), else a directory of PNGs")
+                    help="write the decoded 8-bit-MLP model's frames as video: .y4m / .yuv (yuv420p), .rgb (rgb24), else a directory of PNGs "
+                         "(8-bit unless --decoded-format says otherwise)")
+    ap.add_argument("--decoded-format", default=None, metavar="LAYOUT[,MATRIX[,RANGE]]",
+                    help="what --write-decoded writes, e.g. yuv420p10le or yuv444p12le,bt709,full (default: what the path's extension means, 8-bit)")
     ap.add_argument("--video", default=None, metavar="PATH",
-                    help="fit this 8-bit video file (.y4m, or raw .yuv / .rgb with --video-size) instead of the synthetic frames")
+                    help="fit this 8-bit or 10 / 12 / 16-bit video file (.y4m, or raw .yuv / .rgb with --video-size) instead of the synthetic frames")
     ap.add_argument("--video-size", default=None, metavar="WxH", help="frame size of a raw --video file")
     ap.add_argument("--video-format", default=None, metavar="LAYOUT[,MATRIX[,RANGE]]",
-                    help="e.g. yuv420p,bt601,full (default: yuv420p,bt709,limited; rgb24 for .rgb; a .y4m file's own layout and range win)")
+                    help="e.g. yuv420p,bt601,full or yuv420p10le (default: yuv420p,bt709,limited; rgb24 for .rgb; a .y4m file's own layout, "
+                         "depth and range win)")
     ap.add_argument("--flow-dir", default=None, metavar="DIR", help="optical-flow files of --video, one per frame pair (none: optical_lambda = 0)")
     ap.add_argument("--video-resident", choices=("float", "u8"), default="float",
                     help="keep the video on the device as float32 pictures, or as the file's bytes (converted one frame per fetch)")
@@ -89,7 +102,7 @@ def main(argv=None):
         from gsvc_amd.frames_in import VideoFileCube
         from gsvc_amd.frames_out import FrameFormat
         vw, vh = (int(v) for v in args.video_size.lower().split("x")) if args.video_size else (None, None)
-        vfmt = FrameFormat(*args.video_format.split(",")) if args.video_format else None
+        vfmt = _frame_format(args.video_format) if args.video_format else None
         cube = VideoFileCube(args.video, optical_flow_dir=args.flow_dir, W=vw, H=vh, fmt=vfmt, device=dev, resident=args.video_resident)
         H, W, T = cube.height, cube.width, cube.len_z_frames          # the file says what is fitted
         if args.flow_dir is None:
@@ -254,9 +267,9 @@ def main(argv=None):
         log["decoded_8bit_mlp"] = ev
         if args.write_decoded:
             from gsvc_amd.frames_out import open_sink, write_video
-            sink, fmt = open_sink(args.write_decoded, W, H)
+            sink, fmt = open_sink(args.write_decoded, W, H, fmt=_frame_format(args.decoded_format) if args.decoded_format else None)
             log["decoded_video"] = dict(write_video([cube.get_dummy_frame(i) if args.video else cube[i] for i in range(T)], dec_q, pipe, bg, sink, fmt=fmt), path=args.write_decoded,
-                                        layout=fmt.layout)
+                                        layout=fmt.layout, format=fmt.name)
         log["total_bytes"] = int(total_bytes)
         log["bpp"] = 8.0 * total_bytes / (H * W * T)
         log["anchors_final"], log["anchors_coded"] = int(pc._anchor.shape[0]), int(pack.n)
