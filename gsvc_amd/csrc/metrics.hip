@@ -1,0 +1,570 @@
+// gsvc_amd/csrc/metrics.hip — video quality metrics as kernels, gfx950: the per-plane sum of squared code differences of two
+// frame buffers (PSNR-Y / -U / -V on the codes) and a fused MS-SSIM.
+//
+// gsvc_frames_sse   one launch for the n frames of a chunk (frame = blockIdx.y).  The planes of a frame are contiguous, so a frame
+//   is ONE flat run of samples and a plane is a range of sample indices: plane(s) = (s >= HW) + (s >= HW + chroma samples); rgb24's
+//   channel is s mod 3.  A lane's three accumulators are 64-bit; a wave reduces them with shuffles, the workgroup through LDS, and
+//   one thread per plane issues one 64-bit integer atomic (none for a sum of zero) — integer addition is associative: the result is
+//   the same bits in every run.
+//     wide path   (both bases and, for n > 1, both strides 16-byte aligned): a lane takes 16 bytes of a and of b per unit and
+//                 four units 256 units apart (rgb24: 48 bytes = three vectors per unit, so that byte j of a unit is channel j mod 3).
+//                 A vector may straddle a plane boundary (H W = 60: U starts at byte 60): its samples are then classified one by
+//                 one.  The samples behind the last whole unit of the frame are taken one per lane by the units that follow.
+//     edge path   one sample per lane and four samples 256 apart, at any alignment (deep formats: even).
+//   Nothing past the last sample of a frame is read.
+// gsvc_msssim       per scale one launch of k_msssim_scale (32x32 outputs of the VALID 11-tap blur per workgroup: the 42x42 inputs
+//   of both pictures staged in LDS, the five moments blurred separably with the register blocking of ssim.hip, the window taps in
+//   vector registers for the reason given there) and, between scales, one launch of k_msssim_pool (2x2 mean, a leading zero row /
+//   column for an odd side) — pooling is a kernel of its own: its windows start at -1 on an odd side and so do not tile with the
+//   blur's outputs.  A tile writes ONE float partial; k_msssim_finalize adds the partials of a (scale, plane) in a fixed order in
+//   double.  No float atomics: two runs give the same bits.
+//   The samples are CENTRED before the moments: a workgroup subtracts the value of one of its pixels (cx of x, cy of y) on the way
+//   from LDS to the registers.  Variances and the covariance do not change under a shift, mu = m + c, and E[x^2] - mu^2 no longer
+//   subtracts two numbers near 0.5 to get one near 1e-4: that cancellation is the float32 error of the tensor-expression form
+//   (DESIGN section 8e).
+#include "common.h"
+
+#include <cmath>
+#include <type_traits>
+
+namespace gsvc {
+
+// ============================================================================================================================
+// plane SSE on codes
+// ============================================================================================================================
+constexpr int SSE_PER_LANE = 4;          // units (wide) or samples (edge) per lane, 256 apart
+
+struct SseArgs {
+    const uint8_t *a, *b;
+    long long stride_a, stride_b;
+    unsigned long long *out;           // [n, 3]
+    long long samples;                 // of one frame
+    long long p0, p1;                  // first sample of the second / third plane (planar layouts)
+};
+
+__device__ __forceinline__ uint32_t sq_diff(uint32_t x, uint32_t y)
+{
+    const uint32_t d = x > y ? x - y : y - x;
+    return d * d;                       // 65535^2 = 4 294 836 225 < 2^32
+}
+
+template <int BPS>
+__device__ __forceinline__ uint32_t code_of(const uint32_t *w, int k)
+{
+    return BPS == 1 ? (w[k >> 2] >> (8 * (k & 3))) & 255u : (w[k >> 1] >> (16 * (k & 1))) & 65535u;
+}
+
+template <int BPS>
+__device__ __forceinline__ uint32_t code_at(const uint8_t *p, long long s)
+{
+    return BPS == 1 ? (uint32_t)p[s] : (uint32_t)reinterpret_cast<const uint16_t *>(p)[s];
+}
+
+__device__ __forceinline__ void add_to_plane(unsigned long long acc[3], int plane, unsigned long long v)
+{
+    acc[0] += plane == 0 ? v : 0ull;
+    acc[1] += plane == 1 ? v : 0ull;
+    acc[2] += plane == 2 ? v : 0ull;
+}
+
+template <int BPS, bool RGB, bool WIDE>
+__global__ void __launch_bounds__(256) k_frames_sse(SseArgs g)
+{
+    __shared__ unsigned long long red[4][3];
+    const uint8_t *a = g.a + (size_t)blockIdx.y * (size_t)g.stride_a;
+    const uint8_t *b = g.b + (size_t)blockIdx.y * (size_t)g.stride_b;
+    unsigned long long acc[3] = {0ull, 0ull, 0ull};
+    const long long first = (long long)blockIdx.x * (256 * SSE_PER_LANE) + threadIdx.x;
+    if (WIDE) {
+        constexpr int SPV = 16 / BPS;                    // samples of a 16-byte vector
+        constexpr int SPU = RGB ? 3 * SPV : SPV;         // samples of a unit
+        const long long units = g.samples / SPU, tail0 = units * SPU;
+#pragma unroll
+        for (int j = 0; j < SSE_PER_LANE; j++) {
+            const long long unit = first + 256 * j;
+            if (unit < units) {
+                const long long s0 = unit * SPU;
+                if (RGB) {
+                    const uint4 *pa = reinterpret_cast<const uint4 *>(a + s0), *pb = reinterpret_cast<const uint4 *>(b + s0);
+                    const uint4 a0 = pa[0], a1 = pa[1], a2 = pa[2], b0 = pb[0], b1 = pb[1], b2 = pb[2];
+                    const uint32_t wa[12] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w};
+                    const uint32_t wb[12] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w};
+                    uint32_t t[3] = {0u, 0u, 0u};        // 16 squares of at most 255^2 each: 32 bits hold them
+#pragma unroll
+                    for (int k = 0; k < 48; k++) t[k % 3] += sq_diff(code_of<1>(wa, k), code_of<1>(wb, k));
+                    acc[0] += t[0];
+                    acc[1] += t[1];
+                    acc[2] += t[2];
+                } else {
+                    const uint4 qa = *reinterpret_cast<const uint4 *>(a + s0 * BPS), qb = *reinterpret_cast<const uint4 *>(b + s0 * BPS);
+                    const uint32_t wa[4] = {qa.x, qa.y, qa.z, qa.w}, wb[4] = {qb.x, qb.y, qb.z, qb.w};
+                    const long long sl = s0 + SPV - 1;
+                    const int pf = (s0 >= g.p0) + (s0 >= g.p1), pl = (sl >= g.p0) + (sl >= g.p1);
+                    if (pf == pl) {
+                        unsigned long long t = 0ull;
+#pragma unroll
+                        for (int k = 0; k < SPV; k++) t += sq_diff(code_of<BPS>(wa, k), code_of<BPS>(wb, k));
+                        add_to_plane(acc, pf, t);
+                    } else {                              // a plane boundary inside the vector
+#pragma unroll
+                        for (int k = 0; k < SPV; k++) {
+                            const long long s = s0 + k;
+                            add_to_plane(acc, (s >= g.p0) + (s >= g.p1), sq_diff(code_of<BPS>(wa, k), code_of<BPS>(wb, k)));
+                        }
+                    }
+                }
+            } else {
+                const long long s = tail0 + (unit - units);
+                if (s < g.samples)
+                    add_to_plane(acc, RGB ? (int)((uint32_t)s % 3u) : (s >= g.p0) + (s >= g.p1), sq_diff(code_at<BPS>(a, s), code_at<BPS>(b, s)));
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < SSE_PER_LANE; j++) {
+            const long long s = first + 256 * j;
+            if (s < g.samples)
+                add_to_plane(acc, RGB ? (int)((uint32_t)s % 3u) : (s >= g.p0) + (s >= g.p1), sq_diff(code_at<BPS>(a, s), code_at<BPS>(b, s)));
+        }
+    }
+    // wave, then workgroup, then one atomic per plane
+#pragma unroll
+    for (int p = 0; p < 3; p++) {
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const uint32_t lo = __shfl_xor((uint32_t)acc[p], m, 64), hi = __shfl_xor((uint32_t)(acc[p] >> 32), m, 64);
+            acc[p] += ((unsigned long long)hi << 32) | lo;
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[wave][0] = acc[0];
+        red[wave][1] = acc[1];
+        red[wave][2] = acc[2];
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        const unsigned long long v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+        if (v) atomicAdd(&g.out[3 * (size_t)blockIdx.y + threadIdx.x], v);
+    }
+}
+
+// ============================================================================================================================
+// fused MS-SSIM
+// ============================================================================================================================
+constexpr int MS_TILE = 32;
+constexpr int MS_TAPS = 11;
+constexpr int MS_HALO = MS_TILE + MS_TAPS - 1;   // 42 staged rows / columns for 32 valid outputs
+constexpr int MS_LD = 44;                        // row stride of the staged pictures: 16-byte groups of 4 columns
+constexpr int MS_HLD = MS_TILE + 1;              // row stride of the horizontally blurred moments
+constexpr int MS_SCALES = 5;
+constexpr float MS_C1 = 0.01f * 0.01f;
+constexpr float MS_C2 = 0.03f * 0.03f;
+
+struct MsWindow {
+    float w[MS_TAPS];
+};
+
+// the taps as vector registers (see window_in_vgprs in ssim.hip: an FMA reading an SGPR issues at 4.5 cycles per wave, 2.7 without)
+struct MsWinRegs {
+    float w[MS_TAPS];
+};
+__device__ __forceinline__ MsWinRegs ms_window_in_vgprs(const MsWindow &win)
+{
+    MsWinRegs r;
+#pragma unroll
+    for (int k = 0; k < MS_TAPS; k++) asm volatile("v_mov_b32 %0, %1" : "=v"(r.w[k]) : "s"(win.w[k]));
+    return r;
+}
+
+// a sample as a float: codes are DIVIDED by the peak (an IEEE float32 division = torch's uint -> float32 -> div(peak))
+template <typename T>
+__device__ __forceinline__ float ms_sample(const T *p, size_t i, float peak)
+{
+    if (std::is_same<T, float>::value) return (float)p[i];
+    return (float)p[i] / peak;
+}
+
+struct MsPicture {
+    const void *x, *y;
+    long long x_row, x_plane, y_row, y_plane;        // pitches in samples
+    float peak;
+};
+
+__device__ __forceinline__ float ms_block_sum(float v, float *smem)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) smem[wave] = v;
+    __syncthreads();
+    return (smem[0] + smem[1]) + (smem[2] + smem[3]);
+}
+
+// one scale: partials[plane * tiles + tile] = the sum over the tile's valid outputs of the cs map (last = 0) or the SSIM map (last = 1)
+template <typename T>
+__global__ void __launch_bounds__(256) k_msssim_scale(MsWindow win_s, MsPicture pic, int H, int W, int last, float *__restrict__ partials)
+{
+    __shared__ __attribute__((aligned(16))) float sx[MS_HALO][MS_LD];
+    __shared__ __attribute__((aligned(16))) float sy[MS_HALO][MS_LD];
+    __shared__ float hb[5][MS_HALO][MS_HLD];
+    __shared__ float red[4];
+    const MsWinRegs win = ms_window_in_vgprs(win_s);
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * MS_TILE, y0 = blockIdx.y * MS_TILE;
+    const int Hv = H - (MS_TAPS - 1), Wv = W - (MS_TAPS - 1);       // the valid outputs
+    const T *px = reinterpret_cast<const T *>(pic.x) + (size_t)blockIdx.z * (size_t)pic.x_plane;
+    const T *py = reinterpret_cast<const T *>(pic.y) + (size_t)blockIdx.z * (size_t)pic.y_plane;
+    // every load of the tile is issued before the first is waited for (see k_ssim_fwd)
+    constexpr int MS_LOADS = (MS_HALO * MS_HALO + 255) / 256;
+    float xa[MS_LOADS], ya[MS_LOADS];
+#pragma unroll
+    for (int it = 0; it < MS_LOADS; it++) {
+        const int i = tid + 256 * it;
+        const int r = i / MS_HALO, c = i - r * MS_HALO;
+        const int gy = y0 + r, gx = x0 + c;
+        const bool in = i < MS_HALO * MS_HALO && gy < H && gx < W;
+        xa[it] = in ? ms_sample<T>(px, (size_t)gy * (size_t)pic.x_row + gx, pic.peak) : 0.f;
+        ya[it] = in ? ms_sample<T>(py, (size_t)gy * (size_t)pic.y_row + gx, pic.peak) : 0.f;
+    }
+#pragma unroll
+    for (int it = 0; it < MS_LOADS; it++) {
+        const int i = tid + 256 * it;
+        const int r = i / MS_HALO, c = i - r * MS_HALO;
+        if (i < MS_HALO * MS_HALO) {
+            sx[r][c] = xa[it];
+            sy[r][c] = ya[it];
+        }
+    }
+    if (tid < 2 * MS_HALO) {      // the two pad columns the 16-byte reads touch (never used in arithmetic): keep them finite
+        sx[tid >> 1][MS_HALO + (tid & 1)] = 0.f;
+        sy[tid >> 1][MS_HALO + (tid & 1)] = 0.f;
+    }
+    __syncthreads();
+    // the centre of the staged part of the picture: one pixel of each picture, the same for the whole workgroup
+    const int rc = min(MS_HALO / 2, H - 1 - y0), cc = min(MS_HALO / 2, W - 1 - x0);
+    const float cx = sx[rc][cc], cy = sy[rc][cc];
+    // horizontal pass: group g = (row r, outputs 4 cg .. 4 cg + 3 <- columns 4 cg .. 4 cg + 13)
+    for (int g = tid; g < MS_HALO * (MS_TILE / 4); g += 256) {
+        const int r = g >> 3, c0 = 4 * (g & 7);
+        if (y0 + r >= H || x0 + c0 >= Wv) continue;      // a row below the picture, outputs right of the last valid one
+        float xv[16], yv[16];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const float4 a = *reinterpret_cast<const float4 *>(&sx[r][c0 + 4 * q]);
+            const float4 b = *reinterpret_cast<const float4 *>(&sy[r][c0 + 4 * q]);
+            xv[4 * q] = a.x - cx; xv[4 * q + 1] = a.y - cx; xv[4 * q + 2] = a.z - cx; xv[4 * q + 3] = a.w - cx;
+            yv[4 * q] = b.x - cy; yv[4 * q + 1] = b.y - cy; yv[4 * q + 2] = b.z - cy; yv[4 * q + 3] = b.w - cy;
+        }
+        float xx[14], yy[14], xy[14];
+#pragma unroll
+        for (int k = 0; k < 14; k++) { xx[k] = xv[k] * xv[k]; yy[k] = yv[k] * yv[k]; xy[k] = xv[k] * yv[k]; }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
+#pragma unroll
+            for (int k = 0; k < MS_TAPS; k++) {
+                const float w = win.w[k];
+                a0 = fmaf(w, xv[j + k], a0); a1 = fmaf(w, yv[j + k], a1); a2 = fmaf(w, xx[j + k], a2);
+                a3 = fmaf(w, yy[j + k], a3); a4 = fmaf(w, xy[j + k], a4);
+            }
+            hb[0][r][c0 + j] = a0; hb[1][r][c0 + j] = a1; hb[2][r][c0 + j] = a2; hb[3][r][c0 + j] = a3; hb[4][r][c0 + j] = a4;
+        }
+    }
+    __syncthreads();
+    // vertical pass: thread = (column lx, outputs 4 gq .. 4 gq + 3 <- rows 4 gq .. 4 gq + 13)
+    const int lx = tid & 31, gq = tid >> 5;
+    const int gx = x0 + lx;
+    float sum = 0.f;
+    if (gx < Wv && y0 + 4 * gq < Hv) {
+        float mom[5][4];
+#pragma unroll
+        for (int m = 0; m < 5; m++) {
+            float v[14];
+#pragma unroll
+            for (int k = 0; k < 14; k++) v[k] = hb[m][4 * gq + k][lx];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                float a = 0.f;
+#pragma unroll
+                for (int k = 0; k < MS_TAPS; k++) a = fmaf(win.w[k], v[j + k], a);
+                mom[m][j] = a;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            if (y0 + 4 * gq + j < Hv) {          // (rows of hb below the picture were not written: their outputs are not taken)
+                const float m1 = mom[0][j], m2 = mom[1][j];
+                const float s1 = mom[2][j] - m1 * m1, s2 = mom[3][j] - m2 * m2, s12 = mom[4][j] - m1 * m2;
+                const float cs = (2.f * s12 + MS_C2) / (s1 + s2 + MS_C2);
+                const float mu1 = m1 + cx, mu2 = m2 + cy;
+                const float lum = (2.f * mu1 * mu2 + MS_C1) / (mu1 * mu1 + mu2 * mu2 + MS_C1);
+                sum += last ? lum * cs : cs;
+            }
+        }
+    }
+    const float total = ms_block_sum(sum, red);
+    if (tid == 0) partials[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = total;
+}
+
+// 2x2 mean of both pictures: out(i, j) = (in(2i - ph, 2j - pw) + in(2i - ph, 2j - pw + 1) + in(2i - ph + 1, ..) + ..) / 4 with ph = H % 2,
+// pw = W % 2 and index -1 read as zero (the padded cell counts in the divisor); the sum runs row by row as torch's avg_pool2d does
+template <typename T>
+__global__ void __launch_bounds__(256) k_msssim_pool(MsPicture pic, int H, int W, int H2, int W2, float *__restrict__ out_x,
+                                                     float *__restrict__ out_y)
+{
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o >= H2 * W2) return;
+    const int i = o / W2, j = o - i * W2;
+    const int r0 = 2 * i - (H & 1), c0 = 2 * j - (W & 1);
+    const T *px = reinterpret_cast<const T *>(pic.x) + (size_t)blockIdx.y * (size_t)pic.x_plane;
+    const T *py = reinterpret_cast<const T *>(pic.y) + (size_t)blockIdx.y * (size_t)pic.y_plane;
+    float sx = 0.f, sy = 0.f;
+#pragma unroll
+    for (int dr = 0; dr < 2; dr++)
+#pragma unroll
+        for (int dc = 0; dc < 2; dc++) {
+            const int r = r0 + dr, c = c0 + dc;
+            const bool in = r >= 0 && c >= 0;            // (r <= H - 1 and c <= W - 1 by construction)
+            sx += in ? ms_sample<T>(px, (size_t)r * (size_t)pic.x_row + c, pic.peak) : 0.f;
+            sy += in ? ms_sample<T>(py, (size_t)r * (size_t)pic.y_row + c, pic.peak) : 0.f;
+        }
+    const size_t at = (size_t)blockIdx.y * ((size_t)H2 * W2) + o;
+    out_x[at] = 0.25f * sx;
+    out_y[at] = 0.25f * sy;
+}
+
+struct MsFinalize {
+    long long offset[MS_SCALES];       // first partial of a scale
+    int tiles[MS_SCALES];              // tiles of one plane
+    double inv_count[MS_SCALES];       // 1 / valid outputs of one plane
+};
+
+// out[scale, plane] = (the partials of the plane's tiles, added in a fixed order in double) / outputs: lane t takes the tiles
+// t, t + 256, ... in rising order, then a tree over the 256 lanes whose shape does not depend on anything
+__global__ void __launch_bounds__(256) k_msssim_finalize(MsFinalize f, const float *__restrict__ partials, int P, double *__restrict__ out)
+{
+    __shared__ double red[256];
+    const int plane = blockIdx.x, scale = blockIdx.y, n = f.tiles[scale];
+    const float *p = partials + f.offset[scale] + (size_t)plane * n;
+    double a = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) a += (double)p[i];
+    red[threadIdx.x] = a;
+    __syncthreads();
+    for (int m = 128; m >= 1; m >>= 1) {
+        if ((int)threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[(size_t)scale * P + plane] = red[0] * f.inv_count[scale];
+}
+
+static MsWindow ms_make_window()
+{
+    // exp(-(i - 5)^2 / (2 * 1.5^2)) normalised, in double, each tap rounded once to float
+    MsWindow w;
+    double g[MS_TAPS], s = 0.0;
+    for (int i = 0; i < MS_TAPS; i++) {
+        g[i] = std::exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5));
+        s += g[i];
+    }
+    for (int i = 0; i < MS_TAPS; i++) w.w[i] = (float)(g[i] / s);
+    return w;
+}
+
+struct MsLayout {
+    int h[MS_SCALES], w[MS_SCALES], tx[MS_SCALES], ty[MS_SCALES];
+    int64_t pyr[MS_SCALES];            // byte offset of scale s's pooled x pictures (s >= 1); y follows x
+    int64_t partials;                  // byte offset of the partials
+    int64_t part_off[MS_SCALES];       // first partial (in floats) of a scale
+    int64_t bytes;
+};
+
+static MsLayout ms_layout(int32_t P, int32_t H, int32_t W)
+{
+    MsLayout L;
+    int64_t at = 0, parts = 0;
+    int h = H, w = W;
+    for (int s = 0; s < MS_SCALES; s++) {
+        L.h[s] = h;
+        L.w[s] = w;
+        L.tx[s] = (w - (MS_TAPS - 1) + MS_TILE - 1) / MS_TILE;
+        L.ty[s] = (h - (MS_TAPS - 1) + MS_TILE - 1) / MS_TILE;
+        L.pyr[s] = at;
+        if (s > 0) at += (int64_t)align_up((uint64_t)2 * P * h * w * sizeof(float), 256);
+        L.part_off[s] = parts;
+        parts += (int64_t)P * L.tx[s] * L.ty[s];
+        h = (h + 1) / 2;
+        w = (w + 1) / 2;
+    }
+    L.partials = at;
+    L.bytes = at + (int64_t)align_up((uint64_t)parts * sizeof(float), 256);
+    return L;
+}
+
+static bool ms_shape_ok(int32_t P, int32_t H, int32_t W)
+{
+    return P >= 1 && P <= 65535 && H > 160 && W > 160 && H <= 32768 && W <= 32768;
+}
+
+template <typename T>
+static void ms_launch_first(const MsWindow &win, const MsPicture &pic, const MsLayout &L, int32_t P, float *pyr1, float *partials,
+                            hipStream_t s)
+{
+    {
+        ProfScope _p("k_msssim_scale", s);
+        hipLaunchKernelGGL(k_msssim_scale<T>, dim3(L.tx[0], L.ty[0], P), dim3(256), 0, s, win, pic, L.h[0], L.w[0], 0, partials);
+    }
+    {
+        ProfScope _p("k_msssim_pool", s);
+        const int outs = L.h[1] * L.w[1];
+        hipLaunchKernelGGL(k_msssim_pool<T>, dim3((outs + 255) / 256, P), dim3(256), 0, s, pic, L.h[0], L.w[0], L.h[1], L.w[1], pyr1,
+                           pyr1 + (size_t)P * outs);
+    }
+}
+
+}  // namespace gsvc
+
+using namespace gsvc;
+
+extern "C" int gsvc_frames_sse(const uint8_t *a, int64_t a_stride, const uint8_t *b, int64_t b_stride, int32_t n, int32_t H, int32_t W,
+                               int32_t layout, int32_t depth, uint64_t *out, void *stream)
+{
+    GSVC_REQUIRE(a && b && out, "frames_sse: NULL pointer");
+    GSVC_REQUIRE(n >= 1 && n <= 65535, "frames_sse: n must be 1 .. 65535 (got %d)", (int)n);
+    GSVC_REQUIRE(layout == GSVC_FRAMES_RGB24 || layout == GSVC_FRAMES_YUV444P || layout == GSVC_FRAMES_YUV420P,
+                 "frames_sse: unknown layout %d", (int)layout);
+    GSVC_REQUIRE(depth >= 8 && depth <= 16, "frames_sse: depth must be 8 .. 16 (got %d)", (int)depth);
+    GSVC_REQUIRE(layout != GSVC_FRAMES_RGB24 || depth == 8, "frames_sse: rgb24 frames are 8-bit only");
+    GSVC_REQUIRE(H >= 1 && W >= 1 && H <= 32768 && W <= 32768, "frames_sse: image size must be 1 .. 32768 (got %d x %d)", (int)H, (int)W);
+    GSVC_REQUIRE(layout != GSVC_FRAMES_YUV420P || (H % 2 == 0 && W % 2 == 0), "frames_sse: yuv420p needs even H and W (got %d x %d)",
+                 (int)H, (int)W);
+    const int64_t bytes = gsvc_frames_bytes(H, W, layout, depth);
+    GSVC_REQUIRE(a_stride >= bytes && b_stride >= bytes, "frames_sse: stride %lld / %lld is shorter than a frame (%lld bytes)",
+                 (long long)a_stride, (long long)b_stride, (long long)bytes);
+    const bool deep = depth > 8;
+    if (deep) {
+        GSVC_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 1) == 0,
+                     "frames_sse: a frame base is not 2-byte aligned");
+        GSVC_REQUIRE(((a_stride | b_stride) & 1) == 0, "frames_sse: stride %lld / %lld is not a multiple of 2", (long long)a_stride,
+                     (long long)b_stride);
+    }
+    GSVC_REQUIRE((reinterpret_cast<uintptr_t>(out) & 7) == 0, "frames_sse: out is not 8-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (hipMemsetAsync(out, 0, (size_t)n * 3 * sizeof(uint64_t), s) != hipSuccess) {
+        set_error("frames_sse: hipMemsetAsync failed");
+        return GSVC_E_LAUNCH;
+    }
+    SseArgs g;
+    g.a = a;
+    g.b = b;
+    g.stride_a = a_stride;
+    g.stride_b = b_stride;
+    g.out = reinterpret_cast<unsigned long long *>(out);
+    const int64_t px = (int64_t)H * W, chroma = layout == GSVC_FRAMES_YUV420P ? px / 4 : px;
+    g.samples = bytes / (deep ? 2 : 1);
+    g.p0 = px;
+    g.p1 = px + chroma;
+    uintptr_t align = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b);
+    if (n > 1) align |= (uintptr_t)a_stride | (uintptr_t)b_stride;
+    const bool wide = (align & 15) == 0;
+    const bool rgb = layout == GSVC_FRAMES_RGB24;
+    int64_t units = g.samples;
+    if (wide) {
+        const int64_t spu = rgb ? 48 : (deep ? 8 : 16);
+        units = g.samples / spu + g.samples % spu;          // whole units, then the samples behind them one by one
+    }
+    const int64_t per_block = 256 * SSE_PER_LANE;
+    const dim3 grid((unsigned)((units + per_block - 1) / per_block), (unsigned)n), block(256);
+    ProfScope _p("k_frames_sse", s);
+    if (rgb) {
+        if (wide) hipLaunchKernelGGL((k_frames_sse<1, true, true>), grid, block, 0, s, g);
+        else hipLaunchKernelGGL((k_frames_sse<1, true, false>), grid, block, 0, s, g);
+    } else if (!deep) {
+        if (wide) hipLaunchKernelGGL((k_frames_sse<1, false, true>), grid, block, 0, s, g);
+        else hipLaunchKernelGGL((k_frames_sse<1, false, false>), grid, block, 0, s, g);
+    } else {
+        if (wide) hipLaunchKernelGGL((k_frames_sse<2, false, true>), grid, block, 0, s, g);
+        else hipLaunchKernelGGL((k_frames_sse<2, false, false>), grid, block, 0, s, g);
+    }
+    return check_launch("frames_sse");
+}
+
+extern "C" int64_t gsvc_msssim_workspace_bytes(int32_t P, int32_t H, int32_t W)
+{
+    if (!ms_shape_ok(P, H, W)) return -1;
+    return ms_layout(P, H, W).bytes;
+}
+
+extern "C" int gsvc_msssim(const void *x, int64_t x_row_pitch, int64_t x_plane_pitch, const void *y, int64_t y_row_pitch,
+                           int64_t y_plane_pitch, int32_t P, int32_t H, int32_t W, int32_t sample_type, float peak, void *workspace,
+                           double *out, void *stream)
+{
+    GSVC_REQUIRE(x && y && workspace && out, "msssim: NULL pointer");
+    GSVC_REQUIRE(P >= 1 && P <= 65535, "msssim: P must be 1 .. 65535 (got %d)", (int)P);
+    GSVC_REQUIRE(H >= 1 && W >= 1 && H <= 32768 && W <= 32768, "msssim: image size must be 1 .. 32768 (got %d x %d)", (int)H, (int)W);
+    GSVC_REQUIRE(H > 160 && W > 160, "msssim: image sides must exceed 160 pixels for 5 scales (got %d x %d)", (int)H, (int)W);
+    GSVC_REQUIRE(sample_type == GSVC_SAMPLE_F32 || sample_type == GSVC_SAMPLE_U8 || sample_type == GSVC_SAMPLE_U16,
+                 "msssim: unknown sample type %d", (int)sample_type);
+    GSVC_REQUIRE(x_row_pitch >= W && y_row_pitch >= W, "msssim: row pitch %lld / %lld is shorter than a row (%d samples)",
+                 (long long)x_row_pitch, (long long)y_row_pitch, (int)W);
+    const int64_t need_x = (int64_t)(H - 1) * x_row_pitch + W, need_y = (int64_t)(H - 1) * y_row_pitch + W;
+    GSVC_REQUIRE(P == 1 || (x_plane_pitch >= need_x && y_plane_pitch >= need_y),
+                 "msssim: plane pitch %lld / %lld is shorter than a plane (%lld / %lld samples)", (long long)x_plane_pitch,
+                 (long long)y_plane_pitch, (long long)need_x, (long long)need_y);
+    const uintptr_t bases = reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y);
+    const uintptr_t mask = sample_type == GSVC_SAMPLE_F32 ? 3 : (sample_type == GSVC_SAMPLE_U16 ? 1 : 0);
+    GSVC_REQUIRE((bases & mask) == 0, "msssim: a picture base is not aligned to its sample type");
+    GSVC_REQUIRE(sample_type == GSVC_SAMPLE_F32 || peak > 0.f, "msssim: the peak of codes must be positive");
+    GSVC_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0,
+                 "msssim: the workspace must be 16-byte and out 8-byte aligned");
+    const MsLayout L = ms_layout(P, H, W);
+    static const MsWindow win = ms_make_window();
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t *ws = reinterpret_cast<uint8_t *>(workspace);
+    float *partials = reinterpret_cast<float *>(ws + L.partials);
+    MsPicture pic;
+    pic.x = x;
+    pic.y = y;
+    pic.x_row = x_row_pitch;
+    pic.y_row = y_row_pitch;
+    pic.x_plane = x_plane_pitch;
+    pic.y_plane = y_plane_pitch;
+    pic.peak = sample_type == GSVC_SAMPLE_F32 ? 1.f : peak;
+    float *pyr1 = reinterpret_cast<float *>(ws + L.pyr[1]);
+    if (sample_type == GSVC_SAMPLE_F32) ms_launch_first<float>(win, pic, L, P, pyr1, partials, s);
+    else if (sample_type == GSVC_SAMPLE_U8) ms_launch_first<uint8_t>(win, pic, L, P, pyr1, partials, s);
+    else ms_launch_first<uint16_t>(win, pic, L, P, pyr1, partials, s);
+    for (int k = 1; k < MS_SCALES; k++) {
+        const int h = L.h[k], w = L.w[k];
+        float *lx = reinterpret_cast<float *>(ws + L.pyr[k]);
+        MsPicture lv;
+        lv.x = lx;
+        lv.y = lx + (size_t)P * h * w;
+        lv.x_row = lv.y_row = w;
+        lv.x_plane = lv.y_plane = (long long)h * w;
+        lv.peak = 1.f;
+        {
+            ProfScope _p("k_msssim_scale", s);
+            hipLaunchKernelGGL(k_msssim_scale<float>, dim3(L.tx[k], L.ty[k], P), dim3(256), 0, s, win, lv, h, w,
+                               k == MS_SCALES - 1 ? 1 : 0, partials + L.part_off[k]);
+        }
+        if (k + 1 < MS_SCALES) {
+            ProfScope _p("k_msssim_pool", s);
+            const int outs = L.h[k + 1] * L.w[k + 1];
+            float *nx = reinterpret_cast<float *>(ws + L.pyr[k + 1]);
+            hipLaunchKernelGGL(k_msssim_pool<float>, dim3((outs + 255) / 256, P), dim3(256), 0, s, lv, h, w, L.h[k + 1], L.w[k + 1], nx,
+                               nx + (size_t)P * outs);
+        }
+    }
+    MsFinalize f;
+    for (int k = 0; k < MS_SCALES; k++) {
+        f.offset[k] = L.part_off[k];
+        f.tiles[k] = L.tx[k] * L.ty[k];
+        f.inv_count[k] = 1.0 / ((double)(L.h[k] - (MS_TAPS - 1)) * (double)(L.w[k] - (MS_TAPS - 1)));
+    }
+    {
+        ProfScope _p("k_msssim_finalize", s);
+        hipLaunchKernelGGL(k_msssim_finalize, dim3(P, MS_SCALES), dim3(256), 0, s, f, partials, P, out);
+    }
+    return check_launch("msssim");
+}

@@ -19,16 +19,29 @@ from .ortho_gaussian_renderer import render_frames
 
 
 @torch.no_grad()
-def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_fn=None, eight_bit: bool = False, delivered=None) -> dict:
+def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_fn=None, eight_bit: bool = False, delivered=None,
+             code_metrics: bool = False, source_u8=None, msssim: str = "torch") -> dict:
     """Mean L1 / PSNR / SSIM / MS-SSIM (MS-SSIM only for frames at least 160 pixels high and large enough for 5 scales) of the
     rendered two-view frames, clamped to [0, 1], against ``dataset[i].image``; ``fps`` counts the whole loop's wall time,
     metrics excluded.  ``eight_bit=True``: the metrics are taken on what the decoder delivers — the frames quantised to 8 bits
     (``frames_out.frames_to_u8``: rgb24, truncating, as the reference's PNGs) / 255 — as a codec's PSNR is, and the result says so
     (``"eight_bit": True``).  ``delivered=FrameFormat(...)``: the metrics are taken on ``frames_out.delivered_images`` of the frames —
     what a viewer of frames delivered in that format sees, at its depth and chroma subsampling — and the result records the format
-    (``"delivered": fmt.name``).  Giving both is a ValueError."""
+    (``"delivered": fmt.name``).  Giving both is a ValueError.
+    ``code_metrics=True`` (needs ``delivered=fmt``) adds what a video codec is judged by, taken on the sample codes
+    (``metrics.code_metrics``) between ``frames_to_u8(rendered, fmt)`` and the source's frames in ``fmt`` — ``source_u8`` when given (uint8
+    ``[frames, frame_bytes]``, tensor or array, in the order of ``frame_ids``: for example a file's own bytes from ``open_video``), else
+    ``frames_to_u8(gt, fmt)``: ``psnr_y``, ``psnr_u``, ``psnr_v``, ``psnr_avg``, ``psnr_611`` (``yuv420p``) and ``msssim_y`` (frames with both sides above
+    160 pixels), each the mean over the frames.  ``msssim="fused"``: the ``msssim`` entry comes from ``metrics.ms_ssim_fused`` instead of
+    the tensor expressions."""
     if eight_bit and delivered is not None:
         raise ValueError("evaluate: eight_bit=True and delivered= both say what is delivered; give one")
+    if code_metrics and delivered is None:
+        raise ValueError("evaluate: code_metrics=True compares frames of codes; say which with delivered=FrameFormat(...)")
+    if source_u8 is not None and not code_metrics:
+        raise ValueError("evaluate: source_u8 is the source of code_metrics=True")
+    if msssim not in ("torch", "fused"):
+        raise ValueError(f"evaluate: msssim must be 'torch' or 'fused' (got {msssim!r})")
     ids = list(range(dataset.len_z_frames)) if frame_ids is None else list(frame_ids)
     frames = [dataset[i] for i in ids]
     for _ in render_frames(frames[:min(len(frames), batch)], pc, pipe, bg_color, batch=batch):      # warm-up, as the reference does
@@ -42,18 +55,26 @@ def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_
         from .frames_out import FrameFormat, frames_to_u8, rgb24_to_image
         H, W = images[0].shape[1:]
         images = [rgb24_to_image(u8, H, W) for u8 in frames_to_u8(images, FrameFormat("rgb24", rounding="trunc"))]
+    rendered = images
     if delivered is not None and images:
         from .frames_out import delivered_images
         images = list(delivered_images(images, delivered).unbind(0))
     sums = {"l1": 0.0, "psnr": 0.0, "ssim": 0.0, "msssim": 0.0, "lpips": 0.0}
     n_ms = 0
+    gts = []
     for fr, img in zip(frames, images):
         gt = torch.clamp(fr.image.to(img.device), 0.0, 1.0).permute(0, 2, 1).contiguous()
+        if code_metrics and source_u8 is None:
+            gts.append(gt)
         sums["l1"] += float(l1_loss_func(img, gt).mean())
         sums["psnr"] += float(psnr_func(img, gt))
         sums["ssim"] += float(ssim_func(img, gt).mean())
         if min(img.shape[-2:]) > 160:
-            sums["msssim"] += float(msssim_fn(img.unsqueeze(0), gt.unsqueeze(0)))
+            if msssim == "fused":
+                from .metrics import ms_ssim_fused
+                sums["msssim"] += float(ms_ssim_fused(img.float().detach(), gt.detach()))
+            else:
+                sums["msssim"] += float(msssim_fn(img.unsqueeze(0), gt.unsqueeze(0)))
             n_ms += 1
         if lpips_fn is not None:
             sums["lpips"] += float(lpips_fn(img, gt, normalize=True))
@@ -64,7 +85,32 @@ def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_
         out["eight_bit"] = True
     if delivered is not None:
         out["delivered"] = delivered.name
+    if code_metrics and rendered:
+        out.update(_code_metrics_means(rendered, gts, source_u8, delivered, batch))
     return out
+
+
+def _code_metrics_means(rendered, gts, source_u8, fmt, batch):
+    """Means over the frames of ``metrics.code_metrics`` between the rendered frames' codes and the source's (see ``evaluate``)."""
+    from .frames_out import frame_bytes, frames_to_u8
+    from .metrics import code_metrics
+    H, W = (int(v) for v in rendered[0].shape[1:])
+    nbytes, dev = frame_bytes(H, W, fmt), rendered[0].device
+    if source_u8 is not None:
+        import numpy as np
+        src = source_u8 if isinstance(source_u8, torch.Tensor) else torch.from_numpy(np.array(source_u8))      # (a copy: a memory map may be read-only)
+        if src.dtype != torch.uint8 or src.dim() != 2 or src.shape[0] != len(rendered) or src.shape[1] < nbytes:
+            raise ValueError(f"evaluate: source_u8 must be uint8 [{len(rendered)}, >= {nbytes}] (got {src.dtype} {tuple(src.shape)})")
+        src = src.to(dev)
+    sums = {}
+    step = max(int(batch), 1)
+    for i in range(0, len(rendered), step):
+        dec = frames_to_u8(rendered[i:i + step], fmt)
+        ref = src[i:i + step] if source_u8 is not None else frames_to_u8(gts[i:i + step], fmt)
+        for k, v in code_metrics(dec, ref, H, W, fmt).items():
+            if k not in ("peak", "sse"):
+                sums[k] = sums.get(k, 0.0) + float(v.sum())
+    return {k: v / len(rendered) for k, v in sums.items()}
 
 
 def _optimizer_state(optimizer):

@@ -975,6 +975,46 @@ int gsvc_frames_to_u16(const float *const *images_host, int32_t n, int32_t H, in
 int gsvc_frames_from_u16(const uint8_t *in, int64_t in_stride, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t matrix,
                          int32_t range, int32_t chroma, int32_t depth, float *const *images_host, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * [INTERNAL] Video metrics on the codes (csrc/metrics.hip).
+ *
+ * gsvc_frames_sse: out[k, p] (uint64 [n, 3], 8-byte aligned) = the sum over the samples of plane p of frame k of (a - b)^2, a and b the
+ * sample codes of the two frame buffers (frame k of a starts at a + k * a_stride, of b at b + k * b_stride), in exact integer
+ * arithmetic: one squared difference is below 2^32, every sum is 64-bit.  The same bits in every run.
+ *   layout      GSVC_FRAMES_RGB24 (depth 8 only): p = R, G, B, the sample index mod 3.  GSVC_FRAMES_YUV444P / _YUV420P: p = Y, U, V, the
+ *               planes one after the other (H W samples, then twice H W, or twice H W / 4 for 4:2:0).
+ *   depth       8: one byte per sample.  9 .. 16: one little-endian 16-bit word per sample, compared as it is (nothing is masked).
+ * Refused with an error before any launch: an unknown layout, a depth outside 8 .. 16, rgb24 deeper than 8, an odd H or W for 4:2:0,
+ * a stride below the frame's bytes (gsvc_frames_bytes), an odd base or stride for a deep format, a NULL pointer, n < 1.  Bytes
+ * between frames are not read.  The call zeroes out on the stream and does not synchronise.
+ *
+ * gsvc_msssim: the per-scale means of multi-scale SSIM (Wang et al. 2003) of P pairs of planes of H x W; x, y: plane p starts at
+ * base + p * plane_pitch samples, its row r at + r * row_pitch samples.
+ *   samples     GSVC_SAMPLE_F32: v = the float.  GSVC_SAMPLE_U8 / _U16 (little-endian words): v = code / peak, one IEEE float32
+ *               division (= torch's uint -> float32 -> div(peak)); peak = 2^d - 1 puts a d-bit code on [0, 1].
+ *   window      g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)) / sum, 11 taps, applied along the rows and along the columns WITHOUT padding:
+ *               a scale of h x w has (h - 10) (w - 10) outputs.  For an output, with mu1 = g*x, mu2 = g*y (* = the 2-D window sum),
+ *                 s1 = g*x^2 - mu1^2, s2 = g*y^2 - mu2^2, s12 = g*(x y) - mu1 mu2,     C1 = 0.01^2, C2 = 0.03^2 (data range 1)
+ *                 cs = (2 s12 + C2) / (s1 + s2 + C2),   ssim = cs (2 mu1 mu2 + C1) / (mu1^2 + mu2^2 + C1)
+ *               (the kernel takes the moments of x - cx, y - cy, cx and cy one pixel of the workgroup's tile: the same real numbers).
+ *   scales      5; scale k + 1 is the 2x2 mean of scale k, h' = (h + 1) / 2: an odd side gets ONE leading zero row / column — its first
+ *               window covers the indices -1 and 0 — and the divisor stays 4.
+ *   out         double [5, P]: out[k, p] = the mean of cs over the outputs of scale k for k = 0 .. 3 and of ssim for k = 4, not
+ *               clipped.  (MS-SSIM = the product over k of max(out[k], 0)^w[k], w = 0.0448, 0.2856, 0.3001, 0.2363, 0.1333: the
+ *               caller's, in float64.)  A tile of 32 x 32 outputs sums in float32; the tiles of a (scale, plane) are added in a fixed
+ *               order in double: the same bits in every run.
+ * workspace: gsvc_msssim_workspace_bytes(P, H, W) bytes (the pooled pictures of both inputs and the tile sums; < 0 for a shape
+ * gsvc_msssim refuses), 16-byte aligned, the caller's.  Refused with an error before any launch: a side of 160 or less (the last
+ * scale would have fewer than 11 rows or columns), P outside 1 .. 65535, an unknown sample type, a row pitch below W, a plane pitch
+ * below (H - 1) row_pitch + W (P > 1), a base not aligned to its sample type, a NULL pointer.  Nothing synchronises.
+ * ---------------------------------------------------------------------------------------------------- */
+enum { GSVC_SAMPLE_F32 = 0, GSVC_SAMPLE_U8 = 1, GSVC_SAMPLE_U16 = 2 };
+int gsvc_frames_sse(const uint8_t *a, int64_t a_stride, const uint8_t *b, int64_t b_stride, int32_t n, int32_t H, int32_t W,
+                    int32_t layout, int32_t depth, uint64_t *out, void *stream);
+int64_t gsvc_msssim_workspace_bytes(int32_t P, int32_t H, int32_t W);
+int gsvc_msssim(const void *x, int64_t x_row_pitch, int64_t x_plane_pitch, const void *y, int64_t y_row_pitch, int64_t y_plane_pitch,
+                int32_t P, int32_t H, int32_t W, int32_t sample_type, float peak, void *workspace, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,9 @@ def main(argv=None):
                          "(8-bit unless --decoded-format says otherwise)")
     ap.add_argument("--decoded-format", default=None, metavar="LAYOUT[,MATRIX[,RANGE]]",
                     help="what --write-decoded writes, e.g. yuv420p10le or yuv444p12le,bt709,full (default: what the path's extension means, 8-bit)")
+    ap.add_argument("--code-metrics", action="store_true",
+                    help="also report PSNR-Y / -U / -V, their average and 6:1:1 mean, and MS-SSIM-Y of the decoded 8-bit-MLP model on the sample codes "
+                         "of --decoded-format (default yuv420p) against the source's frames in that format: log['decoded_code_metrics']")
     ap.add_argument("--video", default=None, metavar="PATH",
                     help="fit this 8-bit or 10 / 12 / 16-bit video file (.y4m, or raw .yuv / .rgb with --video-size) instead of the synthetic frames")
     ap.add_argument("--video-size", default=None, metavar="WxH", help="frame size of a raw --video file")
@@ -265,6 +268,11 @@ def main(argv=None):
             lp = lpips_fn_from(args.lpips_weights, lin_weights_path=args.lpips_lin_weights, device=dev)
         ev = evaluate(dec_q, cube, pipe, bg, frame_ids=eval_ids, lpips_fn=lp)
         log["decoded_8bit_mlp"] = ev
+        if args.code_metrics:
+            from gsvc_amd.frames_out import FrameFormat
+            cfmt = _frame_format(args.decoded_format) if args.decoded_format else FrameFormat("yuv420p")
+            both = evaluate(dec_q, cube, pipe, bg, frame_ids=eval_ids, delivered=cfmt, code_metrics=True)
+            log["decoded_code_metrics"] = dict({k: v for k, v in both.items() if k not in ev or k == "delivered"}, format=cfmt.name)
         if args.write_decoded:
             from gsvc_amd.frames_out import open_sink, write_video
             sink, fmt = open_sink(args.write_decoded, W, H, fmt=_frame_format(args.decoded_format) if args.decoded_format else None)
