@@ -699,13 +699,21 @@ extern "C" int gsvc_linear_wgrad_reduce_many(const gsvc_wgrad_reduce_job *jobs, 
 {
     GSVC_REQUIRE(jobs && n_jobs >= 0, "linear_wgrad_reduce_many: bad arguments");
     hipStream_t s = (hipStream_t)stream;
+    // every job is looked at before the first launch: a refusal leaves all outputs as they were
+    for (int j = 0; j < n_jobs; j++) {
+        const gsvc_wgrad_reduce_job &q = jobs[j];
+        GSVC_REQUIRE(q.partial && q.dW && q.slots > 0 && q.N > 0 && q.K > 0, "linear_wgrad_reduce_many: bad job %d", j);
+        if (q.N > LIN_NT_MAX * 16 || q.K > LIN_NT_MAX * 16) {
+            set_error("linear_wgrad_reduce_many: N=%d / K=%d exceed %d", q.N, q.K, LIN_NT_MAX * 16);
+            return GSVC_E_UNSUPPORTED;
+        }
+    }
     for (int j0 = 0; j0 < n_jobs; j0 += WGR_JOBS) {
         WgReduceJobs t;
         const int nj = n_jobs - j0 < WGR_JOBS ? n_jobs - j0 : WGR_JOBS;
         int blocks = 0;
         for (int j = 0; j < nj; j++) {
             const gsvc_wgrad_reduce_job &q = jobs[j0 + j];
-            GSVC_REQUIRE(q.partial && q.dW && q.slots > 0 && q.N > 0 && q.K > 0, "linear_wgrad_reduce_many: bad job %d", j0 + j);
             t.part[j] = q.partial; t.dW[j] = q.dW; t.db[j] = q.db; t.slots[j] = q.slots;
             t.nk[j] = q.N * q.K; t.n[j] = t.nk[j] + (q.db ? q.N : 0);
             t.first_block[j] = blocks;

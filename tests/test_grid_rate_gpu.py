@@ -665,7 +665,9 @@ def test_tables_binarised_in_one_launch_with_count_bits():
                                     (4100, 17, 23), (4101, 81, 49), (4097, 33, 129), (4098, 130, 82)])
 def test_mfma_linear_matches_torch(M, K, N):
     """csrc/linear.hip (fp32 MFMA, tall-skinny) vs torch.nn.functional.linear in fp32 on the same GPU: fp32
-    products and accumulation on both sides, only the summation order differs -> 1e-5 relative to the row scale."""
+    products and accumulation on both sides, only the summation order differs -> 1e-5 relative to the row scale.
+    This goes through the modules (4096 rows and more); the kernels themselves, from one row on, per element against float64 and
+    bit for bit on integer inputs, are checked in tests/test_linear_kernels_gpu.py."""
     import torch.nn.functional as F
     from gsvc_amd.model import Linear
     gen = torch.Generator().manual_seed(M + K + N)
