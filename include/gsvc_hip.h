@@ -1015,6 +1015,56 @@ int64_t gsvc_msssim_workspace_bytes(int32_t P, int32_t H, int32_t W);
 int gsvc_msssim(const void *x, int64_t x_row_pitch, int64_t x_plane_pitch, const void *y, int64_t y_row_pitch, int64_t y_plane_pitch,
                 int32_t P, int32_t H, int32_t W, int32_t sample_type, float peak, void *workspace, double *out, void *stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Dense optical flow of adjacent frames (csrc/flow.hip): coarse-to-fine Horn-Schunck with warping.  No weights, stencils only: the
+ * same bits in every run, for every batch size and launch geometry.
+ *
+ * gsvc_flow_estimate: pair k reads the luma planes luma0 + k * plane_pitch and luma1 + k * plane_pitch (float32 [H, W] in [0, 1],
+ * rows contiguous; the T - 1 pairs of T resident frames are one call with luma1 = luma0 + plane_pitch) and writes flow_out[k], float32
+ * [2, H, W]: flow[0] = the x displacement, flow[1] = the y displacement in pixels at the pixel of the first frame,
+ *   I0(x, y) ~ I1(x + flow[0], y + flow[1])
+ * (what gsvc_optical_forward reads).
+ *   pyramid     P[0] = blur(luma), P[l + 1] = blur(pool(P[l])) while min(h, w) / 2 >= min_side and fewer than max_levels levels exist.
+ *               blur: the 5-tap binomial (1 4 6 4 1) / 16 down the columns, then along the rows, borders replicated.  pool: the 2 x 2
+ *               mean, (h, w) -> (h / 2, w / 2); an odd last row or column is dropped.
+ *   bilinear    bil(a, x, y) of an h x w plane: x clamped to [0, w - 1], x0 = min(floor(x), w - 2), fx = x - x0 (y likewise);
+ *               top = a00 + fx (a01 - a00), bot = a10 + fx (a11 - a10), value = top + fy (bot - top).
+ *   levels      from the coarsest to the finest; (u0, v0) = 0 on the coarsest, on a finer level
+ *               2 bil(coarse, (x + 0.5) / 2 - 0.5, (y + 0.5) / 2 - 0.5) for both components.
+ *   warp        `warps` times per level: Bw = bil(P1, x + u0, y + v0); central differences 0.5 (a[x + 1] - a[x - 1]) of P0 and of Bw with
+ *               replicated borders; ox = max(-(x + u0), (x + u0) - (w - 1), 0), oy likewise, m = clamp(1 - max(ox, oy), 0, 1);
+ *               Ix = m 0.5 (P0x + Bwx), Iy = m 0.5 (P0y + Bwy), It = m (Bw - P0), c = It - Ix u0 - Iy v0, den = 1 / (alpha^2 + Ix^2 + Iy^2).
+ *   solve       (U, V) = (u0, v0), then `iters` Jacobi sweeps, every pixel from the previous iterate: Ub, Vb = the means of the four
+ *               neighbours (replicated borders), t = (Ix Ub + Iy Vb + c) den, U = Ub - Ix t, V = Vb - Iy t.
+ *               Then u0 += clamp(U - u0, -max_step, max_step), v0 likewise.
+ * The finest level's (u0, v0) after its last warp is the result.  Every a * b + c rounds twice (no contraction).
+ * workspace: gsvc_flow_workspace_bytes(n, H, W, max_levels, min_side) bytes, 16-byte aligned, the caller's, not relied on to hold
+ * anything: both pyramids, three flow fields and three coefficient planes at full size (about 11.7 floats per pixel and pair; < 0 for
+ * a shape gsvc_flow_estimate refuses).  Refused with an error before any launch: a NULL pointer, n outside 1 .. 65535, a side
+ * outside 2 .. 32768, min_side < 2, min(H, W) < min_side, alpha <= 0, max_step <= 0, warps, iters or max_levels < 1, plane_pitch
+ * below H W, a plane base that is not 4-byte or a workspace that is not 16-byte aligned.  Nothing synchronises.
+ *
+ * [INTERNAL] the stages, for tests (planes [n, h, w] contiguous):
+ * gsvc_flow_pyramid_step   dst = blur(src) (pool = 0) or blur(pool(src)) (pool = 1: dst is [n, sh / 2, sw / 2]).
+ * gsvc_flow_warp           Ix, Iy, c of one warp.  coarse_u, coarse_v NULL: u0, v0 are read.  Else they are WRITTEN: the coarse flow
+ *                          [n, ch, cw] upsampled as above, formed inside the same pass.
+ * gsvc_flow_solve          `iters` sweeps from U, V; u0, v0 NULL: out = (U, V) after them, else out = u0 + clamp(U - u0, +-max_step)
+ *                          (the epilogue of a warp's last solver launch).  A workgroup owns 56 x 56 pixels and runs 4 sweeps per launch
+ *                          on 64 x 64 staged ones; a level of at most 64 x 64 runs all its sweeps in one launch.  workspace:
+ *                          gsvc_flow_solve_workspace_bytes(n, h, w) bytes, 16-byte aligned; out may not alias an input.
+ * ---------------------------------------------------------------------------------------------------- */
+int64_t gsvc_flow_workspace_bytes(int32_t n, int32_t H, int32_t W, int32_t max_levels, int32_t min_side);
+int gsvc_flow_estimate(const float *luma0, const float *luma1, int64_t plane_pitch, int32_t n, int32_t H, int32_t W, float alpha,
+                       int32_t warps, int32_t iters, int32_t min_side, int32_t max_levels, float max_step, float *flow_out,
+                       void *workspace, void *stream);
+int gsvc_flow_pyramid_step(const float *src, int32_t n, int32_t sh, int32_t sw, int32_t pool, float *dst, void *stream);
+int gsvc_flow_warp(const float *P0, const float *P1, float *u0, float *v0, int32_t n, int32_t h, int32_t w, const float *coarse_u,
+                   const float *coarse_v, int32_t ch, int32_t cw, float *Ix, float *Iy, float *c, void *stream);
+int64_t gsvc_flow_solve_workspace_bytes(int32_t n, int32_t h, int32_t w);
+int gsvc_flow_solve(const float *U, const float *V, const float *Ix, const float *Iy, const float *c, const float *u0, const float *v0,
+                    int32_t n, int32_t h, int32_t w, float alpha, int32_t iters, float max_step, float *out_u, float *out_v,
+                    void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

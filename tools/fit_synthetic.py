@@ -21,8 +21,10 @@ built on:
 
 usage: python tools/fit_synthetic.py [--steps 2000] [--height 1080 --width 1920 --frames 64 --anchors 100000] [--json out.json]
                                      [--write-decoded out.y4m]
-       python tools/fit_synthetic.py --video clip.y4m [--flow-dir flows/] [--video-resident u8] ...      (the same chain on a video file: its
-                                     frame count and size replace --frames / --height / --width; raw files: --video-size WxH)
+       python tools/fit_synthetic.py --video clip.y4m [--flow-dir flows/ | --estimate-flow] [--video-resident u8] ...      (the same chain on a
+                                     video file: its frame count and size replace --frames / --height / --width; raw files: --video-size WxH)
+       python tools/fit_synthetic.py --estimate-flow ...      (optical flow estimated from the frames, gsvc_amd/flow.py, instead of the synthetic
+                                     video's analytic flow or a video file's --flow-dir)
 """
 import argparse
 import copy
@@ -77,6 +79,10 @@ def main(argv=None):
                     help="e.g. yuv420p,bt601,full or yuv420p10le (default: yuv420p,bt709,limited; rgb24 for .rgb; a .y4m file's own layout, "
                          "depth and range win)")
     ap.add_argument("--flow-dir", default=None, metavar="DIR", help="optical-flow files of --video, one per frame pair (none: optical_lambda = 0)")
+    ap.add_argument("--estimate-flow", action="store_true",
+                    help="estimate the optical flow from the frames themselves (gsvc_amd.flow.EstimatedFlowCube): a --video keeps optical_lambda "
+                         "without a --flow-dir, the synthetic video's analytic flow is replaced")
+    ap.add_argument("--optical-lambda", type=float, default=None, help="weight of the flow-guided loss (default: the configuration's)")
     ap.add_argument("--video-resident", choices=("float", "u8"), default="float",
                     help="keep the video on the device as float32 pictures, or as the file's bytes (converted one frame per fetch)")
     args = ap.parse_args(argv)
@@ -108,10 +114,25 @@ def main(argv=None):
         vfmt = _frame_format(args.video_format) if args.video_format else None
         cube = VideoFileCube(args.video, optical_flow_dir=args.flow_dir, W=vw, H=vh, fmt=vfmt, device=dev, resident=args.video_resident)
         H, W, T = cube.height, cube.width, cube.len_z_frames          # the file says what is fitted
-        if args.flow_dir is None:
+        flow_source = "files" if args.flow_dir is not None else "none"
+        if args.flow_dir is None and not args.estimate_flow:
             opt.optical_lambda = 0.0
     else:
         cube = SyntheticFrameCube(H, W, T, seed=1234, device=dev).materialize()
+        flow_source = "analytic"
+    if args.optical_lambda is not None:
+        opt.optical_lambda = args.optical_lambda
+    flow_log = {"source": flow_source}
+    if args.estimate_flow:
+        from gsvc_amd.flow import EstimatedFlowCube
+        analytic = cube if not args.video else None
+        cube = EstimatedFlowCube(cube, device=dev)
+        flow_log = cube.describe()
+        if analytic is not None:          # the synthetic video knows its flow: how far is the estimate from it?
+            epe = [float((cube.get_optical_flow(i) - analytic.get_optical_flow(i).to(dev)).square().sum(0).sqrt().mean()) for i in range(T - 1)]
+            zero = [float(analytic.get_optical_flow(i).square().sum(0).sqrt().mean()) for i in range(T - 1)]
+            flow_log["mean_epe_vs_analytic_px"], flow_log["mean_analytic_magnitude_px"] = float(np.mean(epe)), float(np.mean(zero))
+    flow_log["optical_lambda"] = float(opt.optical_lambda)
     mp_.threshold = args.slab_frames / 2.0 / cube.scale
     s = N / 40_000.0
     opt.iterations, opt.lmbda = N, args.lmbda
@@ -143,7 +164,7 @@ def main(argv=None):
                       "slab_frames": args.slab_frames, "schedule": [opt.full_precision_training_total, opt.quantized_training_total,
                                                                     opt.entropy_constrained_train_total, opt.ste_entropy_constrained_train_total],
                       "densify": [opt.start_stat, opt.update_from, opt.update_interval, opt.update_until, opt.pause_densification]},
-           "phases": []}
+           "phases": [], "flow": flow_log}
     if args.video:
         log["video"] = {"path": args.video, "frames": T, "W": W, "H": H, "layout": cube.fmt.layout, "matrix": cube.fmt.matrix,
                         "range": cube.fmt.range, "chroma": cube.chroma, "resident": cube.resident, "optical_lambda": opt.optical_lambda}
