@@ -1,8 +1,7 @@
 """The MFMA layer kernels (csrc/linear.hip, linear_ws.h, linear_epi_{a,b,c,d}.hip, linear_accum.hip) and the weight gradients
 (csrc/linear_wgrad.hip) through their C entry points, at the row counts, widths, alignments and job mixes that choose between their
 code paths, each against the float64 run of its plain tensor statement in tests/_linear_kernel_refs.py.  No module of the package
-stands between the test and the kernel, so nothing here can fall back to torch.  (csrc/mlp_chain.hip is not covered here: it keeps
-tests/test_prod_fixture_gpu.py and tests/test_chain_traffic_gpu.py.)
+stands between the test and the kernel, so nothing here can fall back to torch.
 
 Two assertions per shape:
   * exact probe: integer inputs whose sums of absolute terms stay below 2^24 (tests/test_linear_kernel_refs_cpu.py shows it for
