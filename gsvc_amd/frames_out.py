@@ -190,7 +190,7 @@ def delivered_images(images, fmt: FrameFormat = FrameFormat(), chroma: str = "bi
 
 
 def render_frames_u8(frames, pc, pipe, bg_color, fmt: FrameFormat = FrameFormat(), batch: int = 8, to_host: bool = True,
-                     scaling_modifier=1.0, mode=None):
+                     scaling_modifier=1.0, mode=None, on_device_batch=None):
     """The decoder's render loop with frames of bytes as output (8-bit samples, or little-endian 16-bit samples for a deep ``fmt``): a
     generator over ``render_frames`` that converts each render batch with one
     launch and yields one flat uint8 frame (``frame_bytes`` long; ``planes`` splits it) per video frame, in order.
@@ -199,7 +199,10 @@ def render_frames_u8(frames, pc, pipe, bg_color, fmt: FrameFormat = FrameFormat(
     by events, and handed out one batch late, after its event — by then the next batch is generated, composited, converted and on
     its way into the other buffer.  A yielded frame is a CPU tensor that VIEWS the pinned buffer: it is valid until the generator is
     advanced again; a caller that keeps frames copies them (``frame.clone()``, ``frame.numpy().copy()``).
-    ``to_host=False``: yields device tensors, rows of a per-batch tensor that is never written again."""
+    ``to_host=False``: yields device tensors, rows of a per-batch tensor that is never written again.
+    ``on_device_batch``: called with every batch's converted frames, uint8 ``[n, frame_bytes]`` in device memory, on the current stream
+    before they are yielded or copied to the host (``bitstream.decode_video`` takes their picture hashes there); what it launches on
+    that stream is ordered before the buffer is written again."""
     import torch
 
     from .generate import GenerateMode
@@ -221,7 +224,10 @@ def render_frames_u8(frames, pc, pipe, bg_color, fmt: FrameFormat = FrameFormat(
         images = [next(source) for _ in range(min(batch, len(frames) - i))]
         n = len(images)
         if not to_host:
-            yield from frames_to_u8(images, fmt).unbind(0)
+            rows = frames_to_u8(images, fmt)
+            if on_device_batch is not None:
+                on_device_batch(rows)
+            yield from rows.unbind(0)
             continue
         if ring is None:
             nbytes = frame_bytes(images[0].shape[1], images[0].shape[2], fmt)
@@ -235,6 +241,8 @@ def render_frames_u8(frames, pc, pipe, bg_color, fmt: FrameFormat = FrameFormat(
         frames_to_u8(images, fmt, out=on_dev[:n])
         converted = torch.cuda.Event()
         converted.record(cur)
+        if on_device_batch is not None:
+            on_device_batch(on_dev[:n])     # (behind the event: the copy does not wait for it)
         with torch.cuda.stream(copy_stream):
             copy_stream.wait_event(converted)
             on_host[:n].copy_(on_dev[:n], non_blocking=True)

@@ -9,8 +9,8 @@ clipped to 0) — parity unpinned, checked against an independent NumPy / SciPy 
 LPIPS: gsvc_amd/lpips.py (needs a weights file).  Plain torch ops: these run a few times per evaluation, not per step.
 
 The metrics a video codec is judged by run as kernels (csrc/metrics.hip; formulas in include/gsvc_hip.h): ``plane_sse`` and
-``code_metrics`` take PSNR-Y / -U / -V on the sample CODES of two frame buffers, ``ms_ssim_fused`` is ``ms_ssim`` in ten launches, and
-``compare_videos`` compares two video files.  These need the built library and a GPU (no CPU fallback); importing this module does not.
+``code_metrics`` take PSNR-Y / -U / -V on the sample CODES of two frame buffers, ``ms_ssim_fused`` is ``ms_ssim`` in ten launches,
+``compare_videos`` compares two video files, and ``picture_hash`` (csrc/picture_hash.hip) is the per-plane hash a bitstream file carries.  These need the built library and a GPU (no CPU fallback); importing this module does not.
 """
 from __future__ import annotations
 
@@ -126,6 +126,21 @@ def plane_sse(a_u8, b_u8, H: int, W: int, fmt) -> torch.Tensor:
     with torch.cuda.device(a.device):
         _lib.check(_lib.lib().gsvc_frames_sse(a.data_ptr(), sa, b.data_ptr(), sb, n, H, W, LAYOUTS[fmt.layout], fmt.depth, out.data_ptr(),
                                               _lib.current_stream(a.device)), "gsvc_frames_sse")
+    return out
+
+
+def picture_hash(frames_u8, H: int, W: int, fmt) -> torch.Tensor:
+    """The picture hash of every frame and plane of a buffer of delivered frames (what ``plane_sse`` accepts) -> int64 ``[n, 3]`` on
+    their device: the bits of the uint64 sums ``gsvc_picture_hash`` defines (include/gsvc_hip.h; the ``PHSH`` section of a bitstream
+    file, gsvc_amd/bitstream.py).  One launch on the current stream; nothing synchronises."""
+    from .frames_out import LAYOUTS, frame_bytes
+    H, W = int(H), int(W)
+    nbytes = frame_bytes(H, W, fmt)
+    a, n, sa = _frame_rows(frames_u8, nbytes, fmt, "picture_hash")
+    out = torch.empty((n, 3), dtype=torch.int64, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.lib().gsvc_picture_hash(a.data_ptr(), sa, n, H, W, LAYOUTS[fmt.layout], fmt.depth, out.data_ptr(),
+                                                _lib.current_stream(a.device)), "gsvc_picture_hash")
     return out
 
 

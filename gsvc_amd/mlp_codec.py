@@ -199,8 +199,8 @@ def quantize_model(pc, replace=True):
     return pc.quantized_model_cache
 
 
-def encode_mlp(pc, file_path) -> int:
-    """Write the quantised MLPs (``quantize_model`` must have run); returns the file size in bits (reference :1767-1835)."""
+def encode_mlp_bytes(pc) -> bytes:
+    """The bytes ``encode_mlp`` writes (``quantize_model`` must have run): what the MLPS section of a bitstream file holds."""
     valid_mask_list, quant_weight_list, meta_info_list = pc.quantized_model_cache
     compressed_mask = encode_mask(torch.cat(valid_mask_list))
     sym = torch.cat(quant_weight_list).to(torch.int64).cpu().numpy()
@@ -208,12 +208,13 @@ def encode_mlp(pc, file_path) -> int:
     params = code.encode(sym)
     meta = {"code_lengths": {str(s): l for s, l in code.lengths.items()}, "meta_list": meta_info_list, "n_symbols": int(sym.size)}
     compressed_meta = zlib.compress(json.dumps(meta).encode("utf-8"), 9)
+    return MAGIC + struct.pack("<QQQ", len(compressed_meta), len(compressed_mask), len(params)) + compressed_meta + compressed_mask + params
+
+
+def encode_mlp(pc, file_path) -> int:
+    """Write the quantised MLPs (``quantize_model`` must have run); returns the file size in bits (reference :1767-1835)."""
     with open(file_path, "wb") as f:
-        f.write(MAGIC)
-        f.write(struct.pack("<QQQ", len(compressed_meta), len(compressed_mask), len(params)))
-        f.write(compressed_meta)
-        f.write(compressed_mask)
-        f.write(params)
+        f.write(encode_mlp_bytes(pc))
     import os
     return os.path.getsize(file_path) * 8
 
@@ -221,7 +222,11 @@ def encode_mlp(pc, file_path) -> int:
 def decode_mlp(file_path) -> dict:
     """{state_dict key: de-quantised tensor} of an ``encode_mlp`` file."""
     with open(file_path, "rb") as f:
-        blob = f.read()
+        return decode_mlp_bytes(f.read())
+
+
+def decode_mlp_bytes(blob: bytes) -> dict:
+    """``decode_mlp`` of the file's bytes."""
     if blob[:len(MAGIC)] != MAGIC:
         raise ValueError("not an MLP stream of this library")
     at = len(MAGIC)

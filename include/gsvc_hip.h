@@ -1016,6 +1016,26 @@ int gsvc_msssim(const void *x, int64_t x_row_pitch, int64_t x_plane_pitch, const
                 int32_t P, int32_t H, int32_t W, int32_t sample_type, float peak, void *workspace, double *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * [INTERNAL] Picture hash on the codes (csrc/picture_hash.hip): what the PHSH section of a bitstream file holds.
+ *
+ * gsvc_picture_hash: out[k, p] (uint64 [n, 3], 8-byte aligned) = the hash of plane p of frame k of a buffer of delivered frames (frame
+ * k starts at frames + k * stride).  With s the 0-based raster index of a sample within its plane and c its code, all in uint32
+ * (wrapping):
+ *     x = s * 0x9E3779B1 ^ (c + 1) * 0x85EBCA6B;   x ^= x >> 15;   x *= 0x2C1B3C6D;   x ^= x >> 12
+ *     out[k, p] = the sum of x over the samples of the plane, modulo 2^64
+ * A sum of integers: the same bits in every run and for every launch shape; it depends on where a sample sits, not only on the
+ * multiset of codes.
+ *   layout      GSVC_FRAMES_RGB24 (depth 8 only): p = R, G, B, the sample index mod 3, and s = the pixel index.  GSVC_FRAMES_YUV444P /
+ *               _YUV420P: p = Y, U, V, the planes one after the other (H W samples, then twice H W, or twice H W / 4 for 4:2:0).
+ *   depth       8: one byte per sample.  9 .. 16: one little-endian 16-bit word per sample, hashed as it is (nothing is masked).
+ * Refused with an error before any launch: an unknown layout, a depth outside 8 .. 16, rgb24 deeper than 8, an odd H or W for 4:2:0,
+ * a stride below the frame's bytes (gsvc_frames_bytes), an odd base or stride for a deep format, a NULL pointer, n < 1.  Bytes
+ * between frames are not read.  The call zeroes out on the stream and does not synchronise.
+ * ---------------------------------------------------------------------------------------------------- */
+int gsvc_picture_hash(const uint8_t *frames, int64_t stride, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t depth,
+                      uint64_t *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Dense optical flow of adjacent frames (csrc/flow.hip): coarse-to-fine Horn-Schunck with warping.  No weights, stencils only: the
  * same bits in every run, for every batch size and launch geometry.
  *

@@ -5,6 +5,7 @@ kernels of csrc/metrics.hip, so it needs the GPU).  Prints one JSON line.
 
     python tools/compare_video.py ref.y4m dec.y4m [--json out.json]
     python tools/compare_video.py ref.yuv dec.yuv --size 1920x1080 --format yuv420p10le
+    python tools/compare_video.py a.y4m b.y4m --hash      (also each file's per-frame picture hashes, ``metrics.picture_hash``, and whether they agree)
 """
 import argparse
 import json
@@ -12,6 +13,22 @@ import os
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _hashes(path, W, H, fmt, chunk):
+    """The picture hashes of a video file's frames: [[16 hex digits per plane] per frame]."""
+    import torch
+
+    from gsvc_amd.frames_in import open_video
+    from gsvc_amd.metrics import picture_hash
+    hdr, frames = open_video(path, W, H, fmt)
+    out = []
+    for i in range(0, int(frames.shape[0]), chunk):
+        import numpy as np
+        on_dev = torch.from_numpy(np.ascontiguousarray(frames[i:i + chunk])).cuda()
+        got = picture_hash(on_dev, hdr["H"], hdr["W"], hdr["fmt"]).cpu().numpy().view(np.uint64)
+        out += [[f"{int(v):016x}" for v in row] for row in got]
+    return out
 
 
 def main(argv=None):
@@ -22,6 +39,8 @@ def main(argv=None):
     ap.add_argument("--format", default=None, metavar="LAYOUT", help="format of raw files in ffmpeg's spelling (yuv420p, yuv444p10le, rgb24, ...)")
     ap.add_argument("--chunk", type=int, default=16, help="frames uploaded at a time")
     ap.add_argument("--no-per-frame", action="store_true", help="leave the per-frame lists out of the line")
+    ap.add_argument("--hash", action="store_true",
+                    help="also print the per-frame, per-plane picture hashes of both files (what a bitstream file's PHSH section holds) and whether they agree")
     ap.add_argument("--json", default=None)
     args = ap.parse_args(argv)
     from gsvc_amd.frames_out import FrameFormat
@@ -34,6 +53,10 @@ def main(argv=None):
             raise SystemExit(f"--size is WxH (got {args.size!r})")
     fmt = FrameFormat.from_name(args.format) if args.format else None
     res = dict(compare_videos(args.ref, args.dec, W, H, fmt, chunk=args.chunk), ref=args.ref, dec=args.dec)
+    if args.hash:
+        ha, hb = _hashes(args.ref, W, H, fmt, max(1, args.chunk)), _hashes(args.dec, W, H, fmt, max(1, args.chunk))
+        same = [a == b for a, b in zip(ha, hb)]
+        res["picture_hash"] = {"ref": ha, "dec": hb, "equal": same, "all_equal": all(same)}
     if args.no_per_frame:
         res.pop("per_frame")
     line = json.dumps(res)

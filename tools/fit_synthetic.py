@@ -20,7 +20,7 @@ built on:
     decodable segment, gsvc_amd/codec.py — at ~0.3 bit per symbol that framing is itself ~5 % and is reported beside it).
 
 usage: python tools/fit_synthetic.py [--steps 2000] [--height 1080 --width 1920 --frames 64 --anchors 100000] [--json out.json]
-                                     [--write-decoded out.y4m]
+                                     [--write-decoded out.y4m] [--write-bitstream out.gsvc]
        python tools/fit_synthetic.py --video clip.y4m [--flow-dir flows/ | --estimate-flow] [--video-resident u8] ...      (the same chain on a
                                      video file: its frame count and size replace --frames / --height / --width; raw files: --video-size WxH)
        python tools/fit_synthetic.py --estimate-flow ...      (optical flow estimated from the frames, gsvc_amd/flow.py, instead of the synthetic
@@ -72,6 +72,9 @@ def main(argv=None):
     ap.add_argument("--code-metrics", action="store_true",
                     help="also report PSNR-Y / -U / -V, their average and 6:1:1 mean, and MS-SSIM-Y of the decoded 8-bit-MLP model on the sample codes "
                          "of --decoded-format (default yuv420p) against the source's frames in that format: log['decoded_code_metrics']")
+    ap.add_argument("--write-bitstream", default=None, metavar="PATH",
+                    help="write the shipped-form model (8-bit MLPs, the streams coded under them) as ONE bitstream file (.gsvc, gsvc_amd/bitstream.py): "
+                         "log['bitstream_bytes'] beside log['total_bytes'], the size of the directory of streams")
     ap.add_argument("--video", default=None, metavar="PATH",
                     help="fit this 8-bit or 10 / 12 / 16-bit video file (.y4m, or raw .yuv / .rgb with --video-size) instead of the synthetic frames")
     ap.add_argument("--video-size", default=None, metavar="WxH", help="frame size of a raw --video file")
@@ -91,11 +94,9 @@ def main(argv=None):
     from gsvc_amd.frame import SyntheticFrameCube
     from gsvc_amd.generate import GenerateMode
     from gsvc_amd.loss_utils import psnr_func
-    from gsvc_amd.model import GaussianModel
     from gsvc_amd.ortho_gaussian_renderer import render_pair
     from gsvc_amd.report import evaluate
     from gsvc_amd.stream_codec import conduct_stream_decoding, conduct_stream_encoding
-    from gsvc_amd.train import Trainer
 
     # under torch.distributed.run: data-parallel fit (frames sharded over the ranks, gsvc_amd/dist.py); rank 0 encodes and evaluates.
     # GSVC_DIST_BACKEND=gloo GSVC_SHARE_GPU=1 puts every rank on device 0 (rehearsal on one GPU)
@@ -133,32 +134,9 @@ def main(argv=None):
             zero = [float(analytic.get_optical_flow(i).square().sum(0).sqrt().mean()) for i in range(T - 1)]
             flow_log["mean_epe_vs_analytic_px"], flow_log["mean_analytic_magnitude_px"] = float(np.mean(epe)), float(np.mean(zero))
     flow_log["optical_lambda"] = float(opt.optical_lambda)
-    mp_.threshold = args.slab_frames / 2.0 / cube.scale
-    s = N / 40_000.0
-    opt.iterations, opt.lmbda = N, args.lmbda
-    opt.full_precision_training_total, opt.quantized_training_total = int(10_000 * s), int(5_000 * s)
-    opt.entropy_constrained_train_total = int(20_000 * s)
-    opt.ste_entropy_constrained_train_total = N - int(35_000 * s)
-    opt.start_stat, opt.update_from, opt.update_until = int(500 * s), int(1_500 * s), int(25_000 * s)
-    opt.update_interval = max(20, int(100 * s))
-    opt.pause_densification = int(1_000 * s)
-    if args.densify_grad_threshold is not None:
-        opt.densify_grad_threshold = args.densify_grad_threshold
-    for name in dir(opt):                        # the learning-rate schedules decay over the run's length
-        if name.endswith("_max_steps"):
-            setattr(opt, name, N)
-    torch.manual_seed(0)
-    np.random.seed(0)
-    pc = GaussianModel(mp_, mp_.anchor_feature_dim, mp_.n_offsets, mp_.voxel_size, mp_.update_depth, mp_.update_init_factor,
-                       mp_.update_hierarchy_factor, mp_.use_feat_bank, n_features_per_level=mp_.grid_feature_dim,
-                       log2_hashmap_size=mp_.log2, log2_hashmap_size_2D=mp_.log2_2D, device=dev)
-    # reference frame_cube/utils.py:6-15 (init_point_cloud, bleed 0.1)
-    lim = np.array([cube.x_min, cube.y_min, cube.z_min]) * 1.1
-    pc.create_from_points(np.random.default_rng(0).uniform(lim, -lim, (args.anchors, 3)), spatial_lr_scale=1.0)
-    pc.update_anchor_bound(cube.x_min, cube.y_min, cube.z_min)
-    pc.training_setup(opt)
-    gdist.broadcast_parameters(pc)
-    trainer = Trainer(pc, cube, opt, pipe, mp_, seed=0)
+    from gsvc_amd.fit_setup import configure_fit, new_fit
+    configure_fit(mp_, opt, cube, N, args.lmbda, args.slab_frames, args.densify_grad_threshold)
+    pc, trainer = new_fit(cube, mp_, opt, pipe, args.anchors, dev)
     bg = trainer.background
     log = {"config": {"H": H, "W": W, "frames": T, "steps": N, "anchors_init": args.anchors, "lmbda": args.lmbda,
                       "slab_frames": args.slab_frames, "schedule": [opt.full_precision_training_total, opt.quantized_training_total,
@@ -283,6 +261,11 @@ def main(argv=None):
             pack_q.save(os.path.join(tmp, "streams"))
             total_bytes = sum(os.path.getsize(os.path.join(dp, f)) for dp, _, fs in os.walk(tmp) for f in fs)
             dec_q = conduct_stream_decoding(copy.deepcopy(q), pack_q, mlp_file=mlp_file)
+            if args.write_bitstream:
+                from gsvc_amd.bitstream import CubeGeometry, write_bitstream
+                with open(mlp_file, "rb") as f:
+                    written = write_bitstream(args.write_bitstream, q, pack_q, CubeGeometry.of(cube, mp_, pipe, bg.tolist()), f.read())
+                log["bitstream_bytes"], log["bitstream_sections"] = int(written["bytes"]), written["sections"]
         lp = None
         if args.lpips_weights:
             from gsvc_amd.lpips import lpips_fn_from

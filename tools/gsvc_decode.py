@@ -1,0 +1,62 @@
+#!/usr/bin/env python3
+"""Decode a bitstream file (tools/gsvc_encode.py; gsvc_amd/bitstream.py) to a video.  The file is all it reads:
+
+    python tools/gsvc_decode.py clip.gsvc -o out.y4m [--format yuv420p10le] [--no-verify | --strict]
+
+-o: .y4m / .yuv (yuv420p unless --format says otherwise), .rgb (rgb24), else a directory of PNGs.  The picture hash of every frame is
+taken on the device and, where the file carries hashes of the format decoded to, compared: the JSON line printed says how many frames
+were verified and which did not match.  --strict: exit status 1 on a mismatch, or when nothing could be verified.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("bitstream")
+    ap.add_argument("-o", "--output", required=True, metavar="PATH")
+    ap.add_argument("--format", default=None, metavar="LAYOUT[,MATRIX[,RANGE]]",
+                    help="e.g. yuv420p10le or yuv444p,bt709,full (default: the format of the file's picture hashes where the output takes it, "
+                         "else what the output's extension means)")
+    ap.add_argument("--batch", type=int, default=8, help="frames per render batch")
+    mode = ap.add_mutually_exclusive_group()
+    mode.add_argument("--no-verify", action="store_true", help="do not take picture hashes")
+    mode.add_argument("--strict", action="store_true", help="fail when a frame's picture hash differs from the file's, or nothing could be verified")
+    args = ap.parse_args(argv)
+
+    from gsvc_amd.bitstream import BitstreamError, decode_video, read_bitstream
+    from gsvc_amd.frames_out import FrameFormat, open_sink
+    try:
+        bs = read_bitstream(args.bitstream)
+    except BitstreamError as e:
+        print(f"gsvc_decode: {args.bitstream}: {e}", file=sys.stderr)
+        return 2
+    fmt = None
+    if args.format:
+        name, *rest = args.format.split(",")
+        if len(rest) > 2:
+            raise SystemExit(f"a frame format is LAYOUT[,MATRIX[,RANGE]] (got {args.format!r})")
+        fmt = FrameFormat.from_name(name, **dict(zip(("matrix", "range"), rest)))
+    elif bs.hash_format is not None:
+        ext = os.path.splitext(args.output)[1].lower()
+        takes = {".y4m": ("yuv420p", "yuv444p"), ".yuv": ("yuv420p", "yuv444p"), ".rgb": ("rgb24",)}.get(ext, ("rgb24",))
+        if bs.hash_format.layout in takes:
+            fmt = bs.hash_format
+    g = bs.geometry
+    sink, fmt = open_sink(args.output, g.W, g.H, fps=g.fps, fmt=fmt)
+    try:
+        res = decode_video(bs, sink, fmt=fmt, batch=args.batch, verify=not args.no_verify, strict=args.strict)
+    except BitstreamError as e:
+        print(f"gsvc_decode: {args.bitstream}: {e}", file=sys.stderr)
+        return 1
+    res.pop("hashes", None)
+    print(json.dumps(dict(res, output=args.output, W=g.W, H=g.H, file_bytes=bs.file_bytes)))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
