@@ -576,15 +576,18 @@ __global__ void __launch_bounds__(256) k_grid_input_bwd(const float *__restrict_
     if (t >= N * D) return;
     const uint32_t b = t / D, d = t - b * D;
     const float *dd = dy_dx + (size_t)b * L * D * C;
-    float r = 0.f;
+    // the L * C terms are of the size of resolution * |table| * |grad| and largely cancel: summed in float the result carried
+    // L * C roundings of the TERMS' size (9e-7 of the largest gradient for one point, 4 levels of 8 features); the products of
+    // two floats are exact in double and the kernel is bound by its loads, so the sum is formed there and rounded once
+    double r = 0.0;
     for (uint32_t l = 0; l < L; l++) {
         float g[C], y[C];
         load_row<C>(grad + (size_t)l * io.feat_level_stride + (size_t)b * io.feat_point_stride, g);
         load_row<C>(dd + (size_t)l * D * C + d * C, y);
 #pragma unroll
-        for (uint32_t ch = 0; ch < C; ch++) r += g[ch] * y[ch];
+        for (uint32_t ch = 0; ch < C; ch++) r += (double)g[ch] * (double)y[ch];
     }
-    grad_inputs[t] = r;
+    grad_inputs[t] = (float)r;
 }
 
 static std::atomic<uint32_t> g_absmax_ring{0};      // slot of g_grid_absmax a backward launch uses (single-grid and multi-grid alike)
