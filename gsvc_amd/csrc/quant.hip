@@ -221,14 +221,17 @@ __global__ void __launch_bounds__(256) k_ste_binary_count_many(SteTables t, floa
 
 // out[0] = bits = n1 (-log2 p) + n0 (-log2 (1 - p)) + 32, p = n1 / total clamped to [1e-6, 1 - 1e-6] (reference
 // utils/encodings.py:34-51, float32 as there); out[1] = d bits / d n1 = log2((1 - p) / p) (the terms through p cancel where p
-// is not clamped and vanish where it is)
-__global__ void k_table_bits(const float *__restrict__ counts, int tables, float total, float *__restrict__ out)
+// is not clamped and vanish where it is).  n1 and n0 = total - n1 are formed in double: the counts are integers below 2^24 each,
+// so both are exact whatever the total, where a float total rounds above 2^24 and total - n1 then loses the few zeros of a
+// nearly full set of tables outright.  Below 2^24 the three floats are the same bits as the all-float form gave.
+__global__ void k_table_bits(const float *__restrict__ counts, int tables, long long total, float *__restrict__ out)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    float ones = 0.f;
-    for (int k = 0; k < tables; k++) ones += counts[k];
-    const float p = fminf(fmaxf(ones / total, 1e-6f), 1.f - 1e-6f);
-    out[0] = ones * (-log2f(p)) + (total - ones) * (-log2f(1.f - p)) + 32.f;
+    double n1 = 0.0;
+    for (int k = 0; k < tables; k++) n1 += (double)counts[k];
+    const float ones = (float)n1, zeros = (float)((double)total - n1);
+    const float p = fminf(fmaxf((float)(n1 / (double)total), 1e-6f), 1.f - 1e-6f);
+    out[0] = ones * (-log2f(p)) + zeros * (-log2f(1.f - p)) + 32.f;
     out[1] = log2f((1.f - p) / p);
 }
 
@@ -426,6 +429,6 @@ extern "C" int gsvc_ste_binary_backward_many(const float *const *x, const float 
 extern "C" int gsvc_table_bits(const float *counts, int32_t tables, int64_t total, float *out, void *stream)
 {
     GSVC_REQUIRE(counts && out && tables >= 1 && total > 0, "table_bits: bad arguments");
-    hipLaunchKernelGGL(gsvc::k_table_bits, dim3(1), dim3(64), 0, (hipStream_t)stream, counts, tables, (float)total, out);
+    hipLaunchKernelGGL(gsvc::k_table_bits, dim3(1), dim3(64), 0, (hipStream_t)stream, counts, (int)tables, (long long)total, out);
     return gsvc::check_launch("table_bits");
 }

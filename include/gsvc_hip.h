@@ -396,7 +396,8 @@ int gsvc_ste_binary_count(const float *x, int64_t n, float *y, float *count, voi
 /* The same for up to 8 tables in one launch (x[k], y[k]: n[k] floats; counts[k]); its straight-through backward
  * grad_x[k][i] = |x[k][i]| <= 1 ? grad_y[k][i] + 0.5 count_grads[k count_grad_stride] : 0 (grad_y[k] or count_grads may be NULL = zero: a table
  * entry's share of its count is 1/2); and the Bernoulli code length of the tables from their counts (reference
- * utils/encodings.py:34-51 get_binary_vxl_size over all tables, pipeline/train.py:456): out[0] = bits, out[1] = d bits / d count. */
+ * utils/encodings.py:34-51 get_binary_vxl_size over all tables, pipeline/train.py:456): out[0] = bits, out[1] = d bits / d count
+ * (the counts are added, and total - ones is formed, exactly: total may exceed 2^24). */
 int gsvc_ste_binary_count_many(const float *const *x, float *const *y, const int64_t *n, int32_t tables, float *counts, void *stream);
 int gsvc_ste_binary_backward_many(const float *const *x, const float *const *grad_y, const int64_t *n, int32_t tables,
                                   const float *count_grads, int32_t count_grad_stride, float *const *grad_x, void *stream);
