@@ -3,15 +3,13 @@
 //
 // gsvc_frames_sse   one launch for the n frames of a chunk (frame = blockIdx.y).  The planes of a frame are contiguous, so a frame
 //   is ONE flat run of samples and a plane is a range of sample indices: plane(s) = (s >= HW) + (s >= HW + chroma samples); rgb24's
-//   channel is s mod 3.  A lane's three accumulators are 64-bit; a wave reduces them with shuffles, the workgroup through LDS, and
-//   one thread per plane issues one 64-bit integer atomic (none for a sum of zero) — integer addition is associative: the result is
-//   the same bits in every run.
-//     wide path   (both bases and, for n > 1, both strides 16-byte aligned): a lane takes 16 bytes of a and of b per unit and
-//                 four units 256 units apart (rgb24: 48 bytes = three vectors per unit, so that byte j of a unit is channel j mod 3).
-//                 A vector may straddle a plane boundary (H W = 60: U starts at byte 60): its samples are then classified one by
-//                 one.  The samples behind the last whole unit of the frame are taken one per lane by the units that follow.
-//     edge path   one sample per lane and four samples 256 apart, at any alignment (deep formats: even).
-//   Nothing past the last sample of a frame is read.
+//   channel is s mod 3.  A lane's three accumulators are 64-bit (32-bit partial sums for the 16 pixels of an rgb24 unit); the
+//   64-bit three-plane reduction is add_block_sums of frames_common.h, shared with k_picture_hash, as are the sample helpers.
+//   Integer addition is associative: the result is the same bits in every run.
+//     wide path   (both bases and, for n > 1, both strides 16-byte aligned): a lane takes 16 bytes of a and of b per unit
+//                 (rgb24: 48 bytes = three vectors per unit)
+//     edge path   one sample per lane, at any alignment (deep formats: even).
+//   Nothing past the last sample of a frame is read.  The host part (checks, memset, launch shape, dispatch) is frames_sums_setup.
 // gsvc_msssim       per scale one launch of k_msssim_scale (32x32 outputs of the VALID 11-tap blur per workgroup: the 42x42 inputs
 //   of both pictures staged in LDS, the five moments blurred separably with the register blocking of ssim.hip, the window taps in
 //   vector registers for the reason given there) and, between scales, one launch of k_msssim_pool (2x2 mean, a leading zero row /
@@ -22,7 +20,7 @@
 //   from LDS to the registers.  Variances and the covariance do not change under a shift, mu = m + c, and E[x^2] - mu^2 no longer
 //   subtracts two numbers near 0.5 to get one near 1e-4: that cancellation is the float32 error of the tensor-expression form
 //   (DESIGN section 8e).
-#include "common.h"
+#include "frames_common.h"
 
 #include <cmath>
 #include <type_traits>
@@ -32,14 +30,11 @@ namespace gsvc {
 // ============================================================================================================================
 // plane SSE on codes
 // ============================================================================================================================
-constexpr int SSE_PER_LANE = 4;          // units (wide) or samples (edge) per lane, 256 apart
-
 struct SseArgs {
     const uint8_t *a, *b;
     long long stride_a, stride_b;
     unsigned long long *out;           // [n, 3]
-    long long samples;                 // of one frame
-    long long p0, p1;                  // first sample of the second / third plane (planar layouts)
+    SampleRun run;
 };
 
 __device__ __forceinline__ uint32_t sq_diff(uint32_t x, uint32_t y)
@@ -48,58 +43,44 @@ __device__ __forceinline__ uint32_t sq_diff(uint32_t x, uint32_t y)
     return d * d;                       // 65535^2 = 4 294 836 225 < 2^32
 }
 
-template <int BPS>
-__device__ __forceinline__ uint32_t code_of(const uint32_t *w, int k)
+// plane of the flat sample index s
+template <bool RGB>
+__device__ __forceinline__ int sse_plane(const SampleRun &g, long long s)
 {
-    return BPS == 1 ? (w[k >> 2] >> (8 * (k & 3))) & 255u : (w[k >> 1] >> (16 * (k & 1))) & 65535u;
+    return RGB ? (int)((uint32_t)s % 3u) : (s >= g.p0) + (s >= g.p1);
 }
 
-template <int BPS>
-__device__ __forceinline__ uint32_t code_at(const uint8_t *p, long long s)
-{
-    return BPS == 1 ? (uint32_t)p[s] : (uint32_t)reinterpret_cast<const uint16_t *>(p)[s];
-}
-
-__device__ __forceinline__ void add_to_plane(unsigned long long acc[3], int plane, unsigned long long v)
-{
-    acc[0] += plane == 0 ? v : 0ull;
-    acc[1] += plane == 1 ? v : 0ull;
-    acc[2] += plane == 2 ? v : 0ull;
-}
-
+// the walk of frames_common.h (SampleRun); the per-sample work: the squared difference of the two buffers' codes
 template <int BPS, bool RGB, bool WIDE>
-__global__ void __launch_bounds__(256) k_frames_sse(SseArgs g)
+__global__ void __launch_bounds__(256) k_frames_sse(SseArgs args)
 {
-    __shared__ unsigned long long red[4][3];
-    const uint8_t *a = g.a + (size_t)blockIdx.y * (size_t)g.stride_a;
-    const uint8_t *b = g.b + (size_t)blockIdx.y * (size_t)g.stride_b;
+    const SampleRun &g = args.run;
+    const uint8_t *a = args.a + (size_t)blockIdx.y * (size_t)args.stride_a;
+    const uint8_t *b = args.b + (size_t)blockIdx.y * (size_t)args.stride_b;
     unsigned long long acc[3] = {0ull, 0ull, 0ull};
-    const long long first = (long long)blockIdx.x * (256 * SSE_PER_LANE) + threadIdx.x;
+    const long long first = (long long)blockIdx.x * (256 * SUMS_PER_LANE) + threadIdx.x;
     if (WIDE) {
         constexpr int SPV = 16 / BPS;                    // samples of a 16-byte vector
         constexpr int SPU = RGB ? 3 * SPV : SPV;         // samples of a unit
+        constexpr int NW = SPU * BPS / 4;                // its 32-bit words
         const long long units = g.samples / SPU, tail0 = units * SPU;
 #pragma unroll
-        for (int j = 0; j < SSE_PER_LANE; j++) {
+        for (int j = 0; j < SUMS_PER_LANE; j++) {
             const long long unit = first + 256 * j;
             if (unit < units) {
                 const long long s0 = unit * SPU;
+                uint32_t wa[NW], wb[NW];
+                load_words<4 * NW>(a + s0 * BPS, wa);
+                load_words<4 * NW>(b + s0 * BPS, wb);
                 if (RGB) {
-                    const uint4 *pa = reinterpret_cast<const uint4 *>(a + s0), *pb = reinterpret_cast<const uint4 *>(b + s0);
-                    const uint4 a0 = pa[0], a1 = pa[1], a2 = pa[2], b0 = pb[0], b1 = pb[1], b2 = pb[2];
-                    const uint32_t wa[12] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w, a2.x, a2.y, a2.z, a2.w};
-                    const uint32_t wb[12] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w};
                     uint32_t t[3] = {0u, 0u, 0u};        // 16 squares of at most 255^2 each: 32 bits hold them
 #pragma unroll
-                    for (int k = 0; k < 48; k++) t[k % 3] += sq_diff(code_of<1>(wa, k), code_of<1>(wb, k));
+                    for (int k = 0; k < SPU; k++) t[k % 3] += sq_diff(code_of<1>(wa, k), code_of<1>(wb, k));
                     acc[0] += t[0];
                     acc[1] += t[1];
                     acc[2] += t[2];
                 } else {
-                    const uint4 qa = *reinterpret_cast<const uint4 *>(a + s0 * BPS), qb = *reinterpret_cast<const uint4 *>(b + s0 * BPS);
-                    const uint32_t wa[4] = {qa.x, qa.y, qa.z, qa.w}, wb[4] = {qb.x, qb.y, qb.z, qb.w};
-                    const long long sl = s0 + SPV - 1;
-                    const int pf = (s0 >= g.p0) + (s0 >= g.p1), pl = (sl >= g.p0) + (sl >= g.p1);
+                    const int pf = sse_plane<false>(g, s0), pl = sse_plane<false>(g, s0 + SPV - 1);
                     if (pf == pl) {
                         unsigned long long t = 0ull;
 #pragma unroll
@@ -107,46 +88,23 @@ __global__ void __launch_bounds__(256) k_frames_sse(SseArgs g)
                         add_to_plane(acc, pf, t);
                     } else {                              // a plane boundary inside the vector
 #pragma unroll
-                        for (int k = 0; k < SPV; k++) {
-                            const long long s = s0 + k;
-                            add_to_plane(acc, (s >= g.p0) + (s >= g.p1), sq_diff(code_of<BPS>(wa, k), code_of<BPS>(wb, k)));
-                        }
+                        for (int k = 0; k < SPV; k++)
+                            add_to_plane(acc, sse_plane<false>(g, s0 + k), sq_diff(code_of<BPS>(wa, k), code_of<BPS>(wb, k)));
                     }
                 }
             } else {
                 const long long s = tail0 + (unit - units);
-                if (s < g.samples)
-                    add_to_plane(acc, RGB ? (int)((uint32_t)s % 3u) : (s >= g.p0) + (s >= g.p1), sq_diff(code_at<BPS>(a, s), code_at<BPS>(b, s)));
+                if (s < g.samples) add_to_plane(acc, sse_plane<RGB>(g, s), sq_diff(code_at<BPS>(a, s), code_at<BPS>(b, s)));
             }
         }
     } else {
 #pragma unroll
-        for (int j = 0; j < SSE_PER_LANE; j++) {
+        for (int j = 0; j < SUMS_PER_LANE; j++) {
             const long long s = first + 256 * j;
-            if (s < g.samples)
-                add_to_plane(acc, RGB ? (int)((uint32_t)s % 3u) : (s >= g.p0) + (s >= g.p1), sq_diff(code_at<BPS>(a, s), code_at<BPS>(b, s)));
+            if (s < g.samples) add_to_plane(acc, sse_plane<RGB>(g, s), sq_diff(code_at<BPS>(a, s), code_at<BPS>(b, s)));
         }
     }
-    // wave, then workgroup, then one atomic per plane
-#pragma unroll
-    for (int p = 0; p < 3; p++) {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            const uint32_t lo = __shfl_xor((uint32_t)acc[p], m, 64), hi = __shfl_xor((uint32_t)(acc[p] >> 32), m, 64);
-            acc[p] += ((unsigned long long)hi << 32) | lo;
-        }
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[wave][0] = acc[0];
-        red[wave][1] = acc[1];
-        red[wave][2] = acc[2];
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const unsigned long long v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        if (v) atomicAdd(&g.out[3 * (size_t)blockIdx.y + threadIdx.x], v);
-    }
+    add_block_sums(acc, args.out + 3 * (size_t)blockIdx.y);
 }
 
 // ============================================================================================================================
@@ -430,62 +388,13 @@ extern "C" int gsvc_frames_sse(const uint8_t *a, int64_t a_stride, const uint8_t
                                int32_t layout, int32_t depth, uint64_t *out, void *stream)
 {
     GSVC_REQUIRE(a && b && out, "frames_sse: NULL pointer");
-    GSVC_REQUIRE(n >= 1 && n <= 65535, "frames_sse: n must be 1 .. 65535 (got %d)", (int)n);
-    GSVC_REQUIRE(layout == GSVC_FRAMES_RGB24 || layout == GSVC_FRAMES_YUV444P || layout == GSVC_FRAMES_YUV420P,
-                 "frames_sse: unknown layout %d", (int)layout);
-    GSVC_REQUIRE(depth >= 8 && depth <= 16, "frames_sse: depth must be 8 .. 16 (got %d)", (int)depth);
-    GSVC_REQUIRE(layout != GSVC_FRAMES_RGB24 || depth == 8, "frames_sse: rgb24 frames are 8-bit only");
-    GSVC_REQUIRE(H >= 1 && W >= 1 && H <= 32768 && W <= 32768, "frames_sse: image size must be 1 .. 32768 (got %d x %d)", (int)H, (int)W);
-    GSVC_REQUIRE(layout != GSVC_FRAMES_YUV420P || (H % 2 == 0 && W % 2 == 0), "frames_sse: yuv420p needs even H and W (got %d x %d)",
-                 (int)H, (int)W);
-    const int64_t bytes = gsvc_frames_bytes(H, W, layout, depth);
-    GSVC_REQUIRE(a_stride >= bytes && b_stride >= bytes, "frames_sse: stride %lld / %lld is shorter than a frame (%lld bytes)",
-                 (long long)a_stride, (long long)b_stride, (long long)bytes);
-    const bool deep = depth > 8;
-    if (deep) {
-        GSVC_REQUIRE(((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 1) == 0,
-                     "frames_sse: a frame base is not 2-byte aligned");
-        GSVC_REQUIRE(((a_stride | b_stride) & 1) == 0, "frames_sse: stride %lld / %lld is not a multiple of 2", (long long)a_stride,
-                     (long long)b_stride);
-    }
-    GSVC_REQUIRE((reinterpret_cast<uintptr_t>(out) & 7) == 0, "frames_sse: out is not 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(out, 0, (size_t)n * 3 * sizeof(uint64_t), s) != hipSuccess) {
-        set_error("frames_sse: hipMemsetAsync failed");
-        return GSVC_E_LAUNCH;
-    }
-    SseArgs g;
-    g.a = a;
-    g.b = b;
-    g.stride_a = a_stride;
-    g.stride_b = b_stride;
-    g.out = reinterpret_cast<unsigned long long *>(out);
-    const int64_t px = (int64_t)H * W, chroma = layout == GSVC_FRAMES_YUV420P ? px / 4 : px;
-    g.samples = bytes / (deep ? 2 : 1);
-    g.p0 = px;
-    g.p1 = px + chroma;
-    uintptr_t align = reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b);
-    if (n > 1) align |= (uintptr_t)a_stride | (uintptr_t)b_stride;
-    const bool wide = (align & 15) == 0;
-    const bool rgb = layout == GSVC_FRAMES_RGB24;
-    int64_t units = g.samples;
-    if (wide) {
-        const int64_t spu = rgb ? 48 : (deep ? 8 : 16);
-        units = g.samples / spu + g.samples % spu;          // whole units, then the samples behind them one by one
-    }
-    const int64_t per_block = 256 * SSE_PER_LANE;
-    const dim3 grid((unsigned)((units + per_block - 1) / per_block), (unsigned)n), block(256);
+    FrameSums fs;
+    GSVC_FRAMES_TRY(frames_sums_setup("frames_sse", FrameBufs{"stride", a, a_stride, b, b_stride}, n, H, W, layout, depth, out, s, fs));
+    const SseArgs g = {a, b, a_stride, b_stride, reinterpret_cast<unsigned long long *>(out), fs.run};
+    static void (*const kernels[3][2])(SseArgs) = GSVC_FRAME_SUMS_KERNELS(k_frames_sse);
     ProfScope _p("k_frames_sse", s);
-    if (rgb) {
-        if (wide) hipLaunchKernelGGL((k_frames_sse<1, true, true>), grid, block, 0, s, g);
-        else hipLaunchKernelGGL((k_frames_sse<1, true, false>), grid, block, 0, s, g);
-    } else if (!deep) {
-        if (wide) hipLaunchKernelGGL((k_frames_sse<1, false, true>), grid, block, 0, s, g);
-        else hipLaunchKernelGGL((k_frames_sse<1, false, false>), grid, block, 0, s, g);
-    } else {
-        if (wide) hipLaunchKernelGGL((k_frames_sse<2, false, true>), grid, block, 0, s, g);
-        else hipLaunchKernelGGL((k_frames_sse<2, false, false>), grid, block, 0, s, g);
-    }
+    hipLaunchKernelGGL(kernels[fs.variant][fs.wide], fs.grid, dim3(256), 0, s, g);
     return check_launch("frames_sse");
 }
 
