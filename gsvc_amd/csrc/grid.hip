@@ -12,6 +12,7 @@
 // with 16-byte loads; the [L,N,C] output row of a lane is contiguous so a wave writes 64*4*C contiguous
 // bytes.  The table backward accumulates table slices in LDS (k_grid_bwd_lds below).
 #include "common.h"
+#include "reduce.h"
 #include <algorithm>
 #include <atomic>
 
@@ -319,8 +320,7 @@ __device__ __forceinline__ void grid_absmax_body(const float *__restrict__ grad,
         }
     }
     if (bad) m = __builtin_inff();
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) m = fmaxf(m, __shfl_xor(m, k, 64));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
     __syncthreads();
     if (threadIdx.x == 0) g_grid_absmax[slot][slot_level * gridDim.x + blockIdx.x] = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
@@ -448,8 +448,7 @@ __device__ __forceinline__ void grid_bwd_lds_body(const float *__restrict__ grad
     const uint32_t p0 = chunk_idx * chunk, p1 = min(N, p0 + chunk);
     // largest |grad| of this level (block maxima of k_grid_absmax)
     float gmax = tid < absmax_bpl ? g_grid_absmax[slot][slot_level * absmax_bpl + tid] : 0.f;
-#pragma unroll
-    for (int k = 32; k >= 1; k >>= 1) gmax = fmaxf(gmax, __shfl_xor(gmax, k, 64));
+    gmax = wave_max(gmax);
     if ((tid & 63) == 0) s_max[tid >> 6] = gmax;
     __syncthreads();
     gmax = 0.f;

@@ -13,6 +13,7 @@
 //      sum_r mean_{i in r, opacity_i > 0}(prod_c scaling_ic)   and   sum_r mean_{i in r}(1 - neural_opacity_i)
 //    over un-compacted per-render segments: one reduction launch + a one-thread finalize, one backward launch.
 #include "common.h"
+#include "reduce.h"
 
 namespace gsvc {
 
@@ -22,23 +23,6 @@ struct SegOffsets {
     int64_t off[MAX_RENDERS + 1];   // Gaussian index where render r starts
     int R;
 };
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// sum of v over the 256 threads of a block, returned to thread 0 (red: 4 floats of LDS per value in flight)
-__device__ __forceinline__ float block_sum256(float v, float *red)
-{
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
 
 // out[c] = sum over `count` partial rows of part[row*stride + c], c < ncol; one block of 256 threads (no atomics:
 // thousands of atomics onto the same two or three addresses serialise)
@@ -53,7 +37,7 @@ __device__ __forceinline__ void reduce_partials(const float *__restrict__ part, 
         for (int c = 0; c < NCOL; c++) acc[c] += part[(size_t)b * NCOL + c];
 #pragma unroll
     for (int c = 0; c < NCOL; c++) {
-        const float t = block_sum256(acc[c], red);
+        const float t = block_sum_256<SumOrder::Chain>(acc[c], red);
         if (threadIdx.x == 0) out[c] = t;
     }
 }
@@ -101,8 +85,8 @@ __global__ void __launch_bounds__(256) k_optical_fwd(const float *__restrict__ w
         }
     }
     if (i < n1) partner[i] = code;
-    err = block_sum256(err, red);
-    cnt = block_sum256(cnt, red);
+    err = block_sum_256<SumOrder::Chain>(err, red);
+    cnt = block_sum_256<SumOrder::Chain>(cnt, red);
     if (threadIdx.x == 0) {
         part[2 * blockIdx.x] = err;
         part[2 * blockIdx.x + 1] = cnt;
@@ -192,8 +176,8 @@ __global__ void __launch_bounds__(256) k_optical_fwd_many(const float *__restric
         }
     }
     if (in) partner[i] = code;
-    err = block_sum256(err, red);
-    cnt = block_sum256(cnt, red);
+    err = block_sum_256<SumOrder::Chain>(err, red);
+    cnt = block_sum_256<SumOrder::Chain>(cnt, red);
     if (threadIdx.x == 0) {
         float *d = part + 2 * ((size_t)p * gridDim.x + blockIdx.x);
         d[0] = err;
@@ -266,9 +250,9 @@ __global__ void __launch_bounds__(256) k_regs_fwd(const float *__restrict__ scal
             q += 1.f - opacity[i];
         }
     }
-    p = block_sum256(p, red);
-    m = block_sum256(m, red);
-    q = block_sum256(q, red);
+    p = block_sum_256<SumOrder::Chain>(p, red);
+    m = block_sum_256<SumOrder::Chain>(m, red);
+    q = block_sum_256<SumOrder::Chain>(q, red);
     if (threadIdx.x == 0) {
         float *d = part + ((size_t)r * gridDim.x + blockIdx.x) * 3;
         d[0] = p; d[1] = m; d[2] = q;

@@ -11,8 +11,8 @@
 //     edge path   one sample per lane, at any alignment (deep formats: even).
 //   Nothing past the last sample of a frame is read.  The host part (checks, memset, launch shape, dispatch) is frames_sums_setup.
 // gsvc_msssim       per scale one launch of k_msssim_scale (32x32 outputs of the VALID 11-tap blur per workgroup: the 42x42 inputs
-//   of both pictures staged in LDS, the five moments blurred separably with the register blocking of ssim.hip, the window taps in
-//   vector registers for the reason given there) and, between scales, one launch of k_msssim_pool (2x2 mean, a leading zero row /
+//   of both pictures staged in LDS, the five moments blurred separably by the tile blur of ssim_tile.h, which the SSIM loss kernels
+//   share) and, between scales, one launch of k_msssim_pool (2x2 mean, a leading zero row /
 //   column for an odd side) — pooling is a kernel of its own: its windows start at -1 on an odd side and so do not tile with the
 //   blur's outputs.  A tile writes ONE float partial; k_msssim_finalize adds the partials of a (scale, plane) in a fixed order in
 //   double.  No float atomics: two runs give the same bits.
@@ -21,6 +21,8 @@
 //   subtracts two numbers near 0.5 to get one near 1e-4: that cancellation is the float32 error of the tensor-expression form
 //   (DESIGN section 8e).
 #include "frames_common.h"
+#include "reduce.h"
+#include "ssim_tile.h"
 
 #include <cmath>
 #include <type_traits>
@@ -110,30 +112,7 @@ __global__ void __launch_bounds__(256) k_frames_sse(SseArgs args)
 // ============================================================================================================================
 // fused MS-SSIM
 // ============================================================================================================================
-constexpr int MS_TILE = 32;
-constexpr int MS_TAPS = 11;
-constexpr int MS_HALO = MS_TILE + MS_TAPS - 1;   // 42 staged rows / columns for 32 valid outputs
-constexpr int MS_LD = 44;                        // row stride of the staged pictures: 16-byte groups of 4 columns
-constexpr int MS_HLD = MS_TILE + 1;              // row stride of the horizontally blurred moments
 constexpr int MS_SCALES = 5;
-constexpr float MS_C1 = 0.01f * 0.01f;
-constexpr float MS_C2 = 0.03f * 0.03f;
-
-struct MsWindow {
-    float w[MS_TAPS];
-};
-
-// the taps as vector registers (see window_in_vgprs in ssim.hip: an FMA reading an SGPR issues at 4.5 cycles per wave, 2.7 without)
-struct MsWinRegs {
-    float w[MS_TAPS];
-};
-__device__ __forceinline__ MsWinRegs ms_window_in_vgprs(const MsWindow &win)
-{
-    MsWinRegs r;
-#pragma unroll
-    for (int k = 0; k < MS_TAPS; k++) asm volatile("v_mov_b32 %0, %1" : "=v"(r.w[k]) : "s"(win.w[k]));
-    return r;
-}
 
 // a sample as a float: codes are DIVIDED by the peak (an IEEE float32 division = torch's uint -> float32 -> div(peak))
 template <typename T>
@@ -149,85 +128,45 @@ struct MsPicture {
     float peak;
 };
 
-__device__ __forceinline__ float ms_block_sum(float v, float *smem)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) smem[wave] = v;
-    __syncthreads();
-    return (smem[0] + smem[1]) + (smem[2] + smem[3]);
-}
-
 // one scale: partials[plane * tiles + tile] = the sum over the tile's valid outputs of the cs map (last = 0) or the SSIM map (last = 1)
 template <typename T>
-__global__ void __launch_bounds__(256) k_msssim_scale(MsWindow win_s, MsPicture pic, int H, int W, int last, float *__restrict__ partials)
+__global__ void __launch_bounds__(256) k_msssim_scale(SsimWindow win_s, MsPicture pic, int H, int W, int last, float *__restrict__ partials)
 {
-    __shared__ __attribute__((aligned(16))) float sx[MS_HALO][MS_LD];
-    __shared__ __attribute__((aligned(16))) float sy[MS_HALO][MS_LD];
-    __shared__ float hb[5][MS_HALO][MS_HLD];
+    __shared__ __attribute__((aligned(16))) float st[2][ST_HALO][ST_LD];   // the staged pictures: x, y
+    __shared__ float hb[5][ST_HALO][ST_HLD];
     __shared__ float red[4];
-    const MsWinRegs win = ms_window_in_vgprs(win_s);
+    const SsimWindow win = window_in_vgprs(win_s);
     const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * MS_TILE, y0 = blockIdx.y * MS_TILE;
-    const int Hv = H - (MS_TAPS - 1), Wv = W - (MS_TAPS - 1);       // the valid outputs
+    const int x0 = blockIdx.x * ST_TILE, y0 = blockIdx.y * ST_TILE;
+    const int Hv = H - (ST_TAPS - 1), Wv = W - (ST_TAPS - 1);       // the valid outputs
     const T *px = reinterpret_cast<const T *>(pic.x) + (size_t)blockIdx.z * (size_t)pic.x_plane;
     const T *py = reinterpret_cast<const T *>(pic.y) + (size_t)blockIdx.z * (size_t)pic.y_plane;
-    // every load of the tile is issued before the first is waited for (see k_ssim_fwd)
-    constexpr int MS_LOADS = (MS_HALO * MS_HALO + 255) / 256;
-    float xa[MS_LOADS], ya[MS_LOADS];
+    // the 42x42 inputs of the tile's valid outputs (no offset), zero past the picture
+    float v[ST_LOADS][2];
 #pragma unroll
-    for (int it = 0; it < MS_LOADS; it++) {
-        const int i = tid + 256 * it;
-        const int r = i / MS_HALO, c = i - r * MS_HALO;
+    for (int it = 0; it < ST_LOADS; it++) {
+        int r, c;
+        const bool live = tile_slot(it, r, c);
         const int gy = y0 + r, gx = x0 + c;
-        const bool in = i < MS_HALO * MS_HALO && gy < H && gx < W;
-        xa[it] = in ? ms_sample<T>(px, (size_t)gy * (size_t)pic.x_row + gx, pic.peak) : 0.f;
-        ya[it] = in ? ms_sample<T>(py, (size_t)gy * (size_t)pic.y_row + gx, pic.peak) : 0.f;
+        const bool in = live && gy < H && gx < W;
+        v[it][0] = in ? ms_sample<T>(px, (size_t)gy * (size_t)pic.x_row + gx, pic.peak) : 0.f;
+        v[it][1] = in ? ms_sample<T>(py, (size_t)gy * (size_t)pic.y_row + gx, pic.peak) : 0.f;
     }
-#pragma unroll
-    for (int it = 0; it < MS_LOADS; it++) {
-        const int i = tid + 256 * it;
-        const int r = i / MS_HALO, c = i - r * MS_HALO;
-        if (i < MS_HALO * MS_HALO) {
-            sx[r][c] = xa[it];
-            sy[r][c] = ya[it];
-        }
-    }
-    if (tid < 2 * MS_HALO) {      // the two pad columns the 16-byte reads touch (never used in arithmetic): keep them finite
-        sx[tid >> 1][MS_HALO + (tid & 1)] = 0.f;
-        sy[tid >> 1][MS_HALO + (tid & 1)] = 0.f;
-    }
+    store_tile(st, v);
     __syncthreads();
     // the centre of the staged part of the picture: one pixel of each picture, the same for the whole workgroup
-    const int rc = min(MS_HALO / 2, H - 1 - y0), cc = min(MS_HALO / 2, W - 1 - x0);
-    const float cx = sx[rc][cc], cy = sy[rc][cc];
+    const int rc = min(ST_HALO / 2, H - 1 - y0), cc = min(ST_HALO / 2, W - 1 - x0);
+    const float cx = st[0][rc][cc], cy = st[1][rc][cc];
     // horizontal pass: group g = (row r, outputs 4 cg .. 4 cg + 3 <- columns 4 cg .. 4 cg + 13)
-    for (int g = tid; g < MS_HALO * (MS_TILE / 4); g += 256) {
+    for (int g = tid; g < ST_GROUPS; g += 256) {
         const int r = g >> 3, c0 = 4 * (g & 7);
         if (y0 + r >= H || x0 + c0 >= Wv) continue;      // a row below the picture, outputs right of the last valid one
         float xv[16], yv[16];
+        staged_row16(st[0], r, c0, xv);
+        staged_row16(st[1], r, c0, yv);
 #pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const float4 a = *reinterpret_cast<const float4 *>(&sx[r][c0 + 4 * q]);
-            const float4 b = *reinterpret_cast<const float4 *>(&sy[r][c0 + 4 * q]);
-            xv[4 * q] = a.x - cx; xv[4 * q + 1] = a.y - cx; xv[4 * q + 2] = a.z - cx; xv[4 * q + 3] = a.w - cx;
-            yv[4 * q] = b.x - cy; yv[4 * q + 1] = b.y - cy; yv[4 * q + 2] = b.z - cy; yv[4 * q + 3] = b.w - cy;
-        }
-        float xx[14], yy[14], xy[14];
-#pragma unroll
-        for (int k = 0; k < 14; k++) { xx[k] = xv[k] * xv[k]; yy[k] = yv[k] * yv[k]; xy[k] = xv[k] * yv[k]; }
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f, a4 = 0.f;
-#pragma unroll
-            for (int k = 0; k < MS_TAPS; k++) {
-                const float w = win.w[k];
-                a0 = fmaf(w, xv[j + k], a0); a1 = fmaf(w, yv[j + k], a1); a2 = fmaf(w, xx[j + k], a2);
-                a3 = fmaf(w, yy[j + k], a3); a4 = fmaf(w, xy[j + k], a4);
-            }
-            hb[0][r][c0 + j] = a0; hb[1][r][c0 + j] = a1; hb[2][r][c0 + j] = a2; hb[3][r][c0 + j] = a3; hb[4][r][c0 + j] = a4;
-        }
+        for (int k = 0; k < 16; k++) { xv[k] -= cx; yv[k] -= cy; }
+        blur4_moments(win, xv, yv, hb, r, c0);
     }
     __syncthreads();
     // vertical pass: thread = (column lx, outputs 4 gq .. 4 gq + 3 <- rows 4 gq .. 4 gq + 13)
@@ -237,31 +176,20 @@ __global__ void __launch_bounds__(256) k_msssim_scale(MsWindow win_s, MsPicture 
     if (gx < Wv && y0 + 4 * gq < Hv) {
         float mom[5][4];
 #pragma unroll
-        for (int m = 0; m < 5; m++) {
-            float v[14];
-#pragma unroll
-            for (int k = 0; k < 14; k++) v[k] = hb[m][4 * gq + k][lx];
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                float a = 0.f;
-#pragma unroll
-                for (int k = 0; k < MS_TAPS; k++) a = fmaf(win.w[k], v[j + k], a);
-                mom[m][j] = a;
-            }
-        }
+        for (int m = 0; m < 5; m++) blur4_column(win, hb[m], 4 * gq, lx, mom[m]);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             if (y0 + 4 * gq + j < Hv) {          // (rows of hb below the picture were not written: their outputs are not taken)
                 const float m1 = mom[0][j], m2 = mom[1][j];
                 const float s1 = mom[2][j] - m1 * m1, s2 = mom[3][j] - m2 * m2, s12 = mom[4][j] - m1 * m2;
-                const float cs = (2.f * s12 + MS_C2) / (s1 + s2 + MS_C2);
+                const float cs = (2.f * s12 + SSIM_C2) / (s1 + s2 + SSIM_C2);
                 const float mu1 = m1 + cx, mu2 = m2 + cy;
-                const float lum = (2.f * mu1 * mu2 + MS_C1) / (mu1 * mu1 + mu2 * mu2 + MS_C1);
+                const float lum = (2.f * mu1 * mu2 + SSIM_C1) / (mu1 * mu1 + mu2 * mu2 + SSIM_C1);
                 sum += last ? lum * cs : cs;
             }
         }
     }
-    const float total = ms_block_sum(sum, red);
+    const float total = block_sum_256<SumOrder::Pairs, Slot::Once>(sum, red);
     if (tid == 0) partials[((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x] = total;
 }
 
@@ -316,19 +244,6 @@ __global__ void __launch_bounds__(256) k_msssim_finalize(MsFinalize f, const flo
     if (threadIdx.x == 0) out[(size_t)scale * P + plane] = red[0] * f.inv_count[scale];
 }
 
-static MsWindow ms_make_window()
-{
-    // exp(-(i - 5)^2 / (2 * 1.5^2)) normalised, in double, each tap rounded once to float
-    MsWindow w;
-    double g[MS_TAPS], s = 0.0;
-    for (int i = 0; i < MS_TAPS; i++) {
-        g[i] = std::exp(-(double)((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5));
-        s += g[i];
-    }
-    for (int i = 0; i < MS_TAPS; i++) w.w[i] = (float)(g[i] / s);
-    return w;
-}
-
 struct MsLayout {
     int h[MS_SCALES], w[MS_SCALES], tx[MS_SCALES], ty[MS_SCALES];
     int64_t pyr[MS_SCALES];            // byte offset of scale s's pooled x pictures (s >= 1); y follows x
@@ -345,8 +260,8 @@ static MsLayout ms_layout(int32_t P, int32_t H, int32_t W)
     for (int s = 0; s < MS_SCALES; s++) {
         L.h[s] = h;
         L.w[s] = w;
-        L.tx[s] = (w - (MS_TAPS - 1) + MS_TILE - 1) / MS_TILE;
-        L.ty[s] = (h - (MS_TAPS - 1) + MS_TILE - 1) / MS_TILE;
+        L.tx[s] = (w - (ST_TAPS - 1) + ST_TILE - 1) / ST_TILE;
+        L.ty[s] = (h - (ST_TAPS - 1) + ST_TILE - 1) / ST_TILE;
         L.pyr[s] = at;
         if (s > 0) at += (int64_t)align_up((uint64_t)2 * P * h * w * sizeof(float), 256);
         L.part_off[s] = parts;
@@ -365,7 +280,7 @@ static bool ms_shape_ok(int32_t P, int32_t H, int32_t W)
 }
 
 template <typename T>
-static void ms_launch_first(const MsWindow &win, const MsPicture &pic, const MsLayout &L, int32_t P, float *pyr1, float *partials,
+static void ms_launch_first(const SsimWindow &win, const MsPicture &pic, const MsLayout &L, int32_t P, float *pyr1, float *partials,
                             hipStream_t s)
 {
     {
@@ -427,7 +342,7 @@ extern "C" int gsvc_msssim(const void *x, int64_t x_row_pitch, int64_t x_plane_p
     GSVC_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 7) == 0,
                  "msssim: the workspace must be 16-byte and out 8-byte aligned");
     const MsLayout L = ms_layout(P, H, W);
-    static const MsWindow win = ms_make_window();
+    static const SsimWindow win = make_msssim_window();
     hipStream_t s = (hipStream_t)stream;
     uint8_t *ws = reinterpret_cast<uint8_t *>(workspace);
     float *partials = reinterpret_cast<float *>(ws + L.partials);
@@ -469,7 +384,7 @@ extern "C" int gsvc_msssim(const void *x, int64_t x_row_pitch, int64_t x_plane_p
     for (int k = 0; k < MS_SCALES; k++) {
         f.offset[k] = L.part_off[k];
         f.tiles[k] = L.tx[k] * L.ty[k];
-        f.inv_count[k] = 1.0 / ((double)(L.h[k] - (MS_TAPS - 1)) * (double)(L.w[k] - (MS_TAPS - 1)));
+        f.inv_count[k] = 1.0 / ((double)(L.h[k] - (ST_TAPS - 1)) * (double)(L.w[k] - (ST_TAPS - 1)));
     }
     {
         ProfScope _p("k_msssim_finalize", s);

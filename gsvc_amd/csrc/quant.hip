@@ -7,6 +7,7 @@
 // In PyTorch that is ~25 small launches per tensor and direction (segment means through index_add, broadcasts, clamp with
 // tensor bounds); here: one reduction (+ a one-block finalize), one elementwise forward, one backward.
 #include "common.h"
+#include "reduce.h"
 
 namespace gsvc {
 
@@ -25,22 +26,6 @@ __device__ __forceinline__ int q_render_of(const QSeg &seg, long long row)
     return r;
 }
 
-__device__ __forceinline__ float q_wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-__device__ __forceinline__ float q_block_sum(float v, float *red)
-{
-    v = q_wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
 // part[(r*nbx + bx)*2 + {0,1}] = block sums of x (all columns) and of q over 64-row slabs of render r
 __global__ void __launch_bounds__(256) k_quant_sums(const float *__restrict__ x, const float *__restrict__ q, QSeg seg, int C,
                                                     float *__restrict__ part)
@@ -54,8 +39,8 @@ __global__ void __launch_bounds__(256) k_quant_sums(const float *__restrict__ x,
         for (long long e = e0 + threadIdx.x; e < e1; e += 256) sx += x[e];
         if (q && row0 + threadIdx.x < row1) sq = q[row0 + threadIdx.x];
     }
-    sx = q_block_sum(sx, red);
-    sq = q_block_sum(sq, red);
+    sx = block_sum_256<SumOrder::Chain>(sx, red);
+    sq = block_sum_256<SumOrder::Chain>(sq, red);
     if (threadIdx.x == 0) {
         float *d = part + ((size_t)r * gridDim.x + blockIdx.x) * 2;
         d[0] = sx; d[1] = sq;
@@ -73,8 +58,8 @@ __global__ void __launch_bounds__(256) k_quant_centre(const float *__restrict__ 
             sx += part[((size_t)r * nbx + b) * 2];
             sq += part[((size_t)r * nbx + b) * 2 + 1];
         }
-        sx = q_block_sum(sx, red);
-        sq = q_block_sum(sq, red);
+        sx = block_sum_256<SumOrder::Chain>(sx, red);
+        sq = block_sum_256<SumOrder::Chain>(sq, red);
         if (threadIdx.x == 0) {
             const float rows = (float)(seg.off[r + 1] - seg.off[r]);
             const float xm = sx / fmaxf(rows * (float)C, 1.f);
@@ -161,8 +146,7 @@ __global__ void __launch_bounds__(256) k_ste_binary_count(const float *__restric
         y[i] = pos ? 1.0f : -1.0f;
         c += pos ? 1.f : 0.f;
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(count, (red[0] + red[1]) + (red[2] + red[3]));      // integer-valued sums below 2^24: exact
@@ -212,8 +196,7 @@ __global__ void __launch_bounds__(256) k_ste_binary_count_many(SteTables t, floa
             c += pos ? 1.f : 0.f;
         }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
+    c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
     __syncthreads();
     if (threadIdx.x == 0) atomicAdd(counts + k, (red[0] + red[1]) + (red[2] + red[3]));      // integer-valued sums below 2^24: exact
@@ -264,7 +247,7 @@ __global__ void __launch_bounds__(256) k_ste_bounds(const float *__restrict__ pa
     for (int r = 0; r < seg.R; r++) {
         float sq = 0.f;
         for (int b = threadIdx.x; b < nbx; b += 256) sq += part[((size_t)r * nbx + b) * 2 + 1];
-        sq = q_block_sum(sq, red);
+        sq = block_sum_256<SumOrder::Chain>(sq, red);
         if (threadIdx.x == 0) {
             const float rows = (float)(seg.off[r + 1] - seg.off[r]);
             const float qm = has_q ? sq / fmaxf(rows, 1.f) : q_scalar;

@@ -13,6 +13,7 @@
 //                    conic -> 2-D covariance -> 3-D covariance -> (scale, quaternion),
 //                    screen-space -> world mean (constant orthographic Jacobian, no covariance->mean term).
 #include "raster_common.h"
+#include "reduce.h"
 
 #include <cstdlib>
 #include <type_traits>
@@ -380,10 +381,7 @@ __global__ void __launch_bounds__(64, AUX ? GSVC_BWD_AUX_WAVES : GSVC_BWD_WAVES)
         p.tb = ZERO_BG ? 0.f : Tf[q] * (st.bg0 * p.d0 + st.bg1 * p.d1 + st.bg2 * p.d2);
         p.T = Tf[q];
         p.bd = 0.f;
-        int m = p.last;
-#pragma unroll
-        for (int k = 32; k >= 1; k >>= 1) m = max(m, __shfl_xor(m, k, 64));
-        wl[q] = __builtin_amdgcn_readfirstlane(m);
+        wl[q] = __builtin_amdgcn_readfirstlane(wave_max(p.last));
     }
     const int tile_last = max(max(wl[0], wl[1]), max(wl[2], wl[3]));
 
@@ -712,9 +710,7 @@ __global__ void __launch_bounds__(256) k_gaussian_bwd(RasterParams st, int P, co
             }
         }
 #pragma unroll
-        for (int c = 0; c < NS; c++)
-#pragma unroll
-            for (int k = 32; k >= 1; k >>= 1) v[c] += __shfl_xor(v[c], k, 64);
+        for (int c = 0; c < NS; c++) v[c] = wave_sum(v[c]);
         if (lane == src) {
             a0 = make_float4(v[0], v[1], v[2], v[3]);
             a1 = make_float4(v[4], v[5], v[6], v[7]);

@@ -25,6 +25,7 @@
 //                   nothing in the spec either); survivors are compacted into a wave-private LDS strip and
 //                   composited front to back from LDS broadcast reads by a branch-free inner loop.
 #include "raster_common.h"
+#include "reduce.h"
 
 #include <cstdlib>
 
@@ -130,8 +131,8 @@ __device__ __forceinline__ void scan_tiles_body(int T, const int32_t *__restrict
                                                 gsvc_raster_counters *__restrict__ counters, long long max_instances,
                                                 int *__restrict__ s_v, int api_count_in_reserved2 = 0)
 {
-    __shared__ int wave_sum[16];
-    __shared__ int wave_max[16];
+    __shared__ int s_wave_sum[16];
+    __shared__ int s_wave_max[16];
     __shared__ int s_big;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (tid == 0) s_big = 0;
@@ -161,11 +162,11 @@ __device__ __forceinline__ void scan_tiles_body(int T, const int32_t *__restrict
             const int y = __shfl_up(x, d, 64);
             if (lane >= d) x += y;
         }
-        if (lane == 63) wave_sum[wave] = x;
+        if (lane == 63) s_wave_sum[wave] = x;
         __syncthreads();
         int prefix = carry, total = 0;
         for (int w = 0; w < 16; w++) {
-            const int ws = wave_sum[w];
+            const int ws = s_wave_sum[w];
             if (w < wave) prefix += ws;
             total += ws;
         }
@@ -186,13 +187,12 @@ __device__ __forceinline__ void scan_tiles_body(int T, const int32_t *__restrict
             }
         }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) local_max = max(local_max, __shfl_xor(local_max, m, 64));
-    if (lane == 0) wave_max[wave] = local_max;
+    local_max = wave_max(local_max);
+    if (lane == 0) s_wave_max[wave] = local_max;
     __syncthreads();
     if (tid == 0) {
         int mx = 0;
-        for (int w = 0; w < 16; w++) mx = max(mx, wave_max[w]);
+        for (int w = 0; w < 16; w++) mx = max(mx, s_wave_max[w]);
         tile_offsets[T] = carry;
         // GSVC_RASTER_TIGHT_BINNING: the lists are shorter than the API's count (the 3-sigma rectangles' tiles, summed by K1)
         counters->num_rendered = api_count_in_reserved2 ? __hip_atomic_load(&counters->reserved[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : carry;
@@ -458,6 +458,7 @@ __global__ void __launch_bounds__(1024) k_preprocess(RasterParams st, int P, con
         __syncthreads();
         const unsigned long long vm = __ballot(radius > 0);
         if ((tid & 63) == 0 && vm != 0ull) atomicAdd(&s_vis, __popcll(vm));
+        // (the two sums are not wave_sum of reduce.h: through it one instantiation of this kernel takes 43 VGPRs, not 42)
         int ne = n_extra;
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) ne += __shfl_xor(ne, m, 64);
@@ -836,11 +837,8 @@ __device__ __forceinline__ bool bucket_rank(const uint64_t *__restrict__ s, int 
             dmin = fminf(dmin, d); dmax = fmaxf(dmax, d);
         }
     }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        dmin = fminf(dmin, __shfl_xor(dmin, m, 64));
-        dmax = fmaxf(dmax, __shfl_xor(dmax, m, 64));
-    }
+    dmin = wave_min(dmin);
+    dmax = wave_max(dmax);
     const float span = dmax - dmin;
     const float scale = span > 0.f ? 255.0f / span : 0.f;      // (NaN / inf depths never reach a tile list)
     uint32_t *cnt = scr;                                        // [256] counts; the same bytes hold the index list afterwards
@@ -863,9 +861,7 @@ __device__ __forceinline__ bool bucket_rank(const uint64_t *__restrict__ s, int 
     uint32_t c[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) c[q] = cnt[4 * lane + q];
-    uint32_t big = max(max(c[0], c[1]), max(c[2], c[3]));
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) big = max(big, (uint32_t)__shfl_xor((int)big, m, 64));
+    const uint32_t big = wave_max(max(max(c[0], c[1]), max(c[2], c[3])));
     if (big > (uint32_t)BUCKET_MAX) return false;
     const uint32_t tot = (c[0] + c[1]) + (c[2] + c[3]);
     uint32_t inc = tot;

@@ -10,6 +10,7 @@
 // one partial per workgroup (a float pair) in the caller's scratch, added up in fixed order by a one-workgroup
 // second stage and rounded to float once — the same bits every run, whatever order the workgroups finish in.
 #include "common.h"
+#include "reduce.h"
 
 namespace gsvc {
 
@@ -25,16 +26,6 @@ __device__ __forceinline__ float normal_cdf(float v, float mu, float inv_sigma)
 }
 
 constexpr int RATE_FWD_BLOCKS = 2048;
-
-__device__ __forceinline__ double block_sum_256d(double v, double *smem)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) smem[wave] = v;
-    __syncthreads();
-    return (smem[0] + smem[1]) + (smem[2] + smem[3]);
-}
 
 // SUM: the workgroup's (weighted) sum goes to part[2 * blockIdx.x] as a float pair (high part, remainder)
 template <bool SUM>
@@ -62,7 +53,7 @@ __global__ void __launch_bounds__(256) k_rate_fwd(const float *__restrict__ x, c
         if (SUM) acc += weight ? (double)b * (double)weight[i] : (double)b;
     }
     if (SUM) {
-        const double s = block_sum_256d(acc, smem);
+        const double s = block_sum_256<SumOrder::Pairs, Slot::Once>(acc, smem);
         if (threadIdx.x == 0) {
             const float h = (float)s;
             part[2 * blockIdx.x] = h;
@@ -77,7 +68,7 @@ __global__ void __launch_bounds__(256) k_rate_fwd_sum(const float *__restrict__ 
     __shared__ double smem[4];
     double acc = 0.0;
     for (int b = threadIdx.x; b < blocks; b += 256) acc += (double)part[2 * b] + (double)part[2 * b + 1];
-    const double s = block_sum_256d(acc, smem);
+    const double s = block_sum_256<SumOrder::Pairs, Slot::Once>(acc, smem);
     if (threadIdx.x == 0) *bits_sum = (float)((double)*bits_sum + s);
 }
 
@@ -124,8 +115,7 @@ __global__ void __launch_bounds__(256) k_rate_bwd(const float *__restrict__ x, c
             dq_acc += dl * 0.5f * (pu + pl);
         }
         if (dQ) {
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) dq_acc += __shfl_xor(dq_acc, m, 64);
+            dq_acc = wave_sum(dq_acc);
             if (lane == 0) dQ[row] += dq_acc;
         }
     }
@@ -183,9 +173,7 @@ __global__ void __launch_bounds__(256) k_rate_sample_stats(RateSampleArgs a, flo
     for (int r = 0; r < a.R; r++)
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            float v = acc[r][j];
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+            const float v = wave_sum(acc[r][j]);
             if (lane == 0) sm[wave][r][j] = v;
         }
     __syncthreads();
@@ -265,12 +253,10 @@ __global__ void __launch_bounds__(256) k_rate_sample(RateSampleArgs a, const flo
             }
         }
         if (MODE == 0) {
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) row_acc += __shfl_xor(row_acc, m, 64);
+            row_acc = wave_sum(row_acc);
             if (lane == 0) sacc[wave][r] += row_acc;          // the wave's own slot, rows in the wave's loop order
         } else if (DQ) {
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) dq_acc += __shfl_xor(dq_acc, m, 64);
+            dq_acc = wave_sum(dq_acc);
             if (lane == 0) DQ[srow] = dq_acc;
         }
     }
@@ -347,8 +333,7 @@ __global__ void __launch_bounds__(256) k_param_means_part(const float *__restric
     if (blk < fb) v = pm_stream_sum<false>(a, na, blk, fb);
     else if (blk < fc) v = b_exp ? pm_stream_sum<true>(b, nb, blk - fb, fc - fb) : pm_stream_sum<false>(b, nb, blk - fb, fc - fb);
     else v = pm_stream_sum<false>(c, nc, blk - fc, (int)gridDim.x - fc);
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    v = wave_sum(v);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     if (threadIdx.x == 0) part[blk] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -433,8 +418,7 @@ __global__ void __launch_bounds__(256) k_rate_normalise(const float *__restrict_
     for (int r = 0; r < R; r++) {
         int v = 0;
         for (int b = t; b < blocks; b += 256) v += part[b * RS_MAX_R + r];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+        v = wave_sum(v);
         if ((t & 63) == 0 && v) atomicAdd(&live_s[r], v);
     }
     if (t <= R) edge[t] = rn_lower_bound(sel, n_sel, rb.b[t]);      // the R + 1 searches side by side

@@ -108,7 +108,7 @@ def l2_loss_func(network_output, gt):
 @lru_cache(maxsize=4)
 def _window_1d(window_size: int, sigma: float):
     g = torch.tensor([exp(-(x - window_size // 2) ** 2 / float(2 * sigma ** 2)) for x in range(window_size)])
-    # the taps of make_window() in csrc/ssim.hip, bit for bit: the fp32 taps are added one by one in fp32.  (g.sum() adds them in
+    # the taps of make_loss_window() in csrc/ssim_tile.h, bit for bit: the fp32 taps are added one by one in fp32.  (g.sum() adds them in
     # another order; for 11 taps at sigma 1.5 its sum is one ulp larger and nine of the taps come out one ulp smaller.)
     s = g[0]
     for t in g[1:]:

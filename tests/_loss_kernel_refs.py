@@ -19,7 +19,7 @@ CLAMP_STEPS = 15000.0
 
 # ------------------------------------------------------------------------------------------------------------ SSIM / L1
 def ssim_window():
-    """The eleven fp32 taps as make_window() of csrc/ssim.hip builds them: exp(-(i - 5)^2 / (2 * 1.5^2)) in double, each tap rounded
+    """The eleven fp32 taps as make_loss_window() of csrc/ssim_tile.h builds them: exp(-(i - 5)^2 / (2 * 1.5^2)) in double, each tap rounded
     to float, divided by the float sum (the rounded taps added one by one in float, in tap order).  The taps are an input of the
     operation: a float64 reference uses these fp32 values cast up."""
     g = [np.float32(math.exp(-float((i - 5) * (i - 5)) / (2.0 * 1.5 * 1.5))) for i in range(11)]
