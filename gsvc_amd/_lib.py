@@ -270,6 +270,7 @@ _SIGNATURES = {
     "gsvc_msssim_workspace_bytes": (_i64, [C.c_int32, C.c_int32, C.c_int32]),
     "gsvc_msssim": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _vp, _vp, _vp]),
     "gsvc_picture_hash": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "gsvc_frames_histogram": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "gsvc_flow_workspace_bytes": (_i64, [C.c_int32] * 5),
     "gsvc_flow_estimate": (C.c_int, [_vp, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _vp,
                                      _vp, _vp]),

@@ -17,6 +17,8 @@ VERSION is refused.  Sections of version 1:
     PHSH   optional: the name of the FrameFormat the hashes were taken in (+ matrix, range, rounding) and uint64 [frames, 3] picture
            hashes (``metrics.picture_hash``: include/gsvc_hip.h, gsvc_picture_hash)
 
+A clip of several groups of pictures is a sequence file of such file images: gsvc_amd/sequence.py.
+
 ``write_bitstream`` / ``read_bitstream`` need neither a GPU nor the built library; ``Bitstream.build_model`` and ``decode_video`` do.
 Nothing here reads the source video or the trainer.
 """

@@ -1,8 +1,8 @@
-// gsvc_amd/csrc/frames_common.h — what frames_out.hip, frames_in.hip, metrics.hip (plane SSE) and picture_hash.hip share: the frame
-// format stated once.
+// gsvc_amd/csrc/frames_common.h — what frames_out.hip, frames_in.hip, metrics.hip (plane SSE), picture_hash.hip and scene.hip share: the
+// frame format stated once.
 //   host     the argument checks of the six entries (their texts carry the entry's name), the colour matrix and the range constants as
-//            functions of (matrix) and (range, depth), the gather of a batch's image pointers, and the host part of the two per-plane
-//            sums (gsvc_frames_sse, gsvc_picture_hash): checks, memset, launch shape, dispatch;
+//            functions of (matrix) and (range, depth), the gather of a batch's image pointers, and the host part of the per-plane
+//            sums (gsvc_frames_sse, gsvc_picture_hash, gsvc_frames_histogram): checks, memset, launch shape, dispatch;
 //   device   sample codes out of loaded words, vector loads and stores by byte count, and the 64-bit three-plane workgroup reduction of
 //            the two per-plane sums.  (Their walks over a frame's samples stay two bodies of one shape, k_frames_sse and
 //            k_picture_hash: as one template over the per-sample work the 8-bit wide instantiations took 74 - 108 registers
@@ -233,16 +233,18 @@ __device__ __forceinline__ void add_block_sums(unsigned long long acc[3], unsign
     }
 }
 
-// ---- host part of the two sums: checks, the zeroed out[n, 3], the run of samples and the launch shape ------------------------------
+// ---- host part of the sums: checks, the zeroed out[n, out_per_frame] of out_elem-byte integers (uint64 [n, 3] for the two 64-bit
+//      sums, uint32 [n, 768] for the histograms), the run of samples and the launch shape -------------------------------------------
 struct FrameSums {
     SampleRun run;
     int variant;          // 0 rgb24, 1 8-bit planar, 2 deep planar: the row of GSVC_FRAME_SUMS_KERNELS
     bool wide;
-    dim3 grid;
+    int64_t units;        // what the lanes share out: whole units, then the samples behind them (wide), or samples (edge)
+    dim3 grid;            // SUMS_PER_LANE of them per lane (the histogram takes more per workgroup and sets its own)
 };
 
 inline int frames_sums_setup(const char *who, const FrameBufs &bufs, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t depth,
-                             uint64_t *out, hipStream_t s, FrameSums &fs)
+                             void *out, hipStream_t s, FrameSums &fs, int out_elem = 8, int out_per_frame = 3)
 {
     GSVC_FRAMES_TRY(frames_check_format(who, n, 65535, layout, depth, 8, 16));
     GSVC_FRAMES_TRY(frames_check_size(who, H, W, layout));
@@ -250,8 +252,8 @@ inline int frames_sums_setup(const char *who, const FrameBufs &bufs, int32_t n, 
     GSVC_FRAMES_TRY(frames_check_strides(who, bufs, bytes));
     const bool deep = depth > 8, rgb = layout == GSVC_FRAMES_RGB24;
     if (deep) GSVC_FRAMES_TRY(frames_check_even(who, bufs));
-    GSVC_REQUIRE((reinterpret_cast<uintptr_t>(out) & 7) == 0, "%s: out is not 8-byte aligned", who);
-    if (hipMemsetAsync(out, 0, (size_t)n * 3 * sizeof(uint64_t), s) != hipSuccess) {
+    GSVC_REQUIRE((reinterpret_cast<uintptr_t>(out) & (uintptr_t)(out_elem - 1)) == 0, "%s: out is not %d-byte aligned", who, out_elem);
+    if (hipMemsetAsync(out, 0, (size_t)n * (size_t)out_per_frame * (size_t)out_elem, s) != hipSuccess) {
         set_error("%s: hipMemsetAsync failed", who);
         return GSVC_E_LAUNCH;
     }
@@ -266,6 +268,7 @@ inline int frames_sums_setup(const char *who, const FrameBufs &bufs, int32_t n, 
         const int64_t spu = rgb ? 48 : (deep ? 8 : 16);
         units = fs.run.samples / spu + fs.run.samples % spu;          // whole units, then the samples behind them one by one
     }
+    fs.units = units;
     const int64_t per_block = 256 * SUMS_PER_LANE;
     fs.grid = dim3((unsigned)((units + per_block - 1) / per_block), (unsigned)n);
     return GSVC_OK;

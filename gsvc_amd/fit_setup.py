@@ -1,5 +1,6 @@
 """The set-up of a fit that tools/fit_synthetic.py and tools/gsvc_encode.py share: the reference's 40 000-iteration schedule scaled to
-a run's length, and the model, its initial anchors and the Trainer on a frame cube.
+a run's length, the model, its initial anchors and the Trainer on a frame cube, and ``encode_gop``: a range of frames of a video file
+fitted, stream-encoded and verified into the bytes of one bitstream file (a whole clip, or one group of pictures of a sequence file).
 
 The reference's schedule (pipeline/train.py:325-583: 10 k full precision / 5 k quantised / 20 k entropy-constrained / 5 k
 straight-through; statistics from 500, densification 1 500 .. 25 000 every 100, paused 1 000 iterations at the first phase change) is
@@ -49,3 +50,64 @@ def new_fit(cube, mp_, opt, pipe, anchors: int, device):
     gdist.broadcast_parameters(pc)
     trainer = Trainer(pc, cube, opt, pipe, mp_, seed=0)
     return pc, trainer
+
+
+def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float = 0.004, anchors: int = 100_000, slab_frames: float = 16.0,
+               densify_grad_threshold=None, estimate_flow: bool = False, flow_dir=None, video_size=(None, None), video_format=None,
+               hash_format=None):
+    """One group of pictures of a video file -> ``(the bytes of a complete GSVC file, log)``: what tools/gsvc_encode.py does with a whole
+    clip, for the frames ``frame_range = (first, stop)`` of it (None: all).  VideoFileCube (optionally with the flow estimated from the
+    frames) -> the fit -> ``conduct_stream_encoding`` with 8-bit MLPs -> the file image; that image is then decoded into a null sink by
+    the function, batch size and format the decoder will use (``decode_video``), which yields the picture hashes it is given as its PHSH
+    section.  The trainer, the cube and the model are released before this returns.  ``log``: {"W", "H", "frames", "steps",
+    "anchors_coded", "fit_seconds", "hash_format", "verify_decode_fps", "sections"}."""
+    import gc
+    import os
+    import tempfile
+    import time
+
+    from .arguments import cfg_20240919
+    from .bitstream import CubeGeometry, NullSink, bitstream_bytes, decode_video, parse_bitstream, unpack_sections, with_hashes
+    from .frames_in import VideoFileCube
+    from .frames_out import FrameFormat
+    from .stream_codec import conduct_stream_encoding
+    mp_, opt, pipe = cfg_20240919()
+    cube = VideoFileCube(video, optical_flow_dir=flow_dir, W=video_size[0], H=video_size[1], fmt=video_format, device=device,
+                         frame_range=frame_range)
+    log = {"W": cube.width, "H": cube.height, "frames": cube.len_z_frames, "steps": int(steps)}
+    geometry_source = cube
+    if estimate_flow:
+        from .flow import EstimatedFlowCube
+        cube = EstimatedFlowCube(cube, device=device)
+    elif flow_dir is None:
+        opt.optical_lambda = 0.0
+    configure_fit(mp_, opt, cube, steps, lmbda, slab_frames, densify_grad_threshold)
+    pc, trainer = new_fit(cube, mp_, opt, pipe, anchors, device)
+    bg = trainer.background
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for it in range(1, int(steps) + 1):
+        trainer.step(it)
+    torch.cuda.synchronize()
+    log["fit_seconds"] = time.perf_counter() - t0
+    trainer.sync_replicas()
+    trainer.close()
+    with torch.no_grad(), tempfile.TemporaryDirectory() as tmp:
+        mlp_file = os.path.join(tmp, "mlp.bin")
+        pack = conduct_stream_encoding(pc, mlp_file=mlp_file)          # (quantises the MLPs of pc in place: the shipped form)
+        with open(mlp_file, "rb") as f:
+            mlp_bytes = f.read()
+    blob = bitstream_bytes(pc, pack, CubeGeometry.of(geometry_source, mp_, pipe, bg.tolist()), mlp_bytes)
+    log["anchors_coded"] = int(pack.n)
+    # the decoder's own path on the file image: the hashes are those of the pictures IT produces
+    del trainer, cube, geometry_source, pc, pack
+    gc.collect()
+    fmt = hash_format or FrameFormat("yuv420p")
+    res = decode_video(parse_bitstream(blob), NullSink(), fmt=fmt, verify=True, device=device)
+    blob = with_hashes(blob, fmt, res["hashes"])
+    del res["hashes"]
+    gc.collect()
+    torch.cuda.empty_cache()
+    log["hash_format"], log["verify_decode_fps"] = fmt.name, res["fps"]
+    log["sections"] = {t.decode("ascii"): len(p) for t, p in unpack_sections(blob)}
+    return blob, log

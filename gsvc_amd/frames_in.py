@@ -141,10 +141,15 @@ class VideoFileCube:
                             Two limits: a conversion is remembered through the tensor its ``Frame`` carries — a reader that keeps
                             only another view of the picture must order itself —, and every fetch converts and allocates 12 H W
                             bytes, also one whose picture is never read (a batched ``Trainer`` step fetches its pair twice: four
-                            conversions per step where two are read)."""
+                            conversions per step where two are read).
+
+    ``frame_range=(first, stop)``: the cube of the file's frames ``first .. stop - 1`` alone (one group of pictures of a long clip,
+    gsvc_amd/scene.py): only those frames are uploaded, frame i of the cube is file frame ``first + i``, and ``len``, ``scale``,
+    ``x_min``, ``y_min`` and ``z_min`` are those of a clip of ``stop - first`` frames; the flow files used are those of the pairs
+    inside the range.  None: all frames."""
 
     def __init__(self, path, optical_flow_dir=None, W: int | None = None, H: int | None = None, fmt: FrameFormat | None = None,
-                 chroma: str = "bilinear", device="cuda", resident: str = "float"):
+                 chroma: str = "bilinear", device="cuda", resident: str = "float", frame_range=None):
         import pathlib
 
         import torch
@@ -157,11 +162,24 @@ class VideoFileCube:
         self.height, self.width, self.len = int(self.header["H"]), int(self.header["W"]), int(frames.shape[0])
         if self.len < 1:
             raise ValueError(f"{self.path}: no frames")
+        self.frame_range = None
+        if frame_range is not None:
+            try:
+                first, stop = (int(v) for v in frame_range)
+            except (TypeError, ValueError):
+                raise ValueError(f"VideoFileCube: frame_range must be (first, stop) (got {frame_range!r})") from None
+            if not 0 <= first < stop <= self.len:
+                raise ValueError(f"VideoFileCube: frame_range ({first}, {stop}) is not a non-empty range inside the {self.len} frames of "
+                                 f"{self.path}")
+            self.frame_range = (first, stop)
+            frames, self.len = frames[first:stop], stop - first
         self.scale = max(self.height, self.width, self.len) / 2
         self.x_min = -self.width / 2 / self.scale
         self.y_min = -self.height / 2 / self.scale
         self.z_min = -self.len / 2 / self.scale
         self.optical_flow_paths = sorted(pathlib.Path(optical_flow_dir).iterdir()) if optical_flow_dir is not None else []
+        if self.frame_range is not None:
+            self.optical_flow_paths = self.optical_flow_paths[self.frame_range[0]:self.frame_range[1] - 1]
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.GsvcError("VideoFileCube converts its frames with the HIP kernels of csrc/frames_in.hip; it needs a CUDA device")

@@ -10,7 +10,9 @@ LPIPS: gsvc_amd/lpips.py (needs a weights file).  Plain torch ops: these run a f
 
 The metrics a video codec is judged by run as kernels (csrc/metrics.hip; formulas in include/gsvc_hip.h): ``plane_sse`` and
 ``code_metrics`` take PSNR-Y / -U / -V on the sample CODES of two frame buffers, ``ms_ssim_fused`` is ``ms_ssim`` in ten launches,
-``compare_videos`` compares two video files, and ``picture_hash`` (csrc/picture_hash.hip) is the per-plane hash a bitstream file carries.  These need the built library and a GPU (no CPU fallback); importing this module does not.
+``compare_videos`` compares two video files, ``picture_hash`` (csrc/picture_hash.hip) is the per-plane hash a bitstream file carries and
+``plane_histograms`` (csrc/scene.hip) the per-plane code histogram the scene-cut detector reads.  These need the built library and a GPU
+(no CPU fallback); importing this module does not.
 """
 from __future__ import annotations
 
@@ -141,6 +143,22 @@ def picture_hash(frames_u8, H: int, W: int, fmt) -> torch.Tensor:
     with torch.cuda.device(a.device):
         _lib.check(_lib.lib().gsvc_picture_hash(a.data_ptr(), sa, n, H, W, LAYOUTS[fmt.layout], fmt.depth, out.data_ptr(),
                                                 _lib.current_stream(a.device)), "gsvc_picture_hash")
+    return out
+
+
+def plane_histograms(frames_u8, H: int, W: int, fmt) -> torch.Tensor:
+    """The code histogram of every frame and plane of a buffer of delivered frames (what ``picture_hash`` accepts) -> int32
+    ``[n, 3, 256]`` on their device: ``out[f, p, b]`` counts the samples of plane ``p`` (``rgb24``: channel ``p``) of frame ``f`` with
+    ``min(code >> (depth - 8), 255) == b`` (include/gsvc_hip.h, gsvc_frames_histogram; csrc/scene.hip).  What ``scene.histogram_distance``
+    reads.  One launch and the memset on the current stream; nothing synchronises."""
+    from .frames_out import LAYOUTS, frame_bytes
+    H, W = int(H), int(W)
+    nbytes = frame_bytes(H, W, fmt)
+    a, n, sa = _frame_rows(frames_u8, nbytes, fmt, "plane_histograms")
+    out = torch.empty((n, 3, 256), dtype=torch.int32, device=a.device)
+    with torch.cuda.device(a.device):
+        _lib.check(_lib.lib().gsvc_frames_histogram(a.data_ptr(), sa, n, H, W, LAYOUTS[fmt.layout], fmt.depth, out.data_ptr(),
+                                                    _lib.current_stream(a.device)), "gsvc_frames_histogram")
     return out
 
 

@@ -1037,6 +1037,20 @@ int gsvc_picture_hash(const uint8_t *frames, int64_t stride, int32_t n, int32_t 
                       uint64_t *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * [INTERNAL] Per-plane code histograms of delivered frames (csrc/scene.hip): what the scene-cut detector reads.
+ *
+ * gsvc_frames_histogram: out[k, p, b] (uint32 [n, 3, 256], 4-byte aligned) = the number of samples of plane p of frame k of a buffer of
+ * delivered frames (frame k starts at frames + k * stride) whose code c falls in bin
+ *     b = min(c >> (depth - 8), 255)
+ * The min keeps a deep sample with bits above its depth inside the 256 bins (it counts in bin 255).  The bins of a plane add up to
+ * the plane's samples (at most 2^30).  Sums of integers: the same bits in every run and for every launch shape.
+ *   layout, depth, and what is refused before any launch: as gsvc_picture_hash (rgb24: p = the channel); out must be 4-byte aligned.
+ * Bytes between frames are not read.  The call zeroes out on the stream and does not synchronise.
+ * ---------------------------------------------------------------------------------------------------- */
+int gsvc_frames_histogram(const uint8_t *frames, int64_t stride, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t depth,
+                          uint32_t *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Dense optical flow of adjacent frames (csrc/flow.hip): coarse-to-fine Horn-Schunck with warping.  No weights, stencils only: the
  * same bits in every run, for every batch size and launch geometry.
  *

@@ -2,6 +2,11 @@
 """Decode a bitstream file (tools/gsvc_encode.py; gsvc_amd/bitstream.py) to a video.  The file is all it reads:
 
     python tools/gsvc_decode.py clip.gsvc -o out.y4m [--format yuv420p10le] [--no-verify | --strict]
+    python tools/gsvc_decode.py long.gsvs -o part.y4m --frames 300:364
+
+The file is a bitstream file (magic GSVC) or a sequence file of several groups of pictures (magic GSVS; gsvc_amd/sequence.py, DESIGN.md
+section 8h), decoded GOP by GOP with one GOP's model resident.  --frames A:B decodes the frames A .. B - 1 alone: only the GOPs that
+hold them are read and built.
 
 -o: .y4m / .yuv (yuv420p unless --format says otherwise), .rgb (rgb24), else a directory of PNGs.  The picture hash of every frame is
 taken on the device and, where the file carries hashes of the format decoded to, compared: the JSON line printed says how many frames
@@ -23,15 +28,25 @@ def main(argv=None):
                     help="e.g. yuv420p10le or yuv444p,bt709,full (default: the format of the file's picture hashes where the output takes it, "
                          "else what the output's extension means)")
     ap.add_argument("--batch", type=int, default=8, help="frames per render batch")
+    ap.add_argument("--frames", default=None, metavar="A:B", help="decode the frames A .. B - 1 only (default: all)")
     mode = ap.add_mutually_exclusive_group()
     mode.add_argument("--no-verify", action="store_true", help="do not take picture hashes")
     mode.add_argument("--strict", action="store_true", help="fail when a frame's picture hash differs from the file's, or nothing could be verified")
     args = ap.parse_args(argv)
 
-    from gsvc_amd.bitstream import BitstreamError, decode_video, read_bitstream
+    from gsvc_amd.bitstream import BitstreamError
     from gsvc_amd.frames_out import FrameFormat, open_sink
+    from gsvc_amd.sequence import decode_sequence, open_sequence
+    frames = None
+    if args.frames:
+        try:
+            a, b = args.frames.split(":")
+            frames = (int(a), int(b))
+        except ValueError:
+            raise SystemExit(f"--frames is A:B (got {args.frames!r})") from None
     try:
-        bs = read_bitstream(args.bitstream)
+        seq = open_sequence(args.bitstream)
+        hash_format = seq.hash_format
     except BitstreamError as e:
         print(f"gsvc_decode: {args.bitstream}: {e}", file=sys.stderr)
         return 2
@@ -41,20 +56,21 @@ def main(argv=None):
         if len(rest) > 2:
             raise SystemExit(f"a frame format is LAYOUT[,MATRIX[,RANGE]] (got {args.format!r})")
         fmt = FrameFormat.from_name(name, **dict(zip(("matrix", "range"), rest)))
-    elif bs.hash_format is not None:
+    elif hash_format is not None:
         ext = os.path.splitext(args.output)[1].lower()
         takes = {".y4m": ("yuv420p", "yuv444p"), ".yuv": ("yuv420p", "yuv444p"), ".rgb": ("rgb24",)}.get(ext, ("rgb24",))
-        if bs.hash_format.layout in takes:
-            fmt = bs.hash_format
-    g = bs.geometry
-    sink, fmt = open_sink(args.output, g.W, g.H, fps=g.fps, fmt=fmt)
+        if hash_format.layout in takes:
+            fmt = hash_format
+    if frames is not None and not 0 <= frames[0] < frames[1] <= seq.frames:
+        raise SystemExit(f"--frames {args.frames}: not a non-empty range inside the file's {seq.frames} frames")
+    sink, fmt = open_sink(args.output, seq.W, seq.H, fps=tuple(seq.fps), fmt=fmt)
     try:
-        res = decode_video(bs, sink, fmt=fmt, batch=args.batch, verify=not args.no_verify, strict=args.strict)
+        res = decode_sequence(seq, sink, fmt=fmt, batch=args.batch, verify=not args.no_verify, strict=args.strict, frames=frames)
     except BitstreamError as e:
         print(f"gsvc_decode: {args.bitstream}: {e}", file=sys.stderr)
         return 1
     res.pop("hashes", None)
-    print(json.dumps(dict(res, output=args.output, W=g.W, H=g.H, file_bytes=bs.file_bytes)))
+    print(json.dumps(dict(res, output=args.output, W=seq.W, H=seq.H, file_bytes=seq.file_bytes)))
     return 0
 
 

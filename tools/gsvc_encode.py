@@ -5,18 +5,22 @@ the video in another process, with nothing else:
     python tools/gsvc_encode.py clip.y4m -o clip.gsvc [--steps 2000 --lmbda 0.004 --anchors 100000 --estimate-flow]
                                 [--video-format yuv420p,bt601,full] [--video-size WxH] [--hash-format yuv420p]
     python tools/gsvc_decode.py clip.gsvc -o out.y4m --strict
+    python tools/gsvc_encode.py long.y4m -o long.gsvs --gop-frames 32 [--scene-cuts --cut-threshold 0.5 --min-gop 4]
 
 VideoFileCube (optionally with the flow estimated from the frames) -> the fit (the schedule and set-up of tools/fit_synthetic.py:
 gsvc_amd/fit_setup.py) -> conduct_stream_encoding with 8-bit MLPs -> the file.  The file is then read back and decoded into a null sink
 by the function, batch size and format the decoder will use (``decode_video``), which yields the picture hashes; the file is rewritten
 with them (section PHSH).  Prints one JSON line: bytes per section, the file's size, and bpp = 8 x FILE SIZE / (H W T).
+
+With --gop-frames the clip is cut into groups of pictures (GOPs) of at most that many frames (gsvc_amd/scene.py, ``plan_gops``; with
+--scene-cuts also where the luma histogram of the frames changes), every GOP is fitted and verified on its own (``fit_setup.encode_gop``;
+--steps and --anchors are per GOP) and the GOPs are written as ONE sequence file (magic GSVS; gsvc_amd/sequence.py, DESIGN.md section
+8h), also when the plan has one GOP.  The JSON line then lists the GOPs.  Without --gop-frames the file written is the GSVC file.
 """
 import argparse
 import json
 import os
 import sys
-import tempfile
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
@@ -45,57 +49,59 @@ def main(argv=None):
     ap.add_argument("--video-format", default=None, metavar="LAYOUT[,MATRIX[,RANGE]]", help="e.g. yuv420p,bt601,full or yuv420p10le")
     ap.add_argument("--hash-format", default="yuv420p", metavar="LAYOUT[,MATRIX[,RANGE]]",
                     help="the frame format whose picture hashes the file carries: what the decoder verifies when it decodes to it")
+    ap.add_argument("--gop-frames", type=int, default=None, metavar="N",
+                    help="cut the clip into groups of pictures of at most N frames and write a sequence file (GSVS)")
+    ap.add_argument("--scene-cuts", action="store_true", help="with --gop-frames: also start a GOP where the luma histogram changes")
+    ap.add_argument("--cut-threshold", type=float, default=None, metavar="X",
+                    help="histogram distance in [0, 1] above which a frame starts a scene (default 0.5: a starting value, not measured)")
+    ap.add_argument("--min-gop", type=int, default=None, metavar="M", help="the shortest GOP (default 4); --gop-frames must be at least 2 M")
     args = ap.parse_args(argv)
+    if args.gop_frames is None and (args.scene_cuts or args.cut_threshold is not None or args.min_gop is not None):
+        ap.error("--scene-cuts, --cut-threshold and --min-gop need --gop-frames")
 
     import torch
 
-    from gsvc_amd.arguments import cfg_20240919
-    from gsvc_amd.bitstream import CubeGeometry, NullSink, decode_video, read_bitstream, unpack_sections, with_hashes, write_bitstream
-    from gsvc_amd.fit_setup import configure_fit, new_fit
-    from gsvc_amd.frames_in import VideoFileCube
-    from gsvc_amd.stream_codec import conduct_stream_encoding
+    from gsvc_amd.fit_setup import encode_gop
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    mp_, opt, pipe = cfg_20240919()
     vw, vh = (int(v) for v in args.video_size.lower().split("x")) if args.video_size else (None, None)
-    cube = VideoFileCube(args.video, optical_flow_dir=args.flow_dir, W=vw, H=vh, fmt=_frame_format(args.video_format) if args.video_format else None,
-                         device=dev)
-    H, W, T = cube.height, cube.width, cube.len_z_frames
-    geometry_source = cube
-    if args.estimate_flow:
-        from gsvc_amd.flow import EstimatedFlowCube
-        cube = EstimatedFlowCube(cube, device=dev)
-    elif args.flow_dir is None:
-        opt.optical_lambda = 0.0
-    configure_fit(mp_, opt, cube, args.steps, args.lmbda, args.slab_frames, args.densify_grad_threshold)
-    pc, trainer = new_fit(cube, mp_, opt, pipe, args.anchors, dev)
-    bg = trainer.background
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    for it in range(1, args.steps + 1):
-        trainer.step(it)
-    torch.cuda.synchronize()
-    fit_seconds = time.perf_counter() - t0
-    trainer.sync_replicas()
-    trainer.close()
-    with torch.no_grad(), tempfile.TemporaryDirectory() as tmp:
-        mlp_file = os.path.join(tmp, "mlp.bin")
-        pack = conduct_stream_encoding(pc, mlp_file=mlp_file)          # (quantises the MLPs of pc in place: the shipped form)
-        with open(mlp_file, "rb") as f:
-            mlp_bytes = f.read()
-    geometry = CubeGeometry.of(geometry_source, mp_, pipe, bg.tolist())
-    write_bitstream(args.output, pc, pack, geometry, mlp_bytes)
-    log = {"output": args.output, "W": W, "H": H, "frames": T, "steps": args.steps, "anchors_coded": int(pack.n), "fit_seconds": fit_seconds}
-    # the decoder's own path on the file just written: the hashes are those of the pictures IT produces
-    del trainer, cube, geometry_source, pc, pack
-    fmt = _frame_format(args.hash_format)
-    res = decode_video(read_bitstream(args.output), NullSink(), fmt=fmt, verify=True, device=dev)
-    with open(args.output, "rb") as f:
-        blob = with_hashes(f.read(), fmt, res["hashes"])
-    with open(args.output, "wb") as f:
-        f.write(blob)
-    log["hash_format"], log["verify_decode_fps"] = fmt.name, res["fps"]
-    log["sections"] = {t.decode("ascii"): len(p) for t, p in unpack_sections(blob)}
+    video_fmt = _frame_format(args.video_format) if args.video_format else None
+    fit = dict(steps=args.steps, lmbda=args.lmbda, anchors=args.anchors, slab_frames=args.slab_frames,
+               densify_grad_threshold=args.densify_grad_threshold, estimate_flow=args.estimate_flow, flow_dir=args.flow_dir,
+               video_size=(vw, vh), video_format=video_fmt, hash_format=_frame_format(args.hash_format))
+    if args.gop_frames is None:
+        blob, log = encode_gop(args.video, dev, **fit)
+        with open(args.output, "wb") as f:
+            f.write(blob)
+        log = dict({"output": args.output}, **log)
+        log["total_bytes"] = int(os.path.getsize(args.output))
+        log["bpp"] = 8.0 * log["total_bytes"] / (log["H"] * log["W"] * log["frames"])
+        print(json.dumps(log))
+        return log
+
+    from gsvc_amd import scene
+    from gsvc_amd.frames_in import open_video
+    from gsvc_amd.sequence import write_sequence
+    header, frames = open_video(args.video, vw, vh, video_fmt)
+    H, W, T = int(header["H"]), int(header["W"]), int(frames.shape[0])
+    min_gop = scene.DEFAULT_MIN_GOP if args.min_gop is None else args.min_gop
+    threshold = scene.DEFAULT_CUT_THRESHOLD if args.cut_threshold is None else args.cut_threshold
+    cuts = scene.detect_cuts((header, frames), dev, threshold)[0] if args.scene_cuts else []
+    del frames
+    plan = scene.plan_gops(T, cuts, args.gop_frames, min_gop)
+    flags = scene.gop_cut_flags(plan, cuts)
+    blobs, gops, fit_seconds = [], [], 0.0
+    for (first, count), cut in zip(plan, flags):
+        blob, one = encode_gop(args.video, dev, frame_range=(first, first + count), **fit)          # (everything of the GOP's fit is released inside)
+        blobs.append(blob)
+        fit_seconds += one["fit_seconds"]
+        gops.append({"first": first, "frames": count, "bytes": len(blob), "bpp": 8.0 * len(blob) / (H * W * count),
+                     "fit_seconds": one["fit_seconds"], "cut": int(cut), "anchors_coded": one["anchors_coded"], "sections": one["sections"]})
+    fps = header.get("fps") or (30, 1)
+    write_sequence(args.output, blobs, W, H, fps, flags)
+    log = {"output": args.output, "W": W, "H": H, "frames": T, "steps": args.steps, "fit_seconds": fit_seconds,
+           "hash_format": _frame_format(args.hash_format).name, "gop_frames": args.gop_frames, "min_gop": min_gop,
+           "scene_cuts": cuts if args.scene_cuts else None, "cut_threshold": threshold if args.scene_cuts else None, "gops": gops}
     log["total_bytes"] = int(os.path.getsize(args.output))
     log["bpp"] = 8.0 * log["total_bytes"] / (H * W * T)
     print(json.dumps(log))
