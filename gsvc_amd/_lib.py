@@ -266,6 +266,11 @@ _SIGNATURES = {
                                      C.c_int32, _vp, _i64, _vp]),
     "gsvc_frames_from_u16": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.POINTER(C.c_void_p), _vp]),
+    "gsvc_yuv_planes_floats": (_i64, [C.c_int32, C.c_int32, C.c_int32]),
+    "gsvc_frames_planes": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p),
+                                     _vp]),
+    "gsvc_yuv_planes_forward": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
+    "gsvc_yuv_planes_backward": (C.c_int, [_vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp]),
     "gsvc_frames_sse": (C.c_int, [_vp, _i64, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "gsvc_msssim_workspace_bytes": (_i64, [C.c_int32, C.c_int32, C.c_int32]),
     "gsvc_msssim": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _vp, _vp, _vp]),

@@ -184,6 +184,7 @@ class VideoFileCube:
         if self.device.type != "cuda":
             raise _lib.GsvcError("VideoFileCube converts its frames with the HIP kernels of csrc/frames_in.hip; it needs a CUDA device")
         self._views, self._fetched = {}, {}
+        self._planes = None          # resident="float": the plane buffers of every frame, from the first yuv_planes() on
         self._upload(frames)
         from .io import load_flow
         self.prefetched_of = [load_flow(p).to(self.device) for p in self.optical_flow_paths]
@@ -240,6 +241,51 @@ class VideoFileCube:
         live = [(r, ev) for r, ev in self._fetched.get(image_id, ()) if r() is not None]
         self._fetched[image_id] = live + [(weakref.ref(img), done)]
         return img
+
+    def yuv_planes(self, image_id):
+        """The float32 plane buffer ``[Y: H W | Cb | Cr]`` of frame ``image_id`` straight from the file's sample codes, in the file's
+        own layout (``yuv_loss.frame_planes``: no matrix, no chroma upsampling; ``yuv_loss.split_planes`` views it as Y and C) — the
+        ground truth of a fit with ``loss_domain = "yuv420"`` / ``"yuv444"``.  A Y'CbCr file only.
+          ``resident="u8"``     one launch per call on the current stream, reading the resident bytes (complete before the
+                                constructor returned: nothing to order across streams), into a tensor of its own.
+          ``resident="float"``  all frames are converted on first use, in chunks of 16 on the current stream, and kept: 4 bytes per
+                                sample, 6 H W bytes per 4:2:0 frame.  Readers on other streams order themselves behind that first call."""
+        from .yuv_loss import frame_planes
+        if self.fmt.layout not in ("yuv420p", "yuv444p"):
+            raise ValueError(f"{self.path}: {self.fmt.layout} frames hold no Y'CbCr planes")
+        image_id = int(image_id)
+        if not 0 <= image_id < self.len:
+            raise IndexError(f"frame {image_id} of {self.len}")
+        if self._u8 is not None:
+            return frame_planes(self._u8[image_id:image_id + 1], self.height, self.width, self.fmt)[0]
+        if self._planes is None:
+            self._planes = self._convert_planes()
+        return self._planes[image_id]
+
+    def _convert_planes(self):
+        """Every frame's plane buffer, for ``resident="float"``: the file's bytes are uploaded again in chunks of up to 16 frames
+        through one pinned staging buffer (the float pictures cannot give the un-interpolated chroma back)."""
+        import torch
+
+        from .yuv_loss import frame_planes
+        _, frames = open_video(self.path, self.width, self.height, self.fmt)
+        if self.frame_range is not None:
+            frames = frames[self.frame_range[0]:self.frame_range[1]]
+        T, nbytes = self.len, int(self.header["frame_bytes"])
+        chunk = min(MAX_BATCH, T)
+        staging = torch.empty((chunk, nbytes), dtype=torch.uint8, pin_memory=True)
+        host = staging.numpy()
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device)
+            on_dev = torch.empty((chunk, nbytes), dtype=torch.uint8, device=self.device)
+            planes = torch.empty((T, nbytes // (2 if self.fmt.depth > 8 else 1)), dtype=torch.float32, device=self.device)
+            for i in range(0, T, chunk):
+                m = min(chunk, T - i)
+                np.copyto(host[:m], frames[i:i + m])
+                on_dev[:m].copy_(staging[:m], non_blocking=True)
+                frame_planes(on_dev[:m], self.height, self.width, self.fmt, out=planes[i:i + m])
+                stream.synchronize()          # the staging buffer is free again
+        return planes
 
     def ready(self, image_id):
         """Order the current stream behind the conversions of frame ``image_id`` whose pictures are still in use, and tell the

@@ -18,7 +18,7 @@ import contextlib
 import torch
 
 from . import dist as gdist
-from . import schedule, switches
+from . import schedule, switches, yuv_loss
 from .generate import GenerateMode, region
 from .loss_utils import calc_optical_loss, render_regs, ssim_l1, ssim_l1_pair
 from .optim import FusedAdam
@@ -133,6 +133,19 @@ class Trainer:
             warnings.warn("Trainer(shard_optimizer=...) is ignored: the optimizer is replicated (gsvc_amd/dist.py)", DeprecationWarning,
                           stacklevel=2)
         self.batched = batched
+        # where the distortion is taken (gsvc_amd/yuv_loss.py): float RGB, or the Y'CbCr planes the codec delivers and is measured on
+        self.loss_domain = getattr(opt, "loss_domain", "rgb")
+        self._loss_fmt = None
+        self._native_planes = False
+        self.loss_matrix = None          # of the planes; None in the rgb domain
+        layout = yuv_loss.domain_layout(self.loss_domain)          # (an unknown name is refused here)
+        if layout is not None:
+            from .frames_out import FrameFormat
+            yuv_loss.check_domain(self.loss_domain, dataset.height, dataset.width)
+            yuv_loss.check_dataset(dataset, layout)
+            self._loss_fmt = FrameFormat(layout, yuv_loss.loss_matrix(dataset))
+            self.loss_matrix = self._loss_fmt.matrix
+            self._native_planes = yuv_loss.native_planes(dataset, layout)      # the targets come from the file's codes: no picture is read
         # prefetch: the next step's frame pair is drawn, its visibility test run and every data-dependent index list of its
         # generation pass queued at the END of a step (gsvc_amd.generate.StepPlan): the next step then starts with one wait
         # for nine counts instead of six device round trips with an idle GPU
@@ -349,11 +362,23 @@ class Trainer:
         return switches.DP_SPARSE == "1" or gdist.sparse_rows_pay(gdist.world_size(), int(self.pc._anchor.shape[0]),
                                                                                   plan.distinct_cap)
 
+    def _frame(self, i):
+        """Frame i of the dataset; without its picture where the step's targets are the file's own planes (a fetch of a
+        ``VideoFileCube(resident="u8")`` would launch a conversion nobody reads)."""
+        return self.dataset.get_dummy_frame(i) if self._native_planes else self.dataset[i]
+
+    def _targets(self, frame, i, dev):
+        """The ground truth of frame i in the loss domain: the picture [3, H, W], or its planes (tY, tC)."""
+        if self._loss_fmt is None:
+            return frame.image.to(dev).permute(0, 2, 1).contiguous()
+        picture = None if self._native_planes else frame.image.to(dev)
+        return yuv_loss.target_planes(self.dataset, i, self._loss_fmt.layout, self._loss_fmt.matrix, picture=picture)
+
     def _views(self, frame_idx):
         """The step's four views: (frame, frame seen from the opposite side) of the two adjacent frames."""
         import copy
         views = []
-        for fr in (self.dataset[frame_idx], self.dataset[frame_idx + 1]):
+        for fr in (self._frame(frame_idx), self._frame(frame_idx + 1)):
             back = copy.copy(fr)
             back.view_matrix, back.view_matrix_s = fr.view_matrix_s, fr.view_matrix
             views += [fr, back]
@@ -386,7 +411,7 @@ class Trainer:
         if frame_idx is None:
             frame_idx = self.rng.randint(self.lo, max(self.lo, self.hi - 1))
         self._last_idx = frame_idx
-        frame1, frame2 = self.dataset[frame_idx], self.dataset[frame_idx + 1]
+        frame1, frame2 = self._frame(frame_idx), self._frame(frame_idx + 1)
         mode = self.controller.render_mode
         retain_grad = opt.update_until > iteration >= 0
 
@@ -416,17 +441,28 @@ class Trainer:
         if ready is not None:          # pictures uploaded on a copy stream (HostResidentCube): their first readers come now
             ready(frame_idx)
             ready(frame_idx + 1)
-        gt1 = frame1.image.to(dev).permute(0, 2, 1)
-        gt2 = frame2.image.to(dev).permute(0, 2, 1)
-        if image1 is None:
-            ssim1, l1_1, image1 = ssim_l1_pair(r1f.rendered_image, r1b.rendered_image, gt1.contiguous())
-            ssim2, l1_2, image2 = ssim_l1_pair(r2f.rendered_image, r2b.rendered_image, gt2.contiguous())
+        gt1, gt2 = self._targets(frame1, frame_idx, dev), self._targets(frame2, frame_idx + 1, dev)
+        if self._loss_fmt is not None:
+            # the render's planes against the file's (or the picture's) planes: luma and the chroma pair are two calls of the SSIM / L1
+            # kernels per frame, chained into the transform (the two-view frame is formed inside the transform's kernel)
+            y1 = yuv_loss.yuv_ssim_l1(r1f.rendered_image if image1 is None else image1, r1b.rendered_image if image1 is None else None,
+                                      gt1, self._loss_fmt)
+            y2 = yuv_loss.yuv_ssim_l1(r2f.rendered_image if image2 is None else image2, r2b.rendered_image if image2 is None else None,
+                                      gt2, self._loss_fmt)
+            if image1 is None:
+                image1, image2 = y1[4], y2[4]
+            terms = [y1[1], y2[1], y1[3], y2[3], y1[0], y2[0], y1[2], y2[2]]
+        elif image1 is None:
+            ssim1, l1_1, image1 = ssim_l1_pair(r1f.rendered_image, r1b.rendered_image, gt1)
+            ssim2, l1_2, image2 = ssim_l1_pair(r2f.rendered_image, r2b.rendered_image, gt2)
+            terms = [l1_1, l1_2, ssim1, ssim2]
         else:
-            ssim1, l1_1 = ssim_l1(image1, gt1.contiguous())
-            ssim2, l1_2 = ssim_l1(image2, gt2.contiguous())
+            ssim1, l1_1 = ssim_l1(image1, gt1)
+            ssim2, l1_2 = ssim_l1(image2, gt2)
+            terms = [l1_1, l1_2, ssim1, ssim2]
         # the loss is a weighted sum of scalar terms: they are collected and combined with one stack + dot (instead of
         # one tiny kernel per +, *, and their backward nodes)
-        terms, weights, const = [l1_1, l1_2, ssim1, ssim2], [1.0 - opt.lambda_dssim] * 2 + [-opt.lambda_dssim] * 2, 2.0 * opt.lambda_dssim
+        weights, const = yuv_loss.distortion_weights(self.loss_domain, opt.lambda_dssim)
         batch = getattr(r1f.generated_gaussians, "batch", None) if self.batched else None
         # the terms below read the generation pass's tensors and parameters, not the images: a dozen small launches each way, issued
         # on the small-work stream behind the generation pass's event so that they run under the compositing kernels (their backward

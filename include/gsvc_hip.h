@@ -977,6 +977,52 @@ int gsvc_frames_from_u16(const uint8_t *in, int64_t in_stride, int32_t n, int32_
                          int32_t range, int32_t chroma, int32_t depth, float *const *images_host, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * [INTERNAL] The fitting step's distortion in the delivered domain: float Y'CbCr planes (csrc/yuv_loss.hip).
+ *
+ * A plane buffer of a picture of H x W in layout L (GSVC_FRAMES_YUV444P or _YUV420P; RGB24 has none) is one contiguous float32 array
+ *     [ Y: H W | Cb: ch cw | Cr: ch cw ],   (ch, cw) = (H / 2, W / 2) for 4:2:0 (H and W even), (H, W) for 4:4:4,
+ * gsvc_yuv_planes_floats(H, W, L) floats in all (< 0 for an invalid size or layout); as tensors, Y [1, H, W] and C [2, ch, cw].  Every
+ * plane is on a nominal [0, 1]: Y is the Y of gsvc_frames_to_u8's formulas and a chroma plane is that formula's C + 0.5, so that the
+ * constants of SSIM meet the value range they were chosen for.  Nothing is clamped (a clamp would cut the gradient):
+ * gsvc_frames_to_u8 / _u16 differ from gsvc_yuv_planes_forward only by their clamp of the inputs, their range map and their rounding.
+ *
+ * gsvc_frames_planes: the ground truth straight from a file's sample codes.  n (1 .. 16) frames of depth 8 (bytes) or 9 .. 16
+ * (little-endian 16-bit words), frame k at in + k * in_stride, into n plane buffers (planes_host: host array of n device pointers,
+ * each 4-byte aligned):
+ *     Y = (y - y_off) / y_scale,   C = (c - c_off) / c_scale + 0.5
+ * with the constants of the range at that depth (LIMITED: 16, 219, 128, 224, each times 2^(d - 8); FULL: 0, 2^d - 1, 2^(d - 1),
+ * 2^d - 1): one float32 subtraction (exact), one IEEE float32 division and, for chroma, one float32 addition.  No matrix enters and
+ * there is no chroma upsampling: a chroma code becomes one chroma float.  Refused before any launch: RGB24, n outside 1 .. 16, a depth
+ * outside 8 .. 16, an odd H or W for 4:2:0, in_stride below the frame's bytes (gsvc_frames_bytes), and for deep frames an odd base or
+ * in_stride.  Every float of the n buffers is written, nothing else.
+ *
+ * gsvc_yuv_planes_forward: the render as planes.  img_f, img_b: float32 [3, H, W] RGB; img_b may be NULL.
+ *     a = 0.5 (f + flip_W(b))            the two-view frame gsvc_ssim_l1_pair_forward forms on load; a = f when img_b is NULL
+ *     Y  = fma(Kr, R, fma(Kg, G, Kb B))
+ *     Cb = fma(B - Y, 1 / (2 (1 - Kb)), 0.5),   Cr = fma(R - Y, 1 / (2 (1 - Kr)), 0.5)
+ * of a's channels; Kr, Kg = 1 - Kr - Kb, Kb and the two reciprocals are formed in double and rounded once to float.  4:2:0 chroma is
+ * 0.25 ((c00 + c01) + (c10 + c11)) of the 2x2 block's Cb / Cr (c_rs = row r, column s), added in exactly that order: the same bits
+ * for every launch shape and alignment.  avg_out (float32 [3, H, W], may be NULL) receives a.
+ *
+ * gsvc_yuv_planes_backward: the exact adjoint.  d_planes: the gradient (gY, gCb, gCr) in the plane-buffer layout.  Per pixel, with
+ * q = 0.25 for 4:2:0 (gCb / gCr of the pixel's block) and 1 for 4:4:4, s_b = 1 / (2 (1 - Kb)), s_r = 1 / (2 (1 - Kr)):
+ *     gB' = q gCb s_b,  gR' = q gCr s_r,  gY' = gY - gB' - gR'
+ *     dR = Kr gY' + gR',  dG = Kg gY',  dB = Kb gY' + gB'
+ * dL_dimg_f = 0.5 d and dL_dimg_b = 0.5 d at the flipped column; with dL_dimg_b = NULL, dL_dimg_f = d.  Every element of the outputs
+ * given is written, nothing else.
+ *
+ * All pointers 4-byte aligned; the kernels take a vector path when W is a multiple of 4, H is even and every base is 16-byte
+ * aligned, and give the same bits on either path.  Nothing synchronises.
+ * ---------------------------------------------------------------------------------------------------- */
+int64_t gsvc_yuv_planes_floats(int32_t H, int32_t W, int32_t layout);
+int gsvc_frames_planes(const uint8_t *in, int64_t in_stride, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t range,
+                       int32_t depth, float *const *planes_host, void *stream);
+int gsvc_yuv_planes_forward(const float *img_f, const float *img_b, int32_t H, int32_t W, int32_t layout, int32_t matrix,
+                            float *planes_out, float *avg_out, void *stream);
+int gsvc_yuv_planes_backward(const float *d_planes, int32_t H, int32_t W, int32_t layout, int32_t matrix, float *dL_dimg_f,
+                             float *dL_dimg_b, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * [INTERNAL] Video metrics on the codes (csrc/metrics.hip).
  *
  * gsvc_frames_sse: out[k, p] (uint64 [n, 3], 8-byte aligned) = the sum over the samples of plane p of frame k of (a - b)^2, a and b the

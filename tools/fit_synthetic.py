@@ -88,6 +88,9 @@ def main(argv=None):
     ap.add_argument("--optical-lambda", type=float, default=None, help="weight of the flow-guided loss (default: the configuration's)")
     ap.add_argument("--video-resident", choices=("float", "u8"), default="float",
                     help="keep the video on the device as float32 pictures, or as the file's bytes (converted one frame per fetch)")
+    ap.add_argument("--loss-domain", choices=("rgb", "yuv420", "yuv444"), default="rgb",
+                    help="where the fit takes its distortion: float RGB, or Y'CbCr planes (gsvc_amd/yuv_loss.py): those of a Y'CbCr --video "
+                         "file's sample codes, else the transform of the RGB pictures")
     args = ap.parse_args(argv)
 
     from gsvc_amd.arguments import cfg_20240919
@@ -136,9 +139,11 @@ def main(argv=None):
     flow_log["optical_lambda"] = float(opt.optical_lambda)
     from gsvc_amd.fit_setup import configure_fit, new_fit
     configure_fit(mp_, opt, cube, N, args.lmbda, args.slab_frames, args.densify_grad_threshold)
+    opt.loss_domain = args.loss_domain
     pc, trainer = new_fit(cube, mp_, opt, pipe, args.anchors, dev)
     bg = trainer.background
     log = {"config": {"H": H, "W": W, "frames": T, "steps": N, "anchors_init": args.anchors, "lmbda": args.lmbda,
+                      "loss_domain": trainer.loss_domain, "loss_matrix": trainer.loss_matrix,
                       "slab_frames": args.slab_frames, "schedule": [opt.full_precision_training_total, opt.quantized_training_total,
                                                                     opt.entropy_constrained_train_total, opt.ste_entropy_constrained_train_total],
                       "densify": [opt.start_stat, opt.update_from, opt.update_interval, opt.update_until, opt.pause_densification]},
