@@ -37,9 +37,12 @@ __device__ __forceinline__ bool bbox_hits_tile(uint32_t bx, uint32_t by, int tx0
 }
 
 // Pixel state of the back-to-front replay.  The colours only ever enter through their dot product with dL/dpixel, so the
-// composited-behind colour is kept as ONE number: bd = (colour seen behind the current entry, at unit transmittance) . d
+// composited-behind colour is kept as ONE number: bd = (colour seen behind the current entry, at unit transmittance) . d.
+// Invariant: behind entry j that colour is (sum_{k>j} c_k w_k + T_final bg) / T_{j+1}; behind the last contributor it is the
+// background, so bd starts at bg . d and dL/dalpha_j = (c_j . d - bd) T_j already holds the background's share
+// -T_final (bg . d) / (1 - alpha_j): no second term of the size of T (bg . d) to cancel against.
 struct PixState {
-    float T, tb, d0, d1, d2, bd;  // tb = final_T * (bg . dL/dpixel)
+    float T, d0, d1, d2, bd;
     int last;                     // n_contrib; 0 for a pixel outside the image (no list position is <= 0)
 };
 struct PixStateAux : PixState {
@@ -202,8 +205,7 @@ __device__ __forceinline__ bool bwd_pixel(PS &p, float dx, float dy, const float
     const float w = alpha * p.T;
     s.r = fmaf(w, p.d0, s.r); s.g = fmaf(w, p.d1, s.g); s.b = fmaf(w, p.d2, s.b);
     if constexpr (AUX) s.z = fmaf(w, p.gD, s.z);
-    // ZERO_BG (black background, the reference's default): the background's share T_final (bg . d) / (1 - alpha) is zero
-    const float dLda = ZERO_BG ? (cd - p.bd) * p.T : fmaf(cd - p.bd, p.T, -(p.tb * inv));
+    const float dLda = (cd - p.bd) * p.T;       // the background's share rides in bd (PixState)
     p.bd = fmaf(alpha, cd, oma * p.bd);
     // moments of h = G * dL/dalpha; the conic / opacity factors are applied once per Gaussian in B2
     const float h = G * dLda;
@@ -243,8 +245,7 @@ __device__ __forceinline__ bool bwd_pixel_poly(PS &p, float x, float y, float x2
     const float w = alpha * p.T;
     s.r = fmaf(w, p.d0, s.r); s.g = fmaf(w, p.d1, s.g); s.b = fmaf(w, p.d2, s.b);
     if constexpr (AUX) s.z = fmaf(w, p.gD, s.z);
-    // ZERO_BG (black background, the reference's default): the background's share T_final (bg . d) / (1 - alpha) is zero
-    const float dLda = ZERO_BG ? (cd - p.bd) * p.T : fmaf(cd - p.bd, p.T, -(p.tb * inv));
+    const float dLda = (cd - p.bd) * p.T;       // the background's share rides in bd (PixState)
     p.bd = fmaf(alpha, cd, oma * p.bd);
     const float h = Gh * dLda;
     s.h += h;
@@ -378,9 +379,9 @@ __global__ void __launch_bounds__(64, AUX ? GSVC_BWD_AUX_WAVES : GSVC_BWD_WAVES)
 #pragma unroll
     for (int q = 0; q < 4; q++) {
         PS &p = ps[q];
-        p.tb = ZERO_BG ? 0.f : Tf[q] * (st.bg0 * p.d0 + st.bg1 * p.d1 + st.bg2 * p.d2);
         p.T = Tf[q];
-        p.bd = 0.f;
+        // ZERO_BG (black background, the reference's default): nothing behind the last entry
+        p.bd = ZERO_BG ? 0.f : st.bg0 * p.d0 + st.bg1 * p.d1 + st.bg2 * p.d2;
         wl[q] = __builtin_amdgcn_readfirstlane(wave_max(p.last));
     }
     const int tile_last = max(max(wl[0], wl[1]), max(wl[2], wl[3]));
