@@ -276,6 +276,10 @@ _SIGNATURES = {
     "gsvc_msssim": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _vp, _vp, _vp]),
     "gsvc_picture_hash": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "gsvc_frames_histogram": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    # content-adaptive initial anchors (csrc/detail.hip): replace the uniform draw of the reference's init_point_cloud
+    "gsvc_frames_detail": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    "gsvc_detail_sample": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, _vp, _vp,
+                                     _vp]),
     "gsvc_flow_workspace_bytes": (_i64, [C.c_int32] * 5),
     "gsvc_flow_estimate": (C.c_int, [_vp, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _vp,
                                      _vp, _vp]),

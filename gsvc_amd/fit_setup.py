@@ -32,9 +32,17 @@ def configure_fit(mp_, opt, cube, steps: int, lmbda: float, slab_frames: float, 
             setattr(opt, name, N)
 
 
-def new_fit(cube, mp_, opt, pipe, anchors: int, device):
-    """Seed the generators, build the model of configuration ``mp_`` with ``anchors`` uniformly drawn initial points inside the cube
-    (reference frame_cube/utils.py:6-15, init_point_cloud, bleed 0.1) and its Trainer -> ``(pc, trainer)``."""
+def new_fit(cube, mp_, opt, pipe, anchors: int, device, init: str = "uniform", init_cell: int = 8, init_mix: float = 0.25):
+    """Seed the generators, build the model of configuration ``mp_`` with ``anchors`` initial points and its Trainer -> ``(pc, trainer)``.
+      ``init="uniform"``  the points are drawn uniformly inside the cube (reference frame_cube/utils.py:6-15, init_point_cloud, bleed 0.1).
+      ``init="detail"``   they are drawn where the clip's luma has detail (gsvc_amd/detail.py, ``detail_points``: cells of ``init_cell``
+                          pixels, a share ``init_mix`` of the points uniform; both defaults are starting values, not measured ones).
+    Either way ``create_from_points`` merges the points of a voxel and sets every anchor's scale from its 3-NN distance."""
+    from . import detail
+    if init not in detail.INITS:
+        raise ValueError(f"new_fit: init must be one of {', '.join(detail.INITS)} (got {init!r})")
+    if init == "detail":
+        init_cell, init_mix = detail.check_cell_mix(init_cell, init_mix, "new_fit")
     from . import dist as gdist
     from .model import GaussianModel
     from .train import Trainer
@@ -43,8 +51,12 @@ def new_fit(cube, mp_, opt, pipe, anchors: int, device):
     pc = GaussianModel(mp_, mp_.anchor_feature_dim, mp_.n_offsets, mp_.voxel_size, mp_.update_depth, mp_.update_init_factor,
                        mp_.update_hierarchy_factor, mp_.use_feat_bank, n_features_per_level=mp_.grid_feature_dim,
                        log2_hashmap_size=mp_.log2, log2_hashmap_size_2D=mp_.log2_2D, device=device)
-    lim = np.array([cube.x_min, cube.y_min, cube.z_min]) * 1.1
-    pc.create_from_points(np.random.default_rng(0).uniform(lim, -lim, (anchors, 3)), spatial_lr_scale=1.0)
+    if init == "detail":
+        points, _ = detail.detail_points(cube, anchors, init_cell, init_mix, seed=0)
+        pc.create_from_points(points, spatial_lr_scale=1.0)
+    else:
+        lim = np.array([cube.x_min, cube.y_min, cube.z_min]) * 1.1
+        pc.create_from_points(np.random.default_rng(0).uniform(lim, -lim, (anchors, 3)), spatial_lr_scale=1.0)
     pc.update_anchor_bound(cube.x_min, cube.y_min, cube.z_min)
     pc.training_setup(opt)
     gdist.broadcast_parameters(pc)
@@ -54,14 +66,17 @@ def new_fit(cube, mp_, opt, pipe, anchors: int, device):
 
 def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float = 0.004, anchors: int = 100_000, slab_frames: float = 16.0,
                densify_grad_threshold=None, estimate_flow: bool = False, flow_dir=None, video_size=(None, None), video_format=None,
-               hash_format=None, loss_domain: str = "rgb"):
+               hash_format=None, loss_domain: str = "rgb", init: str = "uniform", init_cell: int = 8, init_mix: float = 0.25):
     """One group of pictures of a video file -> ``(the bytes of a complete GSVC file, log)``: what tools/gsvc_encode.py does with a whole
     clip, for the frames ``frame_range = (first, stop)`` of it (None: all).  VideoFileCube (optionally with the flow estimated from the
     frames) -> the fit -> ``conduct_stream_encoding`` with 8-bit MLPs -> the file image; that image is then decoded into a null sink by
     the function, batch size and format the decoder will use (``decode_video``), which yields the picture hashes it is given as its PHSH
     section.  The trainer, the cube and the model are released before this returns.  ``loss_domain``: where the fit takes its
-    distortion (``OptimizationParams.loss_domain``; the bitstream and the decoder are the same for every domain).  ``log``: {"W", "H",
-    "frames", "steps", "loss_domain", "loss_matrix", "anchors_coded", "fit_seconds", "hash_format", "verify_decode_fps", "sections"}."""
+    distortion (``OptimizationParams.loss_domain``; the bitstream and the decoder are the same for every domain).  ``init``,
+    ``init_cell``, ``init_mix``: where the fit's first anchors come from (``new_fit``; anchors are coded wherever they are).  ``log``:
+    {"W", "H", "frames", "steps", "init", ("init_cell", "init_mix": with init="detail" only), "anchors_initial": the anchors after the
+    voxel merge of ``create_from_points``, "loss_domain", "loss_matrix", "anchors_coded", "fit_seconds", "hash_format",
+    "verify_decode_fps", "sections"}."""
     import gc
     import os
     import tempfile
@@ -84,7 +99,11 @@ def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float 
         opt.optical_lambda = 0.0
     configure_fit(mp_, opt, cube, steps, lmbda, slab_frames, densify_grad_threshold)
     opt.loss_domain = loss_domain
-    pc, trainer = new_fit(cube, mp_, opt, pipe, anchors, device)
+    pc, trainer = new_fit(cube, mp_, opt, pipe, anchors, device, init=init, init_cell=init_cell, init_mix=init_mix)
+    log["init"] = init
+    if init == "detail":
+        log["init_cell"], log["init_mix"] = int(init_cell), float(init_mix)
+    log["anchors_initial"] = int(pc._anchor.shape[0])
     log["loss_domain"], log["loss_matrix"] = trainer.loss_domain, trainer.loss_matrix
     bg = trainer.background
     torch.cuda.synchronize()

@@ -129,7 +129,7 @@ class EstimatedFlowCube:
     """A frame cube (``VideoFileCube``, ``io.FrameCubeDataset``, ``SyntheticFrameCube``, ...) whose optical flow is estimated from its
     own pictures: the T - 1 fields are computed once, here, and stay on the device as float32 (8 bytes per pixel and pair: 16.6 MB per
     1080p pair, 1 GB for 64 frames).  ``get_optical_flow(i)`` hands out field i; everything else (``cube[i]``, ``get_z_frame``,
-    ``get_dummy_frame``, ``ready``, ``scale``, ``x_min``, ...) is the wrapped cube's.  The cube's pictures are ``[3, W, H]`` (transposed,
+    ``get_dummy_frame``, ``ready``, ``luma_detail``, ``fmt``, ``scale``, ``x_min``, ...) is the wrapped cube's.  The cube's pictures are ``[3, W, H]`` (transposed,
     as the reference keeps them); the estimator is given ``[H, W]``.  ``Trainer``, ``HostResidentCube`` and ``report.evaluate`` take it
     as they take the cube."""
 

@@ -287,6 +287,23 @@ class VideoFileCube:
                 stream.synchronize()          # the staging buffer is free again
         return planes
 
+    def luma_detail(self, cell: int = 8):
+        """The detail map of the cube's frames from the file's luma codes (gsvc_amd/detail.py) -> uint32 ``[T, Hc, Wc]``: what a fit
+        with ``init="detail"`` draws its anchors from.  A Y'CbCr file only.  The same bits in either residency:
+          ``resident="u8"``     one launch on the resident bytes.
+          ``resident="float"``  the file's bytes are uploaded again in chunks of 16 frames plus one overlapping frame, as
+                                ``_convert_planes`` does (the float pictures cannot give the codes back).
+        A ``frame_range`` cube reads its own frames only: its last frame looks back, never past the range."""
+        from . import detail
+        if self.fmt.layout not in ("yuv420p", "yuv444p"):
+            raise ValueError(f"{self.path}: {self.fmt.layout} frames hold no luma plane")
+        if self._u8 is not None:
+            return detail.luma_detail(self._u8, self.height, self.width, self.fmt, cell)
+        _, frames = open_video(self.path, self.width, self.height, self.fmt)
+        if self.frame_range is not None:
+            frames = frames[self.frame_range[0]:self.frame_range[1]]
+        return detail.file_detail(frames, self.height, self.width, self.fmt, cell, self.device)
+
     def ready(self, image_id):
         """Order the current stream behind the conversions of frame ``image_id`` whose pictures are still in use, and tell the
         allocator that this stream reads them.  Nothing to do for ``resident="float"``: those pictures were complete before the

@@ -1097,6 +1097,41 @@ int gsvc_frames_histogram(const uint8_t *frames, int64_t stride, int32_t n, int3
                           uint32_t *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * [INTERNAL] Content-adaptive initial anchors (csrc/detail.hip, gsvc_amd/detail.py): a detail map of the luma codes
+ * and points drawn from it.  Replaces the uniform draw of the reference's init_point_cloud (frame_cube/utils.py:6-15) for init="detail".
+ *
+ * gsvc_frames_detail: out[f, cy, cx] (uint32 [n_out, Hc, Wc], Hc = ceil(H / cell), Wc = ceil(W / cell), 4-byte aligned) = the sum of
+ *     e = gx + gy + 2 gt
+ * over the pixels (x, y) of cell (cy, cx) of frame f (an edge cell: over the pixels it has), in integers on the luma codes Y as they
+ * are (the first H W samples of a frame; nothing is shifted or masked):
+ *     gx = |Y(min(x + 1, W - 1), y) - Y(max(x - 1, 0), y)|,   gy likewise in y,   gt = |Y_g(x, y) - Y_f(x, y)|
+ * with g the temporal neighbour: f + 1 if f + 1 < n, else f - 1 if n > 1, else gt = 0.  At most 4 * 65535 * 256 < 2^32 per cell.
+ * 1 <= n_out <= n: the first n_out frames get a map and frame n_out - 1 may look at frame n_out (a caller that goes through a video
+ * in chunks overlaps them by one frame).  Every output is written once by a plain store: out need not be zeroed.
+ *   layout      GSVC_FRAMES_YUV444P or _YUV420P; rgb24 is refused.     depth  8, 10, 12 or 16.     cell  4, 8 or 16.
+ * Refused with an error before any launch, besides those: n outside 1 .. 65535, n_out outside 1 .. n, an odd H or W for 4:2:0, a stride
+ * below the frame's bytes (gsvc_frames_bytes), an odd base or stride for a deep format, a NULL pointer.  Nothing outside the luma planes
+ * of the n frames is read.  Does not synchronise.
+ *
+ * gsvc_detail_sample: N points drawn from a map.  cdf (int64 [cells], on the device) = the inclusive prefix sum of the flattened
+ * [T, Hc, Wc] map; its total D = cdf[cells - 1] is read on the device.  With
+ *     h(seed, i, k) = splitmix64 of seed + (5 i + k + 1) * 0x9E3779B97F4A7C15 (mod 2^64):
+ *                     z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;   z = (z ^ z >> 27) * 0x94D049BB133111EB;   h = z ^ z >> 31
+ *     mulhi64(a, b) = the upper 64 bits of a b,     f_k = (h(seed, i, k) >> 40) * 2^-24
+ * point i is uniform if D == 0 or (h(seed, i, 0) >> 40) < mix24: its pixel is p = mulhi64(h(seed, i, 1), T H W), t = p / (H W),
+ * y0 = (p mod H W) / W, x0 = p mod W, cw = ch = 1, and cell_of[i] = the cell that holds the pixel.  Otherwise r = mulhi64(h(seed, i, 1), D),
+ * cell_of[i] = the first index with cdf[index] > r (a cell of weight 0 is never drawn) = (t Hc + cy) Wc + cx, x0 = cx cell, y0 = cy cell,
+ * cw = min(cell, W - x0), ch = min(cell, H - y0).  Then, in float32,
+ *     points[i] = (fmaf(f_2, cw, x0), fmaf(f_3, ch, y0), (f_4 - 0.5) + t)          (x and y in pixels, t in frames; one rounding each)
+ * Refused with an error before any launch: cells != T Hc Wc, cells >= 2^31, mix24 > 2^24, a cell other than 4, 8, 16, T outside
+ * 1 .. 65535, a side outside 1 .. 32768, N < 1, a NULL or misaligned pointer.  Does not synchronise.
+ * ---------------------------------------------------------------------------------------------------- */
+int gsvc_frames_detail(const uint8_t *frames, int64_t stride, int32_t n, int32_t n_out, int32_t H, int32_t W, int32_t layout,
+                       int32_t depth, int32_t cell, uint32_t *out, void *stream);
+int gsvc_detail_sample(const int64_t *cdf, int64_t cells, int32_t T, int32_t H, int32_t W, int32_t cell, int32_t N, uint64_t seed,
+                       uint32_t mix24, float *points, int32_t *cell_of, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Dense optical flow of adjacent frames (csrc/flow.hip): coarse-to-fine Horn-Schunck with warping.  No weights, stencils only: the
  * same bits in every run, for every batch size and launch geometry.
  *

@@ -25,6 +25,8 @@ usage: python tools/fit_synthetic.py [--steps 2000] [--height 1080 --width 1920 
                                      video file: its frame count and size replace --frames / --height / --width; raw files: --video-size WxH)
        python tools/fit_synthetic.py --estimate-flow ...      (optical flow estimated from the frames, gsvc_amd/flow.py, instead of the synthetic
                                      video's analytic flow or a video file's --flow-dir)
+       python tools/fit_synthetic.py --init detail [--init-cell 8 --init-mix 0.25] ...      (the first anchors drawn where the luma has detail,
+                                     gsvc_amd/detail.py, instead of uniformly in the cube)
 """
 import argparse
 import copy
@@ -91,7 +93,16 @@ def main(argv=None):
     ap.add_argument("--loss-domain", choices=("rgb", "yuv420", "yuv444"), default="rgb",
                     help="where the fit takes its distortion: float RGB, or Y'CbCr planes (gsvc_amd/yuv_loss.py): those of a Y'CbCr --video "
                          "file's sample codes, else the transform of the RGB pictures")
+    ap.add_argument("--init", choices=("uniform", "detail"), default="uniform",
+                    help="where the first anchors are drawn: uniformly in the cube, or where the luma has detail (gsvc_amd/detail.py)")
+    ap.add_argument("--init-cell", type=int, choices=(4, 8, 16), default=None, help="with --init detail: the cell of the detail map in pixels (default 8)")
+    ap.add_argument("--init-mix", type=float, default=None, metavar="X",
+                    help="with --init detail: the share of the points that is still drawn uniformly, 0 .. 1 (default 0.25)")
     args = ap.parse_args(argv)
+    if args.init != "detail" and (args.init_cell is not None or args.init_mix is not None):
+        ap.error("--init-cell and --init-mix need --init detail")
+    if args.init_mix is not None and not 0.0 <= args.init_mix <= 1.0:
+        ap.error("--init-mix must lie in 0 .. 1")
 
     from gsvc_amd.arguments import cfg_20240919
     from gsvc_amd.frame import SyntheticFrameCube
@@ -140,9 +151,13 @@ def main(argv=None):
     from gsvc_amd.fit_setup import configure_fit, new_fit
     configure_fit(mp_, opt, cube, N, args.lmbda, args.slab_frames, args.densify_grad_threshold)
     opt.loss_domain = args.loss_domain
-    pc, trainer = new_fit(cube, mp_, opt, pipe, args.anchors, dev)
+    init = {"init": args.init}
+    if args.init == "detail":
+        init.update(init_cell=8 if args.init_cell is None else args.init_cell, init_mix=0.25 if args.init_mix is None else args.init_mix)
+    pc, trainer = new_fit(cube, mp_, opt, pipe, args.anchors, dev, **init)
     bg = trainer.background
-    log = {"config": {"H": H, "W": W, "frames": T, "steps": N, "anchors_init": args.anchors, "lmbda": args.lmbda,
+    log = {"config": {"H": H, "W": W, "frames": T, "steps": N, "anchors_init": args.anchors, **init,
+                      "anchors_initial": int(pc._anchor.shape[0]), "lmbda": args.lmbda,
                       "loss_domain": trainer.loss_domain, "loss_matrix": trainer.loss_matrix,
                       "slab_frames": args.slab_frames, "schedule": [opt.full_precision_training_total, opt.quantized_training_total,
                                                                     opt.entropy_constrained_train_total, opt.ste_entropy_constrained_train_total],

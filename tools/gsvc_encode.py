@@ -4,7 +4,7 @@ the video in another process, with nothing else:
 
     python tools/gsvc_encode.py clip.y4m -o clip.gsvc [--steps 2000 --lmbda 0.004 --anchors 100000 --estimate-flow]
                                 [--video-format yuv420p,bt601,full] [--video-size WxH] [--hash-format yuv420p]
-                                [--loss-domain rgb|yuv420|yuv444]
+                                [--loss-domain rgb|yuv420|yuv444] [--init detail [--init-cell 8 --init-mix 0.25]]
     python tools/gsvc_decode.py clip.gsvc -o out.y4m --strict
     python tools/gsvc_encode.py long.y4m -o long.gsvs --gop-frames 32 [--scene-cuts --cut-threshold 0.5 --min-gop 4]
 
@@ -58,7 +58,16 @@ def main(argv=None):
     ap.add_argument("--cut-threshold", type=float, default=None, metavar="X",
                     help="histogram distance in [0, 1] above which a frame starts a scene (default 0.5: a starting value, not measured)")
     ap.add_argument("--min-gop", type=int, default=None, metavar="M", help="the shortest GOP (default 4); --gop-frames must be at least 2 M")
+    ap.add_argument("--init", choices=("uniform", "detail"), default="uniform",
+                    help="where the first anchors are drawn: uniformly in the cube, or where the luma has detail (gsvc_amd/detail.py)")
+    ap.add_argument("--init-cell", type=int, choices=(4, 8, 16), default=None, help="with --init detail: the cell of the detail map in pixels (default 8)")
+    ap.add_argument("--init-mix", type=float, default=None, metavar="X",
+                    help="with --init detail: the share of the points that is still drawn uniformly, 0 .. 1 (default 0.25)")
     args = ap.parse_args(argv)
+    if args.init != "detail" and (args.init_cell is not None or args.init_mix is not None):
+        ap.error("--init-cell and --init-mix need --init detail")
+    if args.init_mix is not None and not 0.0 <= args.init_mix <= 1.0:
+        ap.error("--init-mix must lie in 0 .. 1")
     if args.gop_frames is None and (args.scene_cuts or args.cut_threshold is not None or args.min_gop is not None):
         ap.error("--scene-cuts, --cut-threshold and --min-gop need --gop-frames")
 
@@ -71,7 +80,9 @@ def main(argv=None):
     video_fmt = _frame_format(args.video_format) if args.video_format else None
     fit = dict(steps=args.steps, lmbda=args.lmbda, anchors=args.anchors, slab_frames=args.slab_frames,
                densify_grad_threshold=args.densify_grad_threshold, estimate_flow=args.estimate_flow, flow_dir=args.flow_dir,
-               video_size=(vw, vh), video_format=video_fmt, hash_format=_frame_format(args.hash_format), loss_domain=args.loss_domain)
+               video_size=(vw, vh), video_format=video_fmt, hash_format=_frame_format(args.hash_format), loss_domain=args.loss_domain,
+               init=args.init, init_cell=8 if args.init_cell is None else args.init_cell,
+               init_mix=0.25 if args.init_mix is None else args.init_mix)
     if args.gop_frames is None:
         blob, log = encode_gop(args.video, dev, **fit)
         with open(args.output, "wb") as f:
@@ -99,11 +110,13 @@ def main(argv=None):
         blobs.append(blob)
         fit_seconds += one["fit_seconds"]
         gops.append({"first": first, "frames": count, "bytes": len(blob), "bpp": 8.0 * len(blob) / (H * W * count),
-                     "fit_seconds": one["fit_seconds"], "cut": int(cut), "anchors_coded": one["anchors_coded"], "sections": one["sections"]})
+                     "fit_seconds": one["fit_seconds"], "cut": int(cut), "anchors_initial": one["anchors_initial"], "anchors_coded": one["anchors_coded"],
+                     "sections": one["sections"]})
     fps = header.get("fps") or (30, 1)
     write_sequence(args.output, blobs, W, H, fps, flags)
     log = {"output": args.output, "W": W, "H": H, "frames": T, "steps": args.steps, "fit_seconds": fit_seconds,
            "loss_domain": one["loss_domain"], "loss_matrix": one["loss_matrix"],
+           **{k: one[k] for k in ("init", "init_cell", "init_mix") if k in one},
            "hash_format": _frame_format(args.hash_format).name, "gop_frames": args.gop_frames, "min_gop": min_gop,
            "scene_cuts": cuts if args.scene_cuts else None, "cut_threshold": threshold if args.scene_cuts else None, "gops": gops}
     log["total_bytes"] = int(os.path.getsize(args.output))
