@@ -70,6 +70,16 @@ def ans_encode(symbols: torch.Tensor, mu: torch.Tensor, sigma: torch.Tensor, min
             out[:total].cpu().numpy().tobytes())
 
 
+_DECODE_CODES = {3: "a segment shorter than its state", 4: "no symbol owns the slot", 5: "a segment's bytes ran out",
+                 6: "a segment did not end with every byte used and the coder back at its initial state"}
+
+
+def _corrupt(what: str, code: int) -> str:
+    """The message for a non-zero error word of the decode kernels (csrc/ans.hip ans_decode_body)."""
+    return (f"{what}: corrupt stream or a model that differs from the encoder's "
+            f"(code {code}: {_DECODE_CODES.get(code, 'unknown')})")
+
+
 class DeferredChecks:
     """Error flags of decode launches whose check is postponed: a decoder that reads its error word after every launch
     synchronises 26 times per model; collecting them lets the launches queue back to back (and run side by side on several
@@ -88,7 +98,7 @@ class DeferredChecks:
         flags, self.flags = self.flags, []
         for code, (_, what) in zip(codes, flags):
             if code != 0:
-                raise _lib.GsvcError(f"{what}: corrupt stream or a model that differs from the encoder's (code {code})")
+                raise _lib.GsvcError(_corrupt(what, code))
 
 
 class PreparedStream:
@@ -176,7 +186,7 @@ def ans_decode(stream, mu: torch.Tensor, sigma: torch.Tensor, defer: "DeferredCh
     if defer is not None:
         defer.add(err, "ans_decode")
     elif int(err.item()) != 0:
-        raise _lib.GsvcError(f"ans_decode: corrupt stream or a model that differs from the encoder's (code {int(err.item())})")
+        raise _lib.GsvcError(_corrupt("ans_decode", int(err.item())))
     return sym[:n]
 
 
@@ -222,7 +232,7 @@ def ans_decode_many(jobs, defer: "DeferredChecks | None" = None):
     else:
         code = int(errs.max().item())
         if code != 0:
-            raise _lib.GsvcError(f"ans_decode: corrupt stream or a model that differs from the encoder's (code {code})")
+            raise _lib.GsvcError(_corrupt("ans_decode", code))
     return out
 
 

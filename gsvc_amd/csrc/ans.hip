@@ -258,6 +258,8 @@ constexpr int ANS_AHEAD = 16;     // records a decode lane keeps in flight (the 
 // One lane decodes one segment.  Everything a lane reads from memory is fetched ahead of its use: the byte stream through a
 // 16-byte register buffer (a renormalisation byte used to be a dependent global load of ~1 us each with the few waves a
 // decode launch has), the model records ANS_AHEAD symbols ahead (each record register is reloaded as soon as it is consumed).
+// error_flag (the encoder sets 1: symbol outside [min, max], 2: zero-frequency symbol): 3 a segment shorter than its 4 state bytes,
+// 4 no symbol owns the slot, 5 the segment's bytes ran out, 6 bytes left over or a state other than ANS_L behind the last symbol.
 __device__ __forceinline__ void ans_decode_body(const uint32_t *__restrict__ phi, const uint8_t *__restrict__ bytes,
                                                 const uint64_t *__restrict__ seg_offsets, int64_t n, int smin, int smax, int seg_len,
                                                 int64_t n_seg, int32_t *__restrict__ sym, int32_t *__restrict__ error_flag,
@@ -321,6 +323,9 @@ __device__ __forceinline__ void ans_decode_body(const uint32_t *__restrict__ phi
         }
         if (!ok) return;
     }
+    // the encoder starts every segment at ANS_L and the decoder undoes its steps exactly: behind the last symbol the coder must be
+    // back at that state with every byte used (a damaged payload otherwise decodes to other symbols with no error at all)
+    if (left != 0 || x != ANS_L) atomicExch(error_flag, 6);
 }
 
 __global__ void __launch_bounds__(64) k_ans_decode(const uint8_t *__restrict__ bytes, const uint64_t *__restrict__ seg_offsets,

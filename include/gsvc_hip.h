@@ -543,7 +543,9 @@ int gsvc_ans_encode(const int32_t *symbols, const float *mu, const float *sigma,
                     int32_t max_symbol, int32_t seg_len, void *scratch, uint32_t *seg_bytes, uint64_t *seg_offsets, uint8_t *out,
                     int32_t *error_flag, void *stream);
 
-/* inverse: bytes + seg_offsets[segments + 1] + the same mu, sigma -> symbols[n].  error_flag non-zero: corrupt stream.
+/* inverse: bytes + seg_offsets[segments + 1] + the same mu, sigma -> symbols[n].  error_flag non-zero: corrupt stream
+ * (3 a segment shorter than its 4 state bytes, 4 no symbol owns the slot, 5 a segment's bytes ran out, 6 a segment did not end
+ * with every byte used and the coder back at its initial state 2^23; the encoder's codes are 1 symbol outside the range, 2 zero frequency).
  * `bytes` must be readable up to 16 bytes past seg_offsets[segments] (the kernel reads the stream in aligned 16-byte pieces).
  * `scratch`: gsvc_ans_decode_scratch_bytes(n, seg_len) bytes, 16-byte aligned: the part of the model that does not depend on
  * the coder state (the cumulative frequencies of every symbol's mode) is computed by a chip-wide parallel kernel first and laid

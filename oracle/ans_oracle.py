@@ -18,6 +18,8 @@ restates that specification in plain Python integers / IEEE doubles, sharing no 
              Segment bytes = final state (big endian) followed by the emitted bytes in REVERSE order of emission (= the order the
              decoder consumes them).  Decoder: slot = x & (2^20 - 1), s = the symbol with C(s) <= slot < C(s + 1),
              x = freq (x >> 20) + slot - start, then while x < 2^23: x = x << 8 | next byte.
+  end        The encoder starts a segment at x = 2^23 and the decoder undoes its steps one by one, so behind a segment's last symbol
+             no byte is left and x = 2^23 again; a decoder refuses a segment that ends in any other way.
   container  "GSA4" | checksum u32 | n u64 | seg_len u32 | min i32 | max i32 | n_seg u64 | seg_bytes u32[n_seg] | segments  (little endian)
 """
 from __future__ import annotations
@@ -154,6 +156,8 @@ def decode_segment(buf: bytes, mu, inv, smin, smax):
             at += 1
     if at != len(buf):
         raise ValueError("ans_oracle: segment longer than its symbols need")
+    if x != L:
+        raise ValueError("ans_oracle: corrupt stream (the coder did not return to its initial state)")
     return out
 
 
