@@ -12,6 +12,7 @@ re-evaluates over all anchors several times per call are evaluated once.
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 import time
 from dataclasses import dataclass
@@ -19,7 +20,7 @@ from enum import Enum
 
 import torch
 
-from . import schedule, switches
+from . import _lib, schedule, switches
 from .encodings import STE_multistep
 
 
@@ -37,6 +38,30 @@ class RatePack:
     bit_per_feat_param: torch.Tensor = None
     bit_per_scaling_param: torch.Tensor = None
     bit_per_offsets_param: torch.Tensor = None
+    bit_per_param_sum: torch.Tensor = None     # on the first render's pack: bit_per_param summed over the batch's renders
+
+
+@dataclass
+class StepBatch:
+    """What the renders of one un-compacted batched generation pass share: the un-split tensors (rasterize_many and the loss work
+    on their row ranges) and the step's scheduling decision.  The fields that default to None are filled in later: a deferred rate's
+    sum by finish_deferred_rate, the last three by render_many.  (No slots: train._release_graph detaches the tensors through __dict__.)"""
+    scaling: torch.Tensor
+    neural_opacity: torch.Tensor
+    mask: torch.Tensor
+    seg_offsets: list
+    vis: torch.Tensor
+    xyz: torch.Tensor
+    color: torch.Tensor
+    rot: torch.Tensor
+    world: torch.Tensor
+    gpu_bound: bool
+    small_work: bool
+    bit_per_param_sum: torch.Tensor = None
+    deferred_rate: tuple = None
+    generated_event: object = None
+    viewspace: torch.Tensor = None
+    seen: torch.Tensor = None
 
 
 @dataclass
@@ -58,7 +83,14 @@ class GeneratedGaussians:
     # extras of the un-compacted ("dense") batched path, None otherwise
     visible_index: torch.Tensor = None   # int64 indices of the visible anchors (what visable_mask.nonzero() gives)
     world_xyz: torch.Tensor = None       # anchor + offsets * scaling[:, :3] before the bound clamp, per Gaussian
-    batch: object = None                 # the renders' shared un-split tensors (scaling, neural_opacity, mask, seg_offsets)
+    batch: StepBatch | None = None       # the renders' shared un-split tensors (scaling, neural_opacity, mask, seg_offsets)
+
+
+def _with_rate(gs: GeneratedGaussians, rate: RatePack) -> GeneratedGaussians:
+    """``gs`` with the pack's four values in its reference-named fields."""
+    gs.bit_per_param, gs.bit_per_feat_param = rate.bit_per_param, rate.bit_per_feat_param
+    gs.bit_per_scaling_param, gs.bit_per_offsets_param = rate.bit_per_scaling_param, rate.bit_per_offsets_param
+    return gs
 
 
 BASE_Q_FEAT, BASE_Q_SCALING, BASE_Q_OFFSETS = 1, 0.001, 0.2
@@ -111,7 +143,6 @@ def det_scatter_rows(idx, src, D, out=None):
     """dst[idx[i]] += src[i] with every target's rows added in list order (GSVC_DETERMINISTIC): a stable sort of the targets, then one
     thread per (target, channel) walks its run (csrc/generate.hip k_segment_rows_sum) — no float atomics, the same bits every run.
     ``out``: a [D, C] tensor to add to (each touched row receives ONE add of its run's sum); else a zero-filled one is returned."""
-    from . import _lib
     n = int(idx.shape[0])
     C_ = max(int(torch.Size(src.shape[1:]).numel()), 1)          # (an empty list still has a row width)
     src2 = src.reshape(n, C_).contiguous()
@@ -145,7 +176,6 @@ class _GatherFeat(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat_p, vis, seen=None, rank=None):
-        from . import _lib
         feat_p, vis = feat_p.contiguous(), vis.contiguous()
         rows, F = vis.shape[0], feat_p.shape[1]
         feat = torch.empty(rows, F, device=feat_p.device, dtype=torch.float32)
@@ -157,7 +187,6 @@ class _GatherFeat(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
         vis, seen, rank = ctx.saved_tensors
         A, F = ctx.shape
         if seen is not None:
@@ -184,7 +213,6 @@ class _GatherRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, offset_p, scaling_p, mask_p, vis, decoded, seen=None, rank=None):
-        from . import _lib
         dev = offset_p.device
         offset_p, scaling_p, mask_p, vis = (t.contiguous() for t in (offset_p, scaling_p, mask_p, vis))
         rows, K, S = vis.shape[0], offset_p.shape[1], scaling_p.shape[1]
@@ -201,7 +229,6 @@ class _GatherRows(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_off, g_scal, g_mask):
-        from . import _lib
         scaling_p, mask_p, vis, seen, rank = ctx.saved_tensors
         oshape, K, S, decoded = ctx.dims
         dev = vis.device
@@ -307,13 +334,11 @@ class StepPlan:
         chosen = None
         if fused:
             # the masks of the plan in one launch (csrc/generate.hip k_plan_masks): views side by side, their union, the rate sample
-            import ctypes
-            from . import _lib
             M = torch.empty(R, A, dtype=torch.bool, device=dev)
             present = torch.empty(A, dtype=torch.bool, device=dev)
             u = torch.rand(R, A, device=dev) if sample else None
             chosen = torch.empty(R, A, dtype=torch.bool, device=dev) if sample else None
-            vp = (ctypes.c_void_p * R)(*[m.data_ptr() for m in visible_masks])
+            vp = (C.c_void_p * R)(*[m.data_ptr() for m in visible_masks])
             _lib.check(_lib.lib().gsvc_plan_masks(vp, R, A, _lib.ptr(pc._mask), pc._mask.numel() // max(A, 1), int(bool(pc.decoded_version)),
                                                   _lib.ptr(u), float(SAMPLE_RATE), _lib.ptr(M), _lib.ptr(present), _lib.ptr(chosen),
                                                   _lib.current_stream(dev)), "gsvc_plan_masks")
@@ -335,8 +360,8 @@ class StepPlan:
             counts = big[3 * R * A + 2 * A:]                         # [R view ends | chosen pairs | distinct anchors]
             scratch = torch.empty(int(L.gsvc_plan_scans_scratch_bytes(R, A)), dtype=torch.uint8, device=dev)
             _lib.check(L.gsvc_plan_scans(_lib.ptr(M), _lib.ptr(chosen), _lib.ptr(present), R, A, _lib.ptr(scratch), _lib.ptr(c), _lib.ptr(self._flat),
-                                         _lib.ptr(sel_flat) if sample else None, ctypes.c_void_p(self.pos.data_ptr()),
-                                         ctypes.c_void_p(self._distinct.data_ptr()), ctypes.c_void_p(counts.data_ptr()), st), "gsvc_plan_scans")
+                                         _lib.ptr(sel_flat) if sample else None, C.c_void_p(self.pos.data_ptr()),
+                                         C.c_void_p(self._distinct.data_ptr()), C.c_void_p(counts.data_ptr()), st), "gsvc_plan_scans")
             self.ranks = (M.view(-1), c)                                 # for the atomic-free gather backward (_gather_rows)
             if sample:
                 self._sel_flat = sel_flat
@@ -456,8 +481,6 @@ class _GenTail(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, op_raw, offset_mask, grid_offsets, neural_offset, scale_rot, grid_scaling, anchor, K, bmin, bmax):
-        import ctypes as C
-        from . import _lib
         dev = op_raw.device
         op_raw, offset_mask = op_raw.contiguous().view(-1), offset_mask.contiguous().view(-1)
         grid_offsets, neural_offset = grid_offsets.contiguous().view(-1, 3), neural_offset.contiguous().view(-1, 3)
@@ -481,7 +504,6 @@ class _GenTail(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_no, _g_mask, g_scaling, g_rot, g_world, g_xyz):
-        from . import _lib
         op_raw, offset_mask, grid_offsets, neural_offset, scale_rot, grid_scaling, world = ctx.saved_tensors
         dev = op_raw.device
         rows, K = grid_scaling.shape[0], ctx.K
@@ -556,17 +578,30 @@ def generate_neural_gaussians(frame, pc, visible_mask=None, mode=GenerateMode.TR
     pe = torch.cat([time_emb, z_emb], dim=1)
 
     V = anchor.shape[0]
-    neural_opacity = pc.get_opacity_mlp(feat, pe).reshape(-1, 1) * offset_masks.view(-1, 1)
-    mask = (neural_opacity > 0.0).view(-1)
+    op_raw = pc.get_opacity_mlp(feat, pe)
     color = pc.get_color_mlp(feat, pe).reshape(V * K, 3)
     scale_rot = pc.get_cov_mlp(feat, pe).reshape(V * K, 7)
     neural_offset = pc.get_deform_mlp(torch.cat([feat, pe], dim=1)).reshape(V * K, 3)
+    xyz, color_a, opacity, scaling, rot, concatenated_all, mask, neural_opacity, _ = _compact_tail(
+        pc, op_raw, offset_masks, grid_offsets, neural_offset, grid_scaling, anchor, color, scale_rot)
+    return _with_rate(GeneratedGaussians(
+        xyz=xyz, color=color_a, opacity=opacity, scaling=scaling, rot=rot,
+        neural_opacity=neural_opacity, visable_mask=visible_mask, mask=mask,
+        concatenated_all=concatenated_all, time_sub=time_sub), rate)
+
+
+def _compact_tail(pc, op_raw, offset_masks, grid_offsets, neural_offset, grid_scaling, anchor, color, scale_rot):
+    """The MLP outputs of the visible anchors' K slots -> the Gaussians with opacity > 0 (reference guassian.py:232-310):
+    (xyz, color, opacity, scaling, rot) of those, then ``concatenated_all``, ``mask`` and ``neural_opacity`` over all slots and the
+    live slots' index list."""
+    neural_opacity = op_raw.reshape(-1, 1) * offset_masks.view(-1, 1)
+    mask = (neural_opacity > 0.0).view(-1)
     offsets = grid_offsets.view(-1, 3) + neural_offset
 
     # per-Gaussian table [scaling(6) | anchor(3) | colour(3) | scale_rot(7) | offset(3)], kept because the
     # optical-flow loss of the training step reads it (reference utils/loss_utils.py:108-118)
     per_anchor = torch.cat([grid_scaling, anchor], dim=-1)
-    concatenated_all = torch.cat([per_anchor.repeat_interleave(K, dim=0), color, scale_rot, offsets], dim=-1)
+    concatenated_all = torch.cat([per_anchor.repeat_interleave(pc.n_offsets, dim=0), color, scale_rot, offsets], dim=-1)
     alive_idx = mask.nonzero(as_tuple=False).squeeze(1)
     alive = concatenated_all.index_select(0, alive_idx)
     scaling_rep, anchor_rep = alive[:, 0:6], alive[:, 6:9]
@@ -575,13 +610,8 @@ def generate_neural_gaussians(frame, pc, visible_mask=None, mode=GenerateMode.TR
     scaling = scaling_rep[:, 3:] * torch.sigmoid(scale_rot_a[:, :3])
     rot = pc.rotation_activation(scale_rot_a[:, 3:7])
     xyz = torch.clamp(anchor_rep + offsets_a * scaling_rep[:, :3], pc.x_bound_min, pc.x_bound_max)
-    return GeneratedGaussians(
-        xyz=xyz, color=color_a, opacity=neural_opacity.index_select(0, alive_idx),
-        scaling=scaling, rot=rot,
-        neural_opacity=neural_opacity, visable_mask=visible_mask, mask=mask,
-        bit_per_param=rate.bit_per_param, bit_per_feat_param=rate.bit_per_feat_param,
-        bit_per_scaling_param=rate.bit_per_scaling_param, bit_per_offsets_param=rate.bit_per_offsets_param,
-        concatenated_all=concatenated_all, time_sub=time_sub)
+    opacity = neural_opacity.index_select(0, alive_idx)
+    return xyz, color_a, opacity, scaling, rot, concatenated_all, mask, neural_opacity, alive_idx
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -657,8 +687,6 @@ class _NoiseQuant(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x2, q_rows, q_scalar, noise, offsets):
-        import ctypes as C
-        from . import _lib
         dev = x2.device
         x2, noise = x2.contiguous(), noise.contiguous()
         q = q_rows.contiguous() if q_rows is not None else None
@@ -677,7 +705,6 @@ class _NoiseQuant(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
         x2, q, noise, centre = ctx.saved_tensors
         dev = x2.device
         dx = torch.empty_like(x2)
@@ -711,8 +738,6 @@ def _seg_ste(x, Q, seg, x_mean):
         # three launches (the step's per-render mean, the truncated bounds, the quantiser) instead of a dozen tensor operations;
         # the same expression operation by operation (csrc/quant.hip k_ste_fwd).  The result carries no graph: the reference
         # detaches it (guassian.py:205-207)
-        import ctypes as C
-        from . import _lib
         with torch.no_grad():
             x2 = x.detach().reshape(x.shape[0], -1).contiguous()
             q = Q.detach().reshape(-1).contiguous() if isinstance(Q, torch.Tensor) else None
@@ -751,8 +776,6 @@ class _SampledRate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, grid_scaling, grid_offsets, offset_masks, Q_feat, Q_scaling, Q_offsets, mean_f, scale_f, mean_s, scale_s,
                 mean_o, scale_o, sel, sel_ctx, x_mean, bounds, K):
-        import ctypes as C
-        from . import _lib
         dev = feat.device
         xs = [feat.contiguous(), grid_scaling.contiguous(), grid_offsets.contiguous().view(grid_offsets.shape[0], -1)]
         means = [mean_f.contiguous(), mean_s.contiguous(), mean_o.contiguous()]
@@ -784,8 +807,6 @@ class _SampledRate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gS):
-        import ctypes as C
-        from . import _lib
         t = ctx.saved_tensors
         xs, means, scales, Qs, mask, scratch = t[0:3], t[3:6], t[6:9], t[9:12], t[12], t[15]
         dev = mask.device
@@ -811,7 +832,6 @@ class _QRows(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, adj_f, adj_s, adj_o, ctx_row, q_f, q_s, q_o, raw=False):
-        from . import _lib
         adj = [a.contiguous().view(-1) for a in (adj_f, adj_s, adj_o)]
         D, dev = adj[0].shape[0], adj[0].device
         ctx_row = ctx_row.contiguous() if ctx_row is not None else None
@@ -826,7 +846,6 @@ class _QRows(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_f, g_s, g_o):
-        from . import _lib
         ctx_row, *adj = ctx.saved_tensors
         gs = [None if g is None else g.contiguous() for g in (g_f, g_s, g_o)]
         dev = next(g.device for g in gs if g is not None) if any(g is not None for g in gs) else None
@@ -858,8 +877,6 @@ class _RateNorm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, S, offset_masks, sel, bounds, dims, K):
-        import ctypes as C
-        from . import _lib
         dev = S.device
         R = len(bounds) - 1
         S, sel = S.contiguous(), sel.contiguous()
@@ -879,7 +896,6 @@ class _RateNorm(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out, g_sum):
-        from . import _lib
         (coef,) = ctx.saved_tensors
         if g_out is None and g_sum is None:
             return None, None, None, None, None, None
@@ -912,7 +928,6 @@ def _param_means(pc):
     if zo is not None and zo.means is not None:      # z-range ownership: the owners' means (a replica's own rows are partly stale)
         return zo.means
 
-    from . import _lib
     f, sc, o = pc._anchor_feat, getattr(pc, "_scaling", None), pc._offset
     if sc is None or not (f.is_cuda and f.dtype == sc.dtype == o.dtype == torch.float32 and f.is_contiguous() and sc.is_contiguous() and o.is_contiguous()):
         with torch.no_grad():
@@ -939,32 +954,19 @@ def _rate_many(pc, seg, feat, grid_scaling, grid_offsets, offset_masks, Q_feat, 
     fused = (feat.is_cuda and R <= 16 and all(isinstance(q, torch.Tensor) and q.numel() == feat.shape[0] for q in (Q_feat, Q_scaling, Q_offsets))
              and not switches.NO_FUSED_RATE)
     compact = hasattr(ec, "rows")        # SampledEntropyContext: mean / scale exist for the sampled rows only, row i = i-th sampled row
-    if fused and sel is not None and offset_masks.dtype == torch.float32:
-        # everything on the device in a dozen launches: the parameter means, the sampled bits summed per render (k_rate_sample),
-        # and their normalisation with the keep rates and sample sizes (k_rate_normalise)
-        sel_ec = sel if ec_row is None else ec_row.index_select(0, sel)
-        if compact:
-            ec, sel_ctx = ec.rows(sel_ec), _iota(dev, sel.shape[0])
-        else:
-            sel_ctx = None if ec_row is None else sel_ec
-        S = _SampledRate.apply(feat, grid_scaling, grid_offsets, offset_masks, Q_feat, Q_scaling, Q_offsets, ec.mean_feat, ec.scale_feat,
-                               ec.mean_scaling, ec.scale_scaling, ec.mean_offsets, ec.scale_offsets, sel,
-                               sel_ctx, _param_means(pc), seg.bounds, K)
-        out, total = _RateNorm.apply(S, offset_masks, sel, seg.bounds, (float(feat.shape[1]), float(grid_scaling.shape[1]), float(3 * K)), K)
-        packs = [RatePack(bit_per_param=out[r, 0], bit_per_feat_param=out[r, 1], bit_per_scaling_param=out[r, 2],
-                          bit_per_offsets_param=out[r, 3]) for r in range(R)]
-        packs[0].bit_per_param_sum = total        # sum over the renders: the fitting loss takes this one scalar (one backward node)
-        return packs
-    with torch.no_grad():
-        live = (torch.sum(offset_masks, dim=1)[:, 0] > 0)
-        kr = seg.sums(live) / seg.counts_t.clamp_min(1)                  # keep rate per render
-        if sel is None:
-            chosen = (torch.rand_like(feat[:, 0]) <= SAMPLE_RATE) & live
-            sel = chosen.nonzero(as_tuple=False).squeeze(1)
-        sel_seg = seg.seg_id.index_select(0, sel)
-        # selected rows per render: the selection is sorted by row, so the counts are differences of its positions of the bounds
-        edges = torch.searchsorted(sel, seg.bounds_t)
-        n_sel = (edges[1:] - edges[:-1]).to(torch.float32)
+    dims = [float(feat.shape[1]), float(grid_scaling.shape[1]), float(3 * K)]     # coded elements per sampled row and group
+    on_device = fused and sel is not None and offset_masks.dtype == torch.float32
+    if not on_device:
+        with torch.no_grad():
+            live = (torch.sum(offset_masks, dim=1)[:, 0] > 0)
+            kr = seg.sums(live) / seg.counts_t.clamp_min(1)                  # keep rate per render
+            if sel is None:
+                chosen = (torch.rand_like(feat[:, 0]) <= SAMPLE_RATE) & live
+                sel = chosen.nonzero(as_tuple=False).squeeze(1)
+            sel_seg = seg.seg_id.index_select(0, sel)
+            # selected rows per render: the selection is sorted by row, so the counts are differences of its positions of the bounds
+            edges = torch.searchsorted(sel, seg.bounds_t)
+            n_sel = (edges[1:] - edges[:-1]).to(torch.float32)
     sel_ec = sel if ec_row is None else ec_row.index_select(0, sel)
     sel_ctx = None if ec_row is None else sel_ec
     if compact:
@@ -972,16 +974,18 @@ def _rate_many(pc, seg, feat, grid_scaling, grid_offsets, offset_masks, Q_feat, 
         sel_ec = sel_ctx = _iota(dev, sel.shape[0])
     if fused:
         # fused path (csrc/rate.hip k_rate_sample): gathers, per-render clamp bounds, offset mask and per-render sums in one launch
-        xm = _param_means(pc)
         S = _SampledRate.apply(feat, grid_scaling, grid_offsets, offset_masks, Q_feat, Q_scaling, Q_offsets, ec.mean_feat, ec.scale_feat,
                                ec.mean_scaling, ec.scale_scaling, ec.mean_offsets, ec.scale_offsets, sel,
-                               sel_ctx, xm, seg.bounds, K)
-        dims = host_values([float(feat.shape[1]), float(grid_scaling.shape[1]), float(3 * K)], dev)
-        N = n_sel.unsqueeze(1) * dims
-        per = S / N * kr.unsqueeze(1)
-        tot = S.sum(dim=1) / N.sum(dim=1) * kr
-        return [RatePack(bit_per_param=tot[r], bit_per_feat_param=per[r, 0], bit_per_scaling_param=per[r, 1],
-                         bit_per_offsets_param=per[r, 2]) for r in range(R)]
+                               sel_ctx, _param_means(pc), seg.bounds, K)
+        if on_device:
+            # everything on the device in a dozen launches: the parameter means, the sampled bits summed per render (k_rate_sample),
+            # and their normalisation with the keep rates and sample sizes (k_rate_normalise)
+            out, total = _RateNorm.apply(S, offset_masks, sel, seg.bounds, dims, K)
+            packs = [RatePack(bit_per_param=out[r, 0], bit_per_feat_param=out[r, 1], bit_per_scaling_param=out[r, 2],
+                              bit_per_offsets_param=out[r, 3]) for r in range(R)]
+            packs[0].bit_per_param_sum = total        # sum over the renders: the fitting loss takes this one scalar (one backward node)
+            return packs
+        return _rate_packs(S, n_sel, dims, kr)
     # steps of the chosen rows, the three groups side by side; clamp bounds = x_mean -+ 15000 * (mean step of the row's render)
     Q3 = torch.cat([Q_feat.reshape(-1, 1), Q_scaling.reshape(-1, 1), Q_offsets.reshape(-1, 1)], dim=1).index_select(0, sel)
     Q3T = Q3.t().contiguous()                                                     # [3, n_sel]: one contiguous row per group
@@ -997,12 +1001,17 @@ def _rate_many(pc, seg, feat, grid_scaling, grid_offsets, offset_masks, Q_feat, 
                                 Q3T[g], 0.0, lo[g], hi[g], True) for g in range(3)]
     bits[2] = bits[2] * offset_masks.index_select(0, sel).repeat(1, 1, 3).view(-1, 3 * K)
     S = torch.zeros(R, 3, device=dev).index_add_(0, sel_seg, torch.stack([b.sum(dim=1) for b in bits], dim=1))   # [R, 3] bit sums
-    dims = host_values([float(bits[0].shape[1]), float(bits[1].shape[1]), float(bits[2].shape[1])], dev)
-    N = n_sel.unsqueeze(1) * dims                                                 # coded elements per render and group
+    return _rate_packs(S, n_sel, dims, kr)
+
+
+def _rate_packs(S, n_sel, dims, kr):
+    """The renders' RatePacks from their bit sums S [R, 3], sample sizes n_sel [R] and keep rates kr [R]; ``dims``: the coded
+    elements of a sampled row per group (reference guassian.py:110-132)."""
+    N = n_sel.unsqueeze(1) * host_values(dims, S.device)                          # coded elements per render and group
     per = S / N * kr.unsqueeze(1)
     tot = S.sum(dim=1) / N.sum(dim=1) * kr
     return [RatePack(bit_per_param=tot[r], bit_per_feat_param=per[r, 0], bit_per_scaling_param=per[r, 1],
-                     bit_per_offsets_param=per[r, 2]) for r in range(R)]
+                     bit_per_offsets_param=per[r, 2]) for r in range(S.shape[0])]
 
 
 def finish_deferred_rate(gss_list):
@@ -1011,11 +1020,10 @@ def finish_deferred_rate(gss_list):
     recorded behind the noise quantisation).  The current stream waits for the result; the rate's autograd nodes belong to that
     stream, so their backward (the first nodes of the step's backward) runs next to the rasterizer's backward instead of in
     front of it.  Fills the renders' ``bit_per_*`` and the batch's ``bit_per_param_sum``; no-op when nothing was deferred."""
-    batch = getattr(gss_list[0], "batch", None) if gss_list else None
-    pending = getattr(batch, "deferred_rate", None)
-    if pending is None:
+    batch = gss_list[0].batch if gss_list else None
+    if batch is None or batch.deferred_rate is None:
         return
-    rate, ready, reads = pending
+    rate, ready, reads = batch.deferred_rate
     batch.deferred_rate = None
     dev = gss_list[0].xyz.device
     main = torch.cuda.current_stream(dev)
@@ -1025,13 +1033,12 @@ def finish_deferred_rate(gss_list):
     with torch.cuda.stream(rs):
         packs = rate()
     main.wait_stream(rs)
-    total = getattr(packs[0], "bit_per_param_sum", None)
+    total = packs[0].bit_per_param_sum
     for t in [total] + [v for p in packs for v in (p.bit_per_param, p.bit_per_feat_param, p.bit_per_scaling_param, p.bit_per_offsets_param)]:
         if isinstance(t, torch.Tensor):
             t.record_stream(main)            # allocated on the rate stream, read by the loss on this one
     for gs, p in zip(gss_list, packs):
-        gs.bit_per_param, gs.bit_per_feat_param = p.bit_per_param, p.bit_per_feat_param
-        gs.bit_per_scaling_param, gs.bit_per_offsets_param = p.bit_per_scaling_param, p.bit_per_offsets_param
+        _with_rate(gs, p)
     batch.bit_per_param_sum = total
 
 
@@ -1072,8 +1079,6 @@ def _embed_rows(pc, frames, anchor, seg):
             and all(getattr(e, "include_input", False) and getattr(e, "input_dims", 0) == 1 for e in (et, ez))
             and et.freq_bands.numel() == ez.freq_bands.numel() <= 24
             and all(torch.equal(e.freq_bands, 2.0 ** torch.arange(e.freq_bands.numel(), dtype=e.freq_bands.dtype)) for e in (et, ez))):
-        import ctypes as C
-        from . import _lib
         F = int(ez.freq_bands.numel())
         pe = torch.empty(seg.rows, 2 * (2 * F + 1), device=anchor.device, dtype=torch.float32)
         bounds = (C.c_int64 * (seg.R + 1))(*seg.bounds)
@@ -1101,12 +1106,11 @@ class _ViewRows(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        from . import _lib
         src_a, src_b = ctx.saved_tensors
         g = g.contiguous()
-        C = g[0].numel() if g.shape[0] else 1
+        C_ = g[0].numel() if g.shape[0] else 1
         out = torch.empty((ctx.rows_u,) + tuple(g.shape[1:]), device=g.device, dtype=torch.float32)
-        _lib.check(_lib.lib().gsvc_pair_rows_sum(_lib.ptr(g), _lib.ptr(src_a), _lib.ptr(src_b), ctx.rows_u, C, _lib.ptr(out),
+        _lib.check(_lib.lib().gsvc_pair_rows_sum(_lib.ptr(g), _lib.ptr(src_a), _lib.ptr(src_b), ctx.rows_u, C_, _lib.ptr(out),
                                                  _lib.current_stream(g.device)), "gsvc_pair_rows_sum")
         return out, None, None, None
 
@@ -1130,8 +1134,6 @@ def _film_rows(pc, frames, plan, vis, seg, anchor_all):
         # FiLM row (f, a): the row of a in views 2 f and 2 f + 1 (scan of the flattened view masks - 1), -1 if unseen
         Mflat, c = plan.ranks
         if vis.is_cuda and R <= 16 and Mflat.dtype == torch.bool and c.dtype == torch.int64 and seg.rows < 2 ** 31 and F * D < 2 ** 31:
-            import ctypes as C
-            from . import _lib
             maps = torch.empty(seg.rows + 2 * F * D, dtype=torch.int32, device=dev)
             row_of, src_a, src_b = maps[:seg.rows], maps[seg.rows:seg.rows + F * D], maps[seg.rows + F * D:]
             _lib.check(_lib.lib().gsvc_film_row_maps(_lib.ptr(vis.contiguous()), (C.c_int64 * (R + 1))(*seg.bounds), R, _lib.ptr(plan.pos.contiguous()),
@@ -1212,8 +1214,7 @@ def generate_neural_gaussians_many(frames, pc, visible_masks, mode=GenerateMode.
     bound = schedule.gpu_bound(seg.rows)
     schedule.host_bound_step = bool(vis.is_cuda and torch.is_grad_enabled() and not bound and "GSVC_MANY_MIN_ROWS" not in os.environ)
     gens = [getattr(pc, n) for n in ("get_opacity_mlp", "get_color_mlp", "get_cov_mlp")]
-    deform_mods = list(pc.get_deform_mlp) if isinstance(pc.get_deform_mlp, torch.nn.Sequential) else []
-    deform_linears = deform_mods[0::2]
+    deform_linears = _mlp.deform_chain_linears(pc.get_deform_mlp)      # (None: not the chain kernels' network)
     seg_u = feat_u = pe_u = None
     if share is not None:
         pe_u, row_of, src_a, src_b = share
@@ -1221,9 +1222,7 @@ def generate_neural_gaussians_many(frames, pc, visible_masks, mode=GenerateMode.
         F_, D_ = R // 2, int(plan.distinct.shape[0])
         with region('gen.gather'):
             (feat_u,) = _gather_rows(pc, plan.distinct.repeat(F_), None, parts="feat")
-        if (all(hasattr(g, "film") and hasattr(g, "out_linear") for g in gens)
-                and all(isinstance(m, torch.nn.Linear) for m in deform_linears) and all(isinstance(m, torch.nn.GELU) for m in deform_mods[1::2])
-                and _mlp.chain_usable(feat_u, pe_u, gens, deform_linears)):
+        if _mlp.chain_usable(feat_u, pe_u, gens, deform_linears):
             seg_u = _Segments([D_] * F_, dev)
         else:
             share = feat_u = pe_u = None          # not the production widths: per view, layer by layer
@@ -1236,7 +1235,7 @@ def generate_neural_gaussians_many(frames, pc, visible_masks, mode=GenerateMode.
         else:
             feat, grid_offsets, grid_scaling, offset_masks = _gather_rows(pc, vis, ranks)
     rates = [RatePack() for _ in range(R)]
-    deferred = []
+    deferred = None
     Q_feat, Q_scaling, Q_offsets = BASE_Q_FEAT, BASE_Q_SCALING, BASE_Q_OFFSETS
     time_sub = 0
     # the conditioning input and the generators' FiLM networks depend on the anchors' z only: issued FIRST, their twelve large
@@ -1249,8 +1248,6 @@ def generate_neural_gaussians_many(frames, pc, visible_masks, mode=GenerateMode.
     # (decoding hands in the cached feature-only half of the generators: with the production widths the forward-only chain kernels,
     # which read the features once and keep a row block in registers through all layers, are faster per frame and are preferred)
     chain = ((trunks is None or (not torch.is_grad_enabled() and not switches.NO_DECODE_CHAIN))
-             and all(hasattr(g, "film") and hasattr(g, "out_linear") for g in gens)
-             and all(isinstance(m, torch.nn.Linear) for m in deform_linears) and all(isinstance(m, torch.nn.GELU) for m in deform_mods[1::2])
              and (seg_u is not None or _mlp.chain_usable(feat, pe, gens, deform_linears)))
     if chain:
         trunks = None
@@ -1260,16 +1257,14 @@ def generate_neural_gaussians_many(frames, pc, visible_masks, mode=GenerateMode.
                 net = getattr(pc, name)
                 films[name] = net.film_nets(pe) if hasattr(net, "film_nets") else None
 
-    rows_work = None       # the phase's work on (offsets, scaling, masks) rows: behind the generators when they are gathered late
+    # what the phase leaves for the (scaling, offsets) rows, done behind the generators when they are gathered late (finish_rows):
+    # their quantiser (None, _seg_noise_quant or _seg_ste with the means ``pm``) and whether the sampled rate follows
+    row_quant, rate_follows, pm = None, False, None
     if mode in (GenerateMode.TRAINING_FULL_PRECISION, GenerateMode.DECODING_AS_IS):
         pass
     elif mode == GenerateMode.TRAINING_QUANTIZED:
         feat = _seg_noise_quant(feat, Q_feat, seg)
-
-        def rows_work():      # the draws keep their order (features, scalings, offsets): nothing in between draws
-            nonlocal grid_offsets, grid_scaling
-            grid_scaling = _seg_noise_quant(grid_scaling, Q_scaling, seg)
-            grid_offsets = _seg_noise_quant(grid_offsets, Q_offsets, seg)
+        row_quant = _seg_noise_quant
     elif mode == GenerateMode.TRAINING_ENTROPY:
         # the priors' mean / scale are read at the rate sample's rows only (reference guassian.py:99-113): their networks run on
         # those rows (SampledEntropyContext); GSVC_CTX_ALL_ROWS=1 keeps the all-rows form (A/B timing, the equivalence test)
@@ -1287,15 +1282,7 @@ def generate_neural_gaussians_many(frames, pc, visible_masks, mode=GenerateMode.
                 Q_feat, Q_scaling, Q_offsets = (Q_feat * rows_of(ec.Q_feat_adj), Q_scaling * rows_of(ec.Q_scaling_adj),
                                                 Q_offsets * rows_of(ec.Q_offsets_adj))
             feat = _seg_noise_quant(feat, Q_feat, seg)
-
-        def rows_work():
-            # the same noise draws in the same order (features, scalings, offsets) wherever this runs: nothing between the
-            # features' quantisation and this draws from the generator
-            nonlocal grid_offsets, grid_scaling, rates
-            with region('gen.noise_quant'):
-                grid_scaling = _seg_noise_quant(grid_scaling, Q_scaling, seg)
-                grid_offsets = _seg_noise_quant(grid_offsets, Q_offsets.unsqueeze(1), seg)
-            rates = rate_now_or_later()
+        row_quant, rate_follows = _seg_noise_quant, True
     elif mode == GenerateMode.TRAININ_STE_ENTROPY:
         ec, ec_row = _entropy_context_distinct(pc, anchor_all, vis, plan, sampled=vis.is_cuda and not switches.CTX_ALL_ROWS)
         rows_of = (lambda t: t) if ec_row is None else (lambda t: t.index_select(0, ec_row))  # noqa: E731
@@ -1313,40 +1300,46 @@ def generate_neural_gaussians_many(frames, pc, visible_masks, mode=GenerateMode.
             # within 1e-3 of an integer, and the clamp only acts 15000 steps from the mean
             feat_u = _seg_ste(feat_u, (BASE_Q_FEAT * ec.Q_feat_adj.detach()).repeat(R // 2, 1), seg_u, mean_feat)
             feat = feat_u.index_select(0, row_of)      # (detached: the rate reads it per view row)
-
-        def rows_work():
-            nonlocal grid_offsets, grid_scaling, rates
-            grid_scaling = _seg_ste(grid_scaling, Q_scaling, seg, pm[1:2] if pm is not None else pc.get_scaling.mean())
-            grid_offsets = _seg_ste(grid_offsets, Q_offsets.unsqueeze(1), seg, pm[2:3] if pm is not None else pc._offset.mean())
-            rates = rate_now_or_later()
+        row_quant, rate_follows = _seg_ste, True
     else:
         raise ValueError(f"Unknown mode {mode}")
 
-    def rate_now_or_later():
-        """The sampled rate of the two entropy phases (runs once the row tensors are in their final form)."""
+    def finish_rows(grid_offsets, grid_scaling, offset_masks):
+        """(offsets, scaling, masks) of the rows in their final form and the sampled rate of the two entropy phases, which reads
+        them: the late gather, the phase's quantiser, the rate now or deferred.  Returns them, the renders' RatePacks and the
+        deferred rate (None: not deferred) — returned, not kept in a variable of the enclosing function: the rate's closure would
+        be in a reference cycle with it, and the step's graph would live until the cycle collector's next pass."""
+        if late_rows:
+            grid_offsets, grid_scaling, offset_masks = _gather_rows(pc, vis, ranks, parts="rows")
+        if row_quant is not None:
+            # the same noise draws in the same order (features, scalings, offsets) wherever this runs: nothing between the
+            # features' quantisation and this draws from the generator
+            q_off = Q_offsets.unsqueeze(1) if isinstance(Q_offsets, torch.Tensor) else Q_offsets
+            with region('gen.noise_quant'):
+                if row_quant is _seg_ste:
+                    grid_scaling = _seg_ste(grid_scaling, Q_scaling, seg, pm[1:2] if pm is not None else pc.get_scaling.mean())
+                    grid_offsets = _seg_ste(grid_offsets, q_off, seg, pm[2:3] if pm is not None else pc._offset.mean())
+                else:
+                    grid_scaling = _seg_noise_quant(grid_scaling, Q_scaling, seg)
+                    grid_offsets = _seg_noise_quant(grid_offsets, q_off, seg)
+        if not rate_follows:
+            return grid_offsets, grid_scaling, offset_masks, rates, None
+
         def rate():
             with region('gen.rate'):
                 return _rate_many(pc, seg, feat, grid_scaling, grid_offsets, offset_masks, Q_feat, Q_scaling, Q_offsets, ec, ec_row,
                                   sel=plan.sel if plan is not None else None)
-        if (defer_rate and dense and late_rows and plan is not None and plan.sel is not None and vis.is_cuda
+        if not (defer_rate and dense and late_rows and plan is not None and plan.sel is not None and vis.is_cuda
                 and bound and not switches.NO_RATE_OVERLAP):
-            # the sampled rate — three small networks on ~10 k rows and a dozen reductions, launch-bound — is issued by the caller
-            # BEHIND the rasterizer's launches, on its own stream (finish_deferred_rate): it runs under the compositing kernels
-            # forward and, its autograd nodes living on that stream, under the rasterizer's backward
-            reads = [feat, grid_scaling, grid_offsets, offset_masks, Q_feat, Q_scaling, Q_offsets, ec_row, plan.sel, ec]
-            ready = torch.cuda.current_stream(vis.device).record_event()
-            deferred.append((rate, ready, reads))
-            return rates
-        return rate()
-
-    def rows_now():
-        nonlocal grid_offsets, grid_scaling, offset_masks
-        if late_rows:
-            grid_offsets, grid_scaling, offset_masks = _gather_rows(pc, vis, ranks, parts="rows")
-        if rows_work is not None:
-            rows_work()
+            return grid_offsets, grid_scaling, offset_masks, rate(), None
+        # the sampled rate — three small networks on ~10 k rows and a dozen reductions, launch-bound — is issued by the caller
+        # BEHIND the rasterizer's launches, on its own stream (finish_deferred_rate): it runs under the compositing kernels
+        # forward and, its autograd nodes living on that stream, under the rasterizer's backward
+        reads = [feat, grid_scaling, grid_offsets, offset_masks, Q_feat, Q_scaling, Q_offsets, ec_row, plan.sel, ec]
+        ready = torch.cuda.current_stream(vis.device).record_event()
+        return grid_offsets, grid_scaling, offset_masks, rates, (rate, ready, reads)
     if not late_rows:
-        rows_now()
+        grid_offsets, grid_scaling, offset_masks, rates, deferred = finish_rows(grid_offsets, grid_scaling, offset_masks)
 
     rows = seg.rows
     with region('gen.mlps'):
@@ -1372,7 +1365,7 @@ def generate_neural_gaussians_many(frames, pc, visible_masks, mode=GenerateMode.
         if not chain:
             neural_offset = pc.get_deform_mlp(torch.cat([feat, pe], dim=1)).reshape(rows * K, 3)
     if late_rows:
-        rows_now()
+        grid_offsets, grid_scaling, offset_masks, rates, deferred = finish_rows(grid_offsets, grid_scaling, offset_masks)
     if dense:
         # opacity mask, sigmoid scaling, normalised rotation, world position, bound clamp: one kernel (csrc/generate.hip)
         neural_opacity, mask, scaling, rot, world, xyz = _GenTail.apply(
@@ -1381,44 +1374,28 @@ def generate_neural_gaussians_many(frames, pc, visible_masks, mode=GenerateMode.
         # per-render pieces by split (one cat in backward per tensor, instead of a zero-fill + copy + add per slice)
         sizes = [c * K for c in seg.counts]
         parts = [t.split(sizes, dim=0) for t in (xyz, color, neural_opacity, scaling, rot, world)]
-        from types import SimpleNamespace
-        batch = SimpleNamespace(scaling=scaling, neural_opacity=neural_opacity, mask=mask, seg_offsets=[b * K for b in seg.bounds], vis=vis,
-                                xyz=xyz, color=color, rot=rot, world=world,      # the un-split tensors: rasterize_many works on their row ranges
-                                bit_per_param_sum=getattr(rates[0], "bit_per_param_sum", None),
-                                deferred_rate=deferred[0] if deferred else None,
-                                gpu_bound=bound, small_work=bool(vis.is_cuda and bound and not switches.NO_RATE_OVERLAP))
+        batch = StepBatch(scaling=scaling, neural_opacity=neural_opacity, mask=mask, seg_offsets=[b * K for b in seg.bounds], vis=vis,
+                          xyz=xyz, color=color, rot=rot, world=world,      # the un-split tensors: rasterize_many works on their row ranges
+                          bit_per_param_sum=rates[0].bit_per_param_sum,
+                          deferred_rate=deferred,
+                          gpu_bound=bound, small_work=bool(vis.is_cuda and bound and not switches.NO_RATE_OVERLAP))
         out = []
         for r, gs in enumerate(seg.slices(K)):
-            out.append(GeneratedGaussians(
+            out.append(_with_rate(GeneratedGaussians(
                 xyz=parts[0][r], color=parts[1][r], opacity=parts[2][r], scaling=parts[3][r], rot=parts[4][r],
                 neural_opacity=parts[2][r], visable_mask=visible_masks[r], mask=mask[gs],
-                bit_per_param=rates[r].bit_per_param, bit_per_feat_param=rates[r].bit_per_feat_param,
-                bit_per_scaling_param=rates[r].bit_per_scaling_param, bit_per_offsets_param=rates[r].bit_per_offsets_param,
-                concatenated_all=None, time_sub=time_sub, visible_index=vis_list[r], world_xyz=parts[5][r], batch=batch))
+                concatenated_all=None, time_sub=time_sub, visible_index=vis_list[r], world_xyz=parts[5][r], batch=batch), rates[r]))
         return out
-    neural_opacity = op_raw.reshape(-1, 1) * offset_masks.view(-1, 1)
-    mask = (neural_opacity > 0.0).view(-1)
-    offsets = grid_offsets.view(-1, 3) + neural_offset
-    per_anchor = torch.cat([grid_scaling, anchor], dim=-1)
-    concatenated_all = torch.cat([per_anchor.repeat_interleave(K, dim=0), color, scale_rot, offsets], dim=-1)
-    alive_idx = mask.nonzero(as_tuple=False).squeeze(1)
-    alive = concatenated_all.index_select(0, alive_idx)
-    scaling_rep, anchor_rep = alive[:, 0:6], alive[:, 6:9]
-    color_a, scale_rot_a, offsets_a = alive[:, 9:12], alive[:, 12:19], alive[:, 19:22]
-    scaling = scaling_rep[:, 3:] * torch.sigmoid(scale_rot_a[:, :3])
-    rot = pc.rotation_activation(scale_rot_a[:, 3:7])
-    xyz = torch.clamp(anchor_rep + offsets_a * scaling_rep[:, :3], pc.x_bound_min, pc.x_bound_max)
-    opacity = neural_opacity.index_select(0, alive_idx)
+    xyz, color_a, opacity, scaling, rot, concatenated_all, mask, neural_opacity, alive_idx = _compact_tail(
+        pc, op_raw, offset_masks, grid_offsets, neural_offset, grid_scaling, anchor, color, scale_rot)
     # split the compacted Gaussians back into the R renders (one host read of R+1 offsets)
     edges = host_values([b * K for b in seg.bounds], dev)
     cut = torch.searchsorted(alive_idx, edges).tolist()
     out = []
     for r, (rs, gs) in enumerate(zip(seg.slices(), seg.slices(K))):
         a = slice(cut[r], cut[r + 1])
-        out.append(GeneratedGaussians(
+        out.append(_with_rate(GeneratedGaussians(
             xyz=xyz[a], color=color_a[a], opacity=opacity[a], scaling=scaling[a], rot=rot[a],
             neural_opacity=neural_opacity[gs], visable_mask=visible_masks[r], mask=mask[gs],
-            bit_per_param=rates[r].bit_per_param, bit_per_feat_param=rates[r].bit_per_feat_param,
-            bit_per_scaling_param=rates[r].bit_per_scaling_param, bit_per_offsets_param=rates[r].bit_per_offsets_param,
-            concatenated_all=concatenated_all[gs], time_sub=time_sub))
+            concatenated_all=concatenated_all[gs], time_sub=time_sub), rates[r]))
     return out

@@ -324,9 +324,10 @@ def calc_optical_loss(render_results1_f, render_results1_b, render_results2_f, r
                       x_min, y_min, scale, x_pix_max: int, y_pix_max: int, n_offsets=10):
     if render_results1_f.dense:
         rs = (render_results1_f, render_results1_b, render_results2_f, render_results2_b)
+        # (getattr: callers hand this function renders of their own making, whose Gaussians are any object with world_xyz / mask)
         batch = getattr(rs[0].generated_gaussians, "batch", None)
-        if (batch is not None and getattr(batch, "world", None) is not None and batch.world.is_cuda and len(batch.seg_offsets) == 5
-                and all(getattr(r.generated_gaussians, "batch", None) is batch for r in rs)):
+        if (batch is not None and batch.world.is_cuda and len(batch.seg_offsets) == 5
+                and all(r.generated_gaussians.batch is batch for r in rs)):
             # the four renders are row ranges of the batch's tensors, in this order: both pairs in one pass
             return _OpticalMany.apply(batch.world, batch.mask, batch.vis, batch.seg_offsets, ((0, 2), (1, 3)),
                                       optical_flow.to(batch.world.device), n_offsets, rs[0].visible_mask.shape[0], x_min, y_min, scale,

@@ -521,6 +521,14 @@ def _act_code(net):
     return {"Tanh": ACT_TANH, "Sigmoid": ACT_SIGMOID, "Identity": ACT_NONE}.get(type(net.out_act).__name__)
 
 
+def deform_chain_linears(net):
+    """The nn.Linear layers of mlp_deform when it is Linear, GELU, Linear, ... (what the chain kernels compute), else None."""
+    mods = list(net) if isinstance(net, torch.nn.Sequential) else None
+    if mods is None or not (all(isinstance(m, torch.nn.Linear) for m in mods[0::2]) and all(isinstance(m, torch.nn.GELU) for m in mods[1::2])):
+        return None
+    return mods[0::2]
+
+
 def chain_usable(feat, cond, gens, deform_linears):
     """The chain kernels exist for the production widths only (feature 50, condition 66, hidden 100, outputs 10 / 30 / 70 and
     30) and need tall contiguous fp32 CUDA matrices; the condition must not require a gradient."""
@@ -532,12 +540,14 @@ def chain_usable(feat, cond, gens, deform_linears):
     if feat.shape[1] != 50 or cond.shape[1] != 66:
         return False
     for net in gens:
+        if not (hasattr(net, "film") and hasattr(net, "out_linear")):
+            return False
         if _act_code(net) is None or net.linear1.out_features != 100 or net.out_linear.out_features not in (10, 30, 70):
             return False
         if any(l.bias is None for l in (net.linear1, net.linear2, net.out_linear, net.film.fc_gamma0, net.film.fc_gamma1,
                                         net.film.fc_beta0, net.film.fc_beta1)):
             return False
-    if len(deform_linears) != 5 or any(l.bias is None for l in deform_linears):
+    if deform_linears is None or len(deform_linears) != 5 or any(l.bias is None for l in deform_linears):
         return False
     dims = [(l.in_features, l.out_features) for l in deform_linears]
     return dims == [(116, 100), (100, 100), (100, 100), (100, 100), (100, 30)]

@@ -933,12 +933,12 @@ class GaussianModel(nn.Module):
                 self.training_statis(r)
             return
         K, A = self.n_offsets, self.opacity_accum.shape[0]
-        batch = getattr(renders[0].generated_gaussians, "batch", None)
-        if batch is not None and len(renders) > 1 and getattr(batch, "vis", None) is not None:
+        batch = renders[0].generated_gaussians.batch
+        if batch is not None and len(renders) > 1:
             vi, op_all = batch.vis, batch.neural_opacity
         else:
             vi, op_all = torch.cat([r.visible_index for r in renders]), torch.cat([r.neural_opacity for r in renders])
-        if batch is not None and getattr(batch, "viewspace", None) is not None and len(renders) > 1:
+        if batch is not None and batch.viewspace is not None and len(renders) > 1:
             # rasterize_many: one leaf, one radii tensor for all renders
             seen, g = batch.seen, batch.viewspace.grad
         else:

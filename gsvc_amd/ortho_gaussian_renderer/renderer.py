@@ -15,6 +15,17 @@ from ..rasterizer import GaussianRasterizer, raster_forward, rasterize_many, set
 from .preprocess import prefilter_geometry, prefilter_voxel, prefilter_voxels_many, raster_settings_for
 
 
+def _results(gss, entropy=True, **per_call):
+    """RenderResults with everything that comes from the generated Gaussians filled in; ``per_call``: the fields of the call.
+    ``entropy=False`` leaves the rate fields and ``entropy_constrained`` at their defaults (render_pair: inference only)."""
+    if entropy:
+        per_call.update(bit_per_param=gss.bit_per_param, bit_per_feat_param=gss.bit_per_feat_param,
+                        bit_per_scaling_param=gss.bit_per_scaling_param, bit_per_offsets_param=gss.bit_per_offsets_param,
+                        entropy_constrained=(gss.bit_per_param is not None))
+    return RenderResults(selection_mask=gss.mask, neural_opacity=gss.neural_opacity, scaling=gss.scaling, generated_gaussians=gss,
+                         time_sub=gss.time_sub, **per_call)
+
+
 def render(frame, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, retain_grad=False,
            mode=GenerateMode.TRAINING_FULL_PRECISION, return_depth=False, return_alpha=False):
     """``return_depth`` / ``return_alpha``: also fill RenderResults.rendered_depth / rendered_alpha ([1, H, W], differentiable) with
@@ -34,13 +45,9 @@ def render(frame, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, retain
         means3D=gss.xyz, means2D=screenspace_points, shs=None, colors_precomp=gss.color, opacities=gss.opacity,
         scales=gss.scaling, rotations=gss.rot, cov3D_precomp=None, return_depth=return_depth, return_alpha=return_alpha)
     rendered_depth, rendered_alpha = maps or (None, None)
-    return RenderResults(
-        rendered_image=rendered_image, rendered_depth=rendered_depth, rendered_alpha=rendered_alpha, viewspace_points=screenspace_points, visibility_filter=radii > 0,
-        visible_mask=visible_mask, radii=radii, active_gaussains=(radii > 0).sum(), num_rendered=num_rendered,
-        selection_mask=gss.mask, neural_opacity=gss.neural_opacity, scaling=gss.scaling,
-        bit_per_param=gss.bit_per_param, bit_per_feat_param=gss.bit_per_feat_param,
-        bit_per_scaling_param=gss.bit_per_scaling_param, bit_per_offsets_param=gss.bit_per_offsets_param,
-        entropy_constrained=(gss.bit_per_param is not None), generated_gaussians=gss, time_sub=gss.time_sub)
+    return _results(
+        gss, rendered_image=rendered_image, rendered_depth=rendered_depth, rendered_alpha=rendered_alpha, viewspace_points=screenspace_points,
+        visibility_filter=radii > 0, visible_mask=visible_mask, radii=radii, active_gaussains=(radii > 0).sum(), num_rendered=num_rendered)
 
 
 def plan_views(frames, pc, pipe, bg_color: torch.Tensor, mode=GenerateMode.TRAINING_FULL_PRECISION):
@@ -77,14 +84,14 @@ def render_many(frames, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, 
         gss_list = generate_neural_gaussians_many(frames, pc, visible, mode, dense=dense,
                                                   anchors=None if anchor_grad else geometry[0], plan=plan, defer_rate=dense)
     results = []
-    batch = getattr(gss_list[0], "batch", None) if (dense and gss_list) else None
-    if batch is not None and getattr(batch, "xyz", None) is not None and len(batch.seg_offsets) == len(frames) + 1:
+    batch = gss_list[0].batch if (dense and gss_list) else None
+    if batch is not None and len(batch.seg_offsets) == len(frames) + 1:
         # the R renders are row ranges of one set of tensors: one autograd function rasterizes them all (no split of the inputs,
         # no concatenation of their gradients, one means2D leaf, one radii tensor)
         bounds = batch.seg_offsets
         leaf = torch.empty(bounds[-1], 3, dtype=pc._anchor.dtype, device=batch.xyz.device, requires_grad=True)   # value never read
         cs_list = [settings_to_c(raster_settings_for(f, pc, pipe, bg_color, scaling_modifier)) for f in frames]
-        if batch.xyz.is_cuda and getattr(batch, "small_work", False):
+        if batch.xyz.is_cuda and batch.small_work:
             # everything the generation pass produced is queued by now: work that reads only that (the sampled rate, the loss's
             # regularisers) may start behind this event on another stream while the rasterizer runs
             batch.generated_event = torch.cuda.current_stream(batch.xyz.device).record_event()
@@ -96,14 +103,10 @@ def render_many(frames, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, 
         batch.viewspace, batch.seen = leaf, seen_all
         for r, (frame, visible_mask, gss) in enumerate(zip(frames, visible, gss_list)):
             a, b = bounds[r], bounds[r + 1]
-            results.append(RenderResults(
-                rendered_image=images[r], viewspace_points=_GradRows(leaf, a, b), visibility_filter=seen_all[a:b],
+            results.append(_results(
+                gss, rendered_image=images[r], viewspace_points=_GradRows(leaf, a, b), visibility_filter=seen_all[a:b],
                 visible_mask=visible_mask, radii=radii_all[a:b], active_gaussains=states[r].binning[8:12].view(torch.int32)[0],
-                num_rendered=None, selection_mask=gss.mask, neural_opacity=gss.neural_opacity, scaling=gss.scaling,
-                bit_per_param=gss.bit_per_param, bit_per_feat_param=gss.bit_per_feat_param,
-                bit_per_scaling_param=gss.bit_per_scaling_param, bit_per_offsets_param=gss.bit_per_offsets_param,
-                entropy_constrained=(gss.bit_per_param is not None), generated_gaussians=gss, time_sub=gss.time_sub,
-                dense=dense, visible_index=gss.visible_index, raster_state=states[r]))
+                num_rendered=None, dense=dense, visible_index=gss.visible_index, raster_state=states[r]))
         return results
     finish_deferred_rate(gss_list)
     for frame, visible_mask, gss in zip(frames, visible, gss_list):
@@ -119,14 +122,10 @@ def render_many(frames, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, 
         seen = radii > 0
         # un-compacted renders: the rasterizer already counted the Gaussians with radius > 0 (gsvc_raster_counters.num_visible)
         active = num_rendered.binning[8:12].view(torch.int32)[0] if dense else seen.sum()
-        results.append(RenderResults(
-            rendered_image=rendered_image, viewspace_points=screenspace_points, visibility_filter=seen,
+        results.append(_results(
+            gss, rendered_image=rendered_image, viewspace_points=screenspace_points, visibility_filter=seen,
             visible_mask=visible_mask, radii=radii, active_gaussains=active,
             num_rendered=None if dense else num_rendered,
-            selection_mask=gss.mask, neural_opacity=gss.neural_opacity, scaling=gss.scaling,
-            bit_per_param=gss.bit_per_param, bit_per_feat_param=gss.bit_per_feat_param,
-            bit_per_scaling_param=gss.bit_per_scaling_param, bit_per_offsets_param=gss.bit_per_offsets_param,
-            entropy_constrained=(gss.bit_per_param is not None), generated_gaussians=gss, time_sub=gss.time_sub,
             dense=dense, visible_index=gss.visible_index, raster_state=num_rendered if dense else None))
     return results
 
@@ -170,10 +169,9 @@ def render_pair(frame, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, m
                 gss.visable_mask = visible_mask
                 image, radii, state = raster_forward(cs, gss.xyz.contiguous(), gss.color.contiguous(), gss.opacity.contiguous(),
                                                      gss.scaling.contiguous(), gss.rot.contiguous(), pair=True)
-                return RenderResults(
-                    rendered_image=image, viewspace_points=None, visibility_filter=radii > 0, visible_mask=visible_mask, radii=radii,
-                    active_gaussains=(radii > 0).sum(), num_rendered=state.counters()[0], selection_mask=gss.mask,
-                    neural_opacity=gss.neural_opacity, scaling=gss.scaling, generated_gaussians=gss, time_sub=gss.time_sub)
+                return _results(
+                    gss, entropy=False, rendered_image=image, viewspace_points=None, visibility_filter=radii > 0, visible_mask=visible_mask,
+                    radii=radii, active_gaussains=(radii > 0).sum(), num_rendered=state.counters()[0])
         visible_mask = prefilter_voxel(frame, pc, pipe, bg_color)
         gss = generate_neural_gaussians(frame, pc, visible_mask, mode)
         args = (gss.xyz.contiguous(), gss.color.contiguous(), gss.opacity.contiguous(), gss.scaling.contiguous(), gss.rot.contiguous())
@@ -186,10 +184,9 @@ def render_pair(frame, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, m
             f, radii, state = raster_forward(cs, *args)
             b, _, _ = raster_forward(settings_to_c(raster_settings_for(back, pc, pipe, bg_color, scaling_modifier)), *args)
             image = 0.5 * (f + torch.flip(b, dims=(-1,)))
-    return RenderResults(
-        rendered_image=image, viewspace_points=None, visibility_filter=radii > 0, visible_mask=visible_mask, radii=radii,
-        active_gaussains=(radii > 0).sum(), num_rendered=state.counters()[0], selection_mask=gss.mask,
-        neural_opacity=gss.neural_opacity, scaling=gss.scaling, generated_gaussians=gss, time_sub=gss.time_sub)
+    return _results(
+        gss, entropy=False, rendered_image=image, viewspace_points=None, visibility_filter=radii > 0, visible_mask=visible_mask,
+        radii=radii, active_gaussains=(radii > 0).sum(), num_rendered=state.counters()[0])
 
 
 def render_frames(frames, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, mode=GenerateMode.DECODING_AS_IS, batch: int = 8):

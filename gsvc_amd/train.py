@@ -60,7 +60,7 @@ def _release_graph(renders):
         g = r.generated_gaussians
         if g is not None:
             strip(g)
-            strip(getattr(g, "batch", None))
+            strip(g.batch)
 
 
 def hash_grid_bits(pc):
@@ -463,12 +463,12 @@ class Trainer:
         # the loss is a weighted sum of scalar terms: they are collected and combined with one stack + dot (instead of
         # one tiny kernel per +, *, and their backward nodes)
         weights, const = yuv_loss.distortion_weights(self.loss_domain, opt.lambda_dssim)
-        batch = getattr(r1f.generated_gaussians, "batch", None) if self.batched else None
+        batch = r1f.generated_gaussians.batch if self.batched else None
         # the terms below read the generation pass's tensors and parameters, not the images: a dozen small launches each way, issued
         # on the small-work stream behind the generation pass's event so that they run under the compositing kernels (their backward
         # too: autograd runs a node on its forward's stream) instead of behind the image losses
         side = None
-        if getattr(batch, "generated_event", None) is not None:      # (recorded only when the batch's small_work is set)
+        if batch is not None and batch.generated_event is not None:      # (recorded only when the batch's small_work is set)
             side = schedule.small_work_stream(dev)
             side.wait_event(batch.generated_event)
         n_image_terms = len(terms)
@@ -491,7 +491,7 @@ class Trainer:
                 # sparse data-parallel exchange (below): the regulariser's dense gradient is added after the exchange (_add_mask_reg)
                 sparse_dp = self._sparse_dp(plan if self.batched else None) or zown is not None
                 self._mask_reg_weight = 5e-4 if sparse_dp else 0.0
-                rate_sum = getattr(batch, "bit_per_param_sum", None)
+                rate_sum = batch.bit_per_param_sum if batch is not None else None
                 # the renders' rates enter with one weight: their sum, when the batched generation already formed it, is one term
                 terms += ([rate_sum] if rate_sum is not None else [r.bit_per_param for r in renders]) + \
                          [hash_grid_bits(pc), (zown.mask_sigmoid_mean if (zown is not None and zown.mask_sigmoid_mean is not None) else
@@ -499,7 +499,7 @@ class Trainer:
                 weights += [opt.lmbda] * (1 if rate_sum is not None else 4) + [opt.lmbda / denom, 5e-4]
         if side is not None:
             # what the terms above read of the step's stream's allocations (and saved for their backward on the small-work stream)
-            schedule.record_on(side, batch.scaling, batch.neural_opacity, batch.mask, getattr(batch, "world", None), getattr(batch, "vis", None),
+            schedule.record_on(side, batch.scaling, batch.neural_opacity, batch.mask, batch.world, batch.vis,
                                [g.step_cache for g in grid_tables(pc)], flow if opt.optical_lambda != 0 else None)
             main_stream = torch.cuda.current_stream(dev)
             main_stream.wait_stream(side)
@@ -556,7 +556,7 @@ class Trainer:
             # a GPU-bound step (the one that uses the small-work stream) also sends the chain networks' weight gradients to their own
             # stream, and waits for both streams behind the backward; a host-bound one would only pay for the events and the allocator's
             # stream records (configs[3]: +0.2 ms of host time)
-            with region('step.backward'), (schedule.backward_streams(dev, self._chain_params) if getattr(batch, "small_work", False)
+            with region('step.backward'), (schedule.backward_streams(dev, self._chain_params) if batch is not None and batch.small_work
                                            else contextlib.nullcontext()):
                 loss.backward()
         finally:

@@ -177,6 +177,20 @@ def test_generate_neural_gaussians_cpu_modes(tiny, mode_value, seeded):
     assert gss.bit_per_param is None
 
 
+@pytest.mark.parametrize("mode_value", [0, 4])
+def test_batched_generation_of_one_render_equals_the_single_render(tiny, mode_value):
+    """The compacting tail is shared: the batched pass on one render (dense=False) and generate_neural_gaussians give the
+    same bits in the modes that draw nothing (TRAINING_FULL_PRECISION, DECODING_AS_IS)."""
+    from gsvc_amd.generate import GenerateMode, generate_neural_gaussians, generate_neural_gaussians_many
+    pc, g = tiny
+    frame = SimpleNamespace(cam_pos=torch.tensor([0.0, 0.0, float(g["z_cam"])]))
+    vis = T(g["visible_mask"])
+    many = generate_neural_gaussians_many([frame], pc, [vis], GenerateMode(mode_value), dense=False)[0]
+    one = generate_neural_gaussians(frame, pc, vis, GenerateMode(mode_value))
+    for nm in ("xyz", "color", "opacity", "scaling", "rot", "neural_opacity", "mask", "concatenated_all"):
+        assert torch.equal(getattr(many, nm), getattr(one, nm)), nm
+
+
 def test_generate_gradients_match_reference(tiny):
     from gsvc_amd.generate import GenerateMode, generate_neural_gaussians
     pc, g = tiny

@@ -1,7 +1,10 @@
 """Is one fitting step a deterministic function of (model, frame pair, seed)?  The same step — optimizer replaced by a gradient capture, the
 random generator re-seeded — is run several times in one process and every parameter's gradient compared bit for bit, per phase and
 under the step's structural switches (one raster stream, no small-work stream, no early plan, layer-by-layer MLPs ...), to find which
-piece, if any, makes two identical runs differ.  Usage: python tools/ab/determinism_check.py [anchors] [repeats]"""
+piece, if any, makes two identical runs differ.  Usage: python tools/ab/determinism_check.py [anchors] [repeats]
+DET_HASHES=file.json: also write the SHA-256 of every captured gradient, per phase and variant (to compare two builds or trees)."""
+import hashlib
+import json
 import os
 import sys
 
@@ -34,9 +37,16 @@ pc.update_anchor_bound(cube.x_min, cube.y_min, cube.z_min)
  opt.ste_entropy_constrained_train_total) = B, 0, 0, 0
 pc.training_setup(opt)
 tr = Trainer(pc, cube, opt, pipe, mp_, seed=0)
+warm_det = bool(os.environ.get("DET_HASHES")) and not os.environ.get("GSVC_DETERMINISTIC")
+if warm_det:          # hashes are compared across processes: the model they are taken on must be the same one too
+    os.environ["GSVC_DETERMINISTIC"] = "1"
+    switches.reload()
 for it in range(1, 41):          # a model with non-degenerate opacities / scales
     tr.step(it)
 torch.cuda.synchronize()
+if warm_det:
+    os.environ.pop("GSVC_DETERMINISTIC", None)
+    switches.reload()
 real_step = pc.optimizer.step
 captured = {}
 
@@ -58,6 +68,7 @@ VARIANTS = [("default", {}), ("GSVC_DETERMINISTIC=1", {"GSVC_DETERMINISTIC": "1"
             ("one stream, no overlap, no prefetch", {"GSVC_RASTER_STREAMS": "1", "GSVC_NO_RATE_OVERLAP": "1", "GSVC_NO_PREFETCH": "1"}),
             ("layer-by-layer MLPs", {"GSVC_NO_MLP_CHAIN": "1"}), ("no multi-product launches", {"GSVC_NO_SHARED_INPUT": "1", "GSVC_NO_ACCUM_MANY": "1"})]
 only = os.environ.get("DET_PHASES")
+hashes = {}
 if os.environ.get("DET_VARIANTS"):          # e.g. DET_VARIANTS=default,GSVC_DETERMINISTIC=1
     VARIANTS = [v for v in VARIANTS if any(v[0].startswith(w) for w in os.environ["DET_VARIANTS"].split(","))]
 for phase, totals in PHASES.items():
@@ -94,6 +105,7 @@ for phase, totals in PHASES.items():
                 if d != 0.0:
                     n = max(int((r[k] != runs[0][k]).sum()) for r in runs[1:])
                     bad[k] = (d / max(float(runs[0][k].abs().max()), 1e-30), n, runs[0][k].numel())
+            hashes[f"{phase} / {tag}"] = {k: hashlib.sha256(v.cpu().numpy().tobytes()).hexdigest() for k, v in sorted(runs[0].items())}
             worst = sorted(bad.items(), key=lambda kv: -kv[1][0])[:6]
             print(f"{phase:8s} {tag:40s} tensors {len(runs[0])} differing {len(bad)}" +
                   ("  worst: " + "; ".join(f"{k} {v[0]:.1e} of scale in {v[1]}/{v[2]}" for k, v in worst) if bad else "  bit-identical"), flush=True)
@@ -104,6 +116,9 @@ for phase, totals in PHASES.items():
                 else:
                     os.environ[k] = v
             switches.reload()
+if os.environ.get("DET_HASHES"):
+    with open(os.environ["DET_HASHES"], "w") as f:
+        json.dump({"anchors": A, "gradients": hashes}, f, indent=1, sort_keys=True)
 
 # what the fixed order costs: the entropy-constrained step, default against GSVC_DETERMINISTIC=1, same process
 import time
