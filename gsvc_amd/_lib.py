@@ -274,6 +274,9 @@ _SIGNATURES = {
     "gsvc_frames_sse": (C.c_int, [_vp, _i64, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "gsvc_msssim_workspace_bytes": (_i64, [C.c_int32, C.c_int32, C.c_int32]),
     "gsvc_msssim": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _vp, _vp, _vp]),
+    "gsvc_msssim_loss_workspace_bytes": (_i64, [C.c_int32, C.c_int32, C.c_int32]),
+    "gsvc_msssim_loss_forward": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
+    "gsvc_msssim_loss_backward": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp]),
     "gsvc_picture_hash": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "gsvc_frames_histogram": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     # content-adaptive initial anchors (csrc/detail.hip): replace the uniform draw of the reference's init_point_cloud

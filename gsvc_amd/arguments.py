@@ -105,6 +105,7 @@ class OptimizationParams:
     percent_dense: float = 0.01
     lambda_dssim: float = 0.2
     loss_domain: str = "rgb"      # where the distortion is taken: "rgb", or on Y'CbCr planes "yuv420" / "yuv444" (gsvc_amd/yuv_loss.py)
+    distortion: str = "ssim"      # the structural term of the distortion: "ssim" (single scale), or "ms_ssim" (five scales; rgb domain, sides > 160)
     start_stat: int = 500
     update_from: int = 1500
     update_interval: int = 100

@@ -66,16 +66,18 @@ def new_fit(cube, mp_, opt, pipe, anchors: int, device, init: str = "uniform", i
 
 def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float = 0.004, anchors: int = 100_000, slab_frames: float = 16.0,
                densify_grad_threshold=None, estimate_flow: bool = False, flow_dir=None, video_size=(None, None), video_format=None,
-               hash_format=None, loss_domain: str = "rgb", init: str = "uniform", init_cell: int = 8, init_mix: float = 0.25):
+               hash_format=None, loss_domain: str = "rgb", init: str = "uniform", init_cell: int = 8, init_mix: float = 0.25,
+               distortion: str = "ssim"):
     """One group of pictures of a video file -> ``(the bytes of a complete GSVC file, log)``: what tools/gsvc_encode.py does with a whole
     clip, for the frames ``frame_range = (first, stop)`` of it (None: all).  VideoFileCube (optionally with the flow estimated from the
     frames) -> the fit -> ``conduct_stream_encoding`` with 8-bit MLPs -> the file image; that image is then decoded into a null sink by
     the function, batch size and format the decoder will use (``decode_video``), which yields the picture hashes it is given as its PHSH
     section.  The trainer, the cube and the model are released before this returns.  ``loss_domain``: where the fit takes its
-    distortion (``OptimizationParams.loss_domain``; the bitstream and the decoder are the same for every domain).  ``init``,
+    distortion (``OptimizationParams.loss_domain``; the bitstream and the decoder are the same for every domain); ``distortion``: its
+    structural term, "ssim" or "ms_ssim" (``OptimizationParams.distortion``).  ``init``,
     ``init_cell``, ``init_mix``: where the fit's first anchors come from (``new_fit``; anchors are coded wherever they are).  ``log``:
     {"W", "H", "frames", "steps", "init", ("init_cell", "init_mix": with init="detail" only), "anchors_initial": the anchors after the
-    voxel merge of ``create_from_points``, "loss_domain", "loss_matrix", "anchors_coded", "fit_seconds", "hash_format",
+    voxel merge of ``create_from_points``, "loss_domain", "loss_matrix", "distortion", "anchors_coded", "fit_seconds", "hash_format",
     "verify_decode_fps", "sections"}."""
     import gc
     import os
@@ -99,12 +101,14 @@ def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float 
         opt.optical_lambda = 0.0
     configure_fit(mp_, opt, cube, steps, lmbda, slab_frames, densify_grad_threshold)
     opt.loss_domain = loss_domain
+    opt.distortion = distortion
     pc, trainer = new_fit(cube, mp_, opt, pipe, anchors, device, init=init, init_cell=init_cell, init_mix=init_mix)
     log["init"] = init
     if init == "detail":
         log["init_cell"], log["init_mix"] = int(init_cell), float(init_mix)
     log["anchors_initial"] = int(pc._anchor.shape[0])
     log["loss_domain"], log["loss_matrix"] = trainer.loss_domain, trainer.loss_matrix
+    log["distortion"] = trainer.distortion
     bg = trainer.background
     torch.cuda.synchronize()
     t0 = time.perf_counter()

@@ -97,6 +97,77 @@ def ssim_l1(img1, img2):
     return _SsimL1.apply(img1, img2)
 
 
+class _MsSsimL1(torch.autograd.Function):
+    """(MS-SSIM, mean |x - gt|[, x]) of [C,H,W] CUDA images through csrc/msssim_loss.hip; ``img_b`` not None is the pair form
+    x = (img + flip_W(img_b)) / 2, formed inside the kernels, and x is the third result (non-differentiable)."""
+
+    @staticmethod
+    def forward(ctx, img, img_b, gt):
+        from . import _lib
+        pair = img_b is not None
+        a, g = img.contiguous().float(), gt.contiguous().float()
+        b = img_b.contiguous().float() if pair else None
+        C_, H, W = a.shape
+        L = _lib.lib()
+        nbytes = int(L.gsvc_msssim_loss_workspace_bytes(C_, H, W))
+        if nbytes < 0:
+            raise ValueError(f"ms_ssim_l1: image sides must exceed 160 pixels for 5 scales (got {C_} planes of {H} x {W})")
+        need = img.requires_grad or (pair and img_b.requires_grad)
+        work = torch.empty(nbytes, device=a.device, dtype=torch.uint8)
+        out = torch.empty(2, device=a.device, dtype=torch.float32)
+        avg = torch.empty_like(a) if pair else None
+        _lib.check(L.gsvc_msssim_loss_forward(_lib.ptr(a), _lib.ptr(b), _lib.ptr(g), C_, H, W, int(need), _lib.ptr(work), _lib.ptr(out),
+                                              _lib.ptr(avg), _lib.current_stream(a.device)), "gsvc_msssim_loss_forward")
+        if need:
+            ctx.save_for_backward(a, g, work, *((b,) if pair else ()))
+        ctx.pair = pair
+        ctx.set_materialize_grads(False)
+        if pair:
+            ctx.mark_non_differentiable(avg)
+            return out[0], out[1], avg
+        return out[0], out[1]
+
+    @staticmethod
+    def backward(ctx, g_ms, g_l1, _g_avg=None):
+        from . import _lib
+        a, g, work = ctx.saved_tensors[:3]
+        b = ctx.saved_tensors[3] if ctx.pair else None
+        C_, H, W = a.shape
+        zero = torch.zeros((), device=a.device) if (g_ms is None or g_l1 is None) else None
+        grads = torch.stack([zero if g_ms is None else g_ms, zero if g_l1 is None else g_l1]).float().contiguous()
+        d = torch.empty_like(a)
+        db = torch.empty_like(b) if ctx.pair else None
+        _lib.check(_lib.lib().gsvc_msssim_loss_backward(_lib.ptr(a), _lib.ptr(b), _lib.ptr(g), C_, H, W, _lib.ptr(work), _lib.ptr(grads),
+                                                        _lib.ptr(d), _lib.ptr(db), _lib.current_stream(a.device)),
+                   "gsvc_msssim_loss_backward")
+        return d, db, None
+
+
+def _check_ms_images(name, *imgs):
+    if any(t.dim() != 3 or t.shape != imgs[0].shape for t in imgs):
+        raise ValueError(f"{name}: images must be [C, H, W] tensors of one shape")
+
+
+def ms_ssim_l1(img1, img2):
+    """(metrics.ms_ssim(img1, img2, data_range=1), l1_loss_func(img1, img2)) of [C,H,W] images, both sides > 160; the gradient goes
+    to img1.  CUDA tensors take the fused kernels of csrc/msssim_loss.hip (eleven launches forward, five backward); CPU tensors the
+    tensor expressions, differentiable through autograd."""
+    _check_ms_images("ms_ssim_l1", img1, img2)
+    if not img1.is_cuda:
+        from .metrics import ms_ssim
+        return ms_ssim(img1, img2, data_range=1), l1_loss_func(img1, img2)
+    return _MsSsimL1.apply(img1, None, img2)
+
+
+def ms_ssim_l1_pair(img_f, img_b, img2):
+    """(ms_ssim, l1, a.detach()) of ms_ssim_l1(a, img2) for the two-view frame a = (img_f + flip(img_b, W)) / 2."""
+    _check_ms_images("ms_ssim_l1_pair", img_f, img_b, img2)
+    if not img_f.is_cuda:
+        a = (img_f + torch.flip(img_b, dims=[2])) / 2
+        return ms_ssim_l1(a, img2) + (a.detach(),)
+    return _MsSsimL1.apply(img_f, img_b, img2)
+
+
 def l1_loss_func(network_output, gt):
     return (network_output - gt).abs().mean()
 

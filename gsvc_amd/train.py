@@ -20,7 +20,7 @@ import torch
 from . import dist as gdist
 from . import schedule, switches, yuv_loss
 from .generate import GenerateMode, region
-from .loss_utils import calc_optical_loss, render_regs, ssim_l1, ssim_l1_pair
+from .loss_utils import calc_optical_loss, ms_ssim_l1, ms_ssim_l1_pair, render_regs, ssim_l1, ssim_l1_pair
 from .optim import FusedAdam
 from .ortho_gaussian_renderer import plan_views, render, render_many
 from .rasterizer import resolve_deferred
@@ -125,6 +125,9 @@ def _mean_over_selected(values, r):
     return (values * w).sum() / w.sum()
 
 
+DISTORTIONS = ("ssim", "ms_ssim")      # OptimizationParams.distortion
+
+
 class Trainer:
     def __init__(self, gaussians, dataset, opt, pipe, model_params, seed: int = 0, batched: bool = True, prefetch: bool = True,
                  shard_optimizer=None):
@@ -146,6 +149,16 @@ class Trainer:
             self._loss_fmt = FrameFormat(layout, yuv_loss.loss_matrix(dataset))
             self.loss_matrix = self._loss_fmt.matrix
             self._native_planes = yuv_loss.native_planes(dataset, layout)      # the targets come from the file's codes: no picture is read
+        # the structural term: single-scale SSIM, or MS-SSIM as metrics.ms_ssim reports it (csrc/msssim_loss.hip)
+        self.distortion = getattr(opt, "distortion", "ssim")
+        if self.distortion not in DISTORTIONS:
+            raise ValueError(f"unknown distortion {self.distortion!r} (one of {', '.join(DISTORTIONS)})")
+        if self.distortion == "ms_ssim":
+            if self.loss_domain != "rgb":
+                raise ValueError(f"distortion 'ms_ssim' is taken on RGB pictures: loss_domain must be 'rgb' (got {self.loss_domain!r})")
+            if min(int(dataset.height), int(dataset.width)) <= 160:
+                raise ValueError(f"distortion 'ms_ssim' needs picture sides above 160 pixels for 5 scales "
+                                 f"(got {int(dataset.height)} x {int(dataset.width)})")
         # prefetch: the next step's frame pair is drawn, its visibility test run and every data-dependent index list of its
         # generation pass queued at the END of a step (gsvc_amd.generate.StepPlan): the next step then starts with one wait
         # for nine counts instead of six device round trips with an idle GPU
@@ -453,12 +466,14 @@ class Trainer:
                 image1, image2 = y1[4], y2[4]
             terms = [y1[1], y2[1], y1[3], y2[3], y1[0], y2[0], y1[2], y2[2]]
         elif image1 is None:
-            ssim1, l1_1, image1 = ssim_l1_pair(r1f.rendered_image, r1b.rendered_image, gt1)
-            ssim2, l1_2, image2 = ssim_l1_pair(r2f.rendered_image, r2b.rendered_image, gt2)
+            pair_loss = ms_ssim_l1_pair if self.distortion == "ms_ssim" else ssim_l1_pair
+            ssim1, l1_1, image1 = pair_loss(r1f.rendered_image, r1b.rendered_image, gt1)
+            ssim2, l1_2, image2 = pair_loss(r2f.rendered_image, r2b.rendered_image, gt2)
             terms = [l1_1, l1_2, ssim1, ssim2]
         else:
-            ssim1, l1_1 = ssim_l1(image1, gt1)
-            ssim2, l1_2 = ssim_l1(image2, gt2)
+            image_loss = ms_ssim_l1 if self.distortion == "ms_ssim" else ssim_l1
+            ssim1, l1_1 = image_loss(image1, gt1)
+            ssim2, l1_2 = image_loss(image2, gt2)
             terms = [l1_1, l1_2, ssim1, ssim2]
         # the loss is a weighted sum of scalar terms: they are collected and combined with one stack + dot (instead of
         # one tiny kernel per +, *, and their backward nodes)

@@ -1065,6 +1065,32 @@ int gsvc_msssim(const void *x, int64_t x_row_pitch, int64_t x_plane_pitch, const
                 int32_t P, int32_t H, int32_t W, int32_t sample_type, float peak, void *workspace, double *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * [INTERNAL] MS-SSIM + L1 as a fitting loss (csrc/msssim_loss.hip).
+ *
+ * Over P planes of H x W float32 samples (contiguous, [P, H, W]): x the fitted picture, gt the ground truth.
+ *   out[0]      the mean over the planes of prod_k max(t[k], 0)^w[k], t[k] the per-scale means of gsvc_msssim (same window, same
+ *               pooling, same weights; float64, tile sums added in a fixed order), rounded to float32 once
+ *   out[1]      the mean of |x - gt| over all P H W samples
+ * img_b != NULL is the pair form: x = (img + flip_W(img_b)) / 2, formed on load; avg_out (may be NULL; pair form only) receives x.
+ * keep_maps != 0 stores what gsvc_msssim_loss_backward reads (three maps over the valid outputs of every scale); with 0 the call is
+ * a measurement and the workspace must not be handed to the backward.
+ *
+ * gsvc_msssim_loss_backward: d_img = grads[0] d out[0] / d x + grads[1] d out[1] / d x (grads: two floats on the device), from the
+ * workspace a forward with keep_maps != 0 left and the same images.  Pair form: d_img = half of that, d_img_b = flip_W(d_img); img_b
+ * and d_img_b go together.  gt gets no gradient.  A plane with any t[k] <= 0 has value 0 and an MS-SSIM gradient of exactly 0.  Every
+ * pixel has one owner and every sum a fixed order: two runs give the same bits.
+ *
+ * workspace: gsvc_msssim_loss_workspace_bytes(P, H, W) bytes (< 0 for a shape the calls refuse), 16-byte aligned, the caller's, and
+ * untouched between a forward and its backward.  Refused with an error before any GPU call: a NULL pointer, a side of 160 or less or
+ * above 32768, P outside 1 .. 65535, an image not 4-byte aligned, a workspace not 16-byte aligned.  Nothing synchronises.
+ * ---------------------------------------------------------------------------------------------------- */
+int64_t gsvc_msssim_loss_workspace_bytes(int32_t P, int32_t H, int32_t W);
+int gsvc_msssim_loss_forward(const float *img, const float *img_b, const float *gt, int32_t P, int32_t H, int32_t W, int32_t keep_maps,
+                             void *workspace, float *out, float *avg_out, void *stream);
+int gsvc_msssim_loss_backward(const float *img, const float *img_b, const float *gt, int32_t P, int32_t H, int32_t W, void *workspace,
+                              const float *grads, float *d_img, float *d_img_b, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * [INTERNAL] Picture hash on the codes (csrc/picture_hash.hip): what the PHSH section of a bitstream file holds.
  *
  * gsvc_picture_hash: out[k, p] (uint64 [n, 3], 8-byte aligned) = the hash of plane p of frame k of a buffer of delivered frames (frame

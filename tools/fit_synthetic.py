@@ -90,6 +90,8 @@ def main(argv=None):
     ap.add_argument("--optical-lambda", type=float, default=None, help="weight of the flow-guided loss (default: the configuration's)")
     ap.add_argument("--video-resident", choices=("float", "u8"), default="float",
                     help="keep the video on the device as float32 pictures, or as the file's bytes (converted one frame per fetch)")
+    ap.add_argument("--distortion", choices=("ssim", "ms_ssim"), default="ssim",
+                    help="the structural term of the distortion: single-scale SSIM, or MS-SSIM (rgb domain, sides above 160 pixels)")
     ap.add_argument("--loss-domain", choices=("rgb", "yuv420", "yuv444"), default="rgb",
                     help="where the fit takes its distortion: float RGB, or Y'CbCr planes (gsvc_amd/yuv_loss.py): those of a Y'CbCr --video "
                          "file's sample codes, else the transform of the RGB pictures")
@@ -151,6 +153,7 @@ def main(argv=None):
     from gsvc_amd.fit_setup import configure_fit, new_fit
     configure_fit(mp_, opt, cube, N, args.lmbda, args.slab_frames, args.densify_grad_threshold)
     opt.loss_domain = args.loss_domain
+    opt.distortion = args.distortion
     init = {"init": args.init}
     if args.init == "detail":
         init.update(init_cell=8 if args.init_cell is None else args.init_cell, init_mix=0.25 if args.init_mix is None else args.init_mix)
@@ -158,7 +161,7 @@ def main(argv=None):
     bg = trainer.background
     log = {"config": {"H": H, "W": W, "frames": T, "steps": N, "anchors_init": args.anchors, **init,
                       "anchors_initial": int(pc._anchor.shape[0]), "lmbda": args.lmbda,
-                      "loss_domain": trainer.loss_domain, "loss_matrix": trainer.loss_matrix,
+                      "loss_domain": trainer.loss_domain, "loss_matrix": trainer.loss_matrix, "distortion": trainer.distortion,
                       "slab_frames": args.slab_frames, "schedule": [opt.full_precision_training_total, opt.quantized_training_total,
                                                                     opt.entropy_constrained_train_total, opt.ste_entropy_constrained_train_total],
                       "densify": [opt.start_stat, opt.update_from, opt.update_interval, opt.update_until, opt.pause_densification]},

@@ -4,7 +4,7 @@ the video in another process, with nothing else:
 
     python tools/gsvc_encode.py clip.y4m -o clip.gsvc [--steps 2000 --lmbda 0.004 --anchors 100000 --estimate-flow]
                                 [--video-format yuv420p,bt601,full] [--video-size WxH] [--hash-format yuv420p]
-                                [--loss-domain rgb|yuv420|yuv444] [--init detail [--init-cell 8 --init-mix 0.25]]
+                                [--loss-domain rgb|yuv420|yuv444] [--distortion ssim|ms_ssim] [--init detail [--init-cell 8 --init-mix 0.25]]
     python tools/gsvc_decode.py clip.gsvc -o out.y4m --strict
     python tools/gsvc_encode.py long.y4m -o long.gsvs --gop-frames 32 [--scene-cuts --cut-threshold 0.5 --min-gop 4]
 
@@ -52,6 +52,9 @@ def main(argv=None):
                     help="the frame format whose picture hashes the file carries: what the decoder verifies when it decodes to it")
     ap.add_argument("--loss-domain", choices=("rgb", "yuv420", "yuv444"), default="rgb",
                     help="where the fit takes its distortion: float RGB, or the Y'CbCr planes of the file (gsvc_amd/yuv_loss.py)")
+    ap.add_argument("--distortion", choices=("ssim", "ms_ssim"), default="ssim",
+                    help="the structural term of the fit's distortion: single-scale SSIM, or MS-SSIM as the metrics report it (rgb "
+                         "domain, sides above 160 pixels)")
     ap.add_argument("--gop-frames", type=int, default=None, metavar="N",
                     help="cut the clip into groups of pictures of at most N frames and write a sequence file (GSVS)")
     ap.add_argument("--scene-cuts", action="store_true", help="with --gop-frames: also start a GOP where the luma histogram changes")
@@ -81,7 +84,7 @@ def main(argv=None):
     fit = dict(steps=args.steps, lmbda=args.lmbda, anchors=args.anchors, slab_frames=args.slab_frames,
                densify_grad_threshold=args.densify_grad_threshold, estimate_flow=args.estimate_flow, flow_dir=args.flow_dir,
                video_size=(vw, vh), video_format=video_fmt, hash_format=_frame_format(args.hash_format), loss_domain=args.loss_domain,
-               init=args.init, init_cell=8 if args.init_cell is None else args.init_cell,
+               distortion=args.distortion, init=args.init, init_cell=8 if args.init_cell is None else args.init_cell,
                init_mix=0.25 if args.init_mix is None else args.init_mix)
     if args.gop_frames is None:
         blob, log = encode_gop(args.video, dev, **fit)
@@ -115,7 +118,7 @@ def main(argv=None):
     fps = header.get("fps") or (30, 1)
     write_sequence(args.output, blobs, W, H, fps, flags)
     log = {"output": args.output, "W": W, "H": H, "frames": T, "steps": args.steps, "fit_seconds": fit_seconds,
-           "loss_domain": one["loss_domain"], "loss_matrix": one["loss_matrix"],
+           "loss_domain": one["loss_domain"], "loss_matrix": one["loss_matrix"], "distortion": one["distortion"],
            **{k: one[k] for k in ("init", "init_cell", "init_mix") if k in one},
            "hash_format": _frame_format(args.hash_format).name, "gop_frames": args.gop_frames, "min_gop": min_gop,
            "scene_cuts": cuts if args.scene_cuts else None, "cut_threshold": threshold if args.scene_cuts else None, "gops": gops}
