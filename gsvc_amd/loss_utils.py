@@ -13,88 +13,69 @@ from math import exp
 import torch
 import torch.nn.functional as F
 
+from . import yuv_loss
+
 
 class _SsimL1(torch.autograd.Function):
-    """(mean SSIM, mean |a-b|) of two [C,H,W] CUDA images through csrc/ssim.hip; gradient w.r.t. the first."""
+    """(mean SSIM, mean |x - gt|[, x]) of [C,H,W] CUDA images through csrc/ssim.hip; ``img_b`` not None is the pair form
+    x = (img + flip_W(img_b)) / 2 formed inside the kernels (the two-view frame of reference pipeline/train.py:368-375: no flip / add /
+    div launches forward, no div / flip backward), and x is the third result (non-differentiable)."""
 
     @staticmethod
-    def forward(ctx, img1, img2):
+    def forward(ctx, img, img_b, gt):
         from . import _lib
-        a, b = img1.contiguous().float(), img2.contiguous().float()
+        pair = img_b is not None
+        a, g = img.contiguous().float(), gt.contiguous().float()
+        b = img_b.contiguous().float() if pair else None
         C_, H, W = a.shape
-        need = img1.requires_grad
+        need = img.requires_grad or (pair and img_b.requires_grad)
         sums = torch.empty(2, device=a.device, dtype=torch.float32)
         work = torch.empty(2048, device=a.device, dtype=torch.float32)
+        avg = torch.empty_like(a) if pair else None
         maps = [torch.empty_like(a) for _ in range(3)] if need else [None, None, None]
-        _lib.check(_lib.lib().gsvc_ssim_l1_forward(_lib.ptr(a), _lib.ptr(b), C_, H, W, _lib.ptr(sums), _lib.ptr(work), _lib.ptr(maps[0]),
-                                                   _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.current_stream(a.device)),
-                   "gsvc_ssim_l1_forward")
+        L, st = _lib.lib(), _lib.current_stream(a.device)
+        if pair:
+            _lib.check(L.gsvc_ssim_l1_pair_forward(_lib.ptr(a), _lib.ptr(b), _lib.ptr(g), C_, H, W, _lib.ptr(sums), _lib.ptr(work),
+                                                   _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(avg), st),
+                       "gsvc_ssim_l1_pair_forward")
+        else:
+            _lib.check(L.gsvc_ssim_l1_forward(_lib.ptr(a), _lib.ptr(g), C_, H, W, _lib.ptr(sums), _lib.ptr(work), _lib.ptr(maps[0]),
+                                              _lib.ptr(maps[1]), _lib.ptr(maps[2]), st), "gsvc_ssim_l1_forward")
         if need:
-            ctx.save_for_backward(a, b, *maps)
+            ctx.save_for_backward(a, g, *maps, *((b,) if pair else ()))
+        ctx.pair = pair
+        ctx.set_materialize_grads(False)      # no zero image for the averaged frame's (absent) gradient
         out = sums / float(C_ * H * W)
+        if pair:
+            ctx.mark_non_differentiable(avg)
+            return out[0], out[1], avg
         return out[0], out[1]
 
     @staticmethod
-    def backward(ctx, g_ssim, g_l1):
+    def backward(ctx, g_ssim, g_l1, _g_avg=None):
         from . import _lib
-        a, b, m0, m1, m2 = ctx.saved_tensors
+        a, g, m0, m1, m2 = ctx.saved_tensors[:5]
+        b = ctx.saved_tensors[5] if ctx.pair else None
         C_, H, W = a.shape
-        grads = torch.stack([g_ssim, g_l1]).float().contiguous()
-        d = torch.empty_like(a)
-        _lib.check(_lib.lib().gsvc_ssim_l1_backward(_lib.ptr(a), _lib.ptr(b), C_, H, W, _lib.ptr(grads), _lib.ptr(m0),
-                                                    _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(d), _lib.current_stream(a.device)),
-                   "gsvc_ssim_l1_backward")
-        return d, None
-
-
-class _SsimL1Pair(torch.autograd.Function):
-    """(mean SSIM, mean |a-b|, a) with a = (img_f + flip_W(img_b)) / 2 formed inside the kernels (the two-view frame of
-    reference pipeline/train.py:368-375): no flip / add / div launches forward, no div / flip backward."""
-
-    @staticmethod
-    def forward(ctx, img_f, img_b, img2):
-        from . import _lib
-        f, b, g = img_f.contiguous().float(), img_b.contiguous().float(), img2.contiguous().float()
-        C_, H, W = f.shape
-        need = img_f.requires_grad or img_b.requires_grad
-        sums = torch.empty(2, device=f.device, dtype=torch.float32)
-        work = torch.empty(2048, device=f.device, dtype=torch.float32)
-        avg = torch.empty_like(f)
-        maps = [torch.empty_like(f) for _ in range(3)] if need else [None, None, None]
-        _lib.check(_lib.lib().gsvc_ssim_l1_pair_forward(_lib.ptr(f), _lib.ptr(b), _lib.ptr(g), C_, H, W, _lib.ptr(sums), _lib.ptr(work),
-                                                        _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(avg),
-                                                        _lib.current_stream(f.device)), "gsvc_ssim_l1_pair_forward")
-        if need:
-            ctx.save_for_backward(f, b, g, *maps)
-        ctx.mark_non_differentiable(avg)
-        ctx.set_materialize_grads(False)      # no zero image for the averaged frame's (absent) gradient
-        out = sums / float(C_ * H * W)
-        return out[0], out[1], avg
-
-    @staticmethod
-    def backward(ctx, g_ssim, g_l1, _g_avg):
-        from . import _lib
-        f, b, g, m0, m1, m2 = ctx.saved_tensors
-        C_, H, W = f.shape
-        zero = None
-        if g_ssim is None or g_l1 is None:
-            zero = torch.zeros((), device=f.device)
+        zero = torch.zeros((), device=a.device) if (g_ssim is None or g_l1 is None) else None
         grads = torch.stack([zero if g_ssim is None else g_ssim, zero if g_l1 is None else g_l1]).float().contiguous()
-        df, db = torch.empty_like(f), torch.empty_like(b)
-        _lib.check(_lib.lib().gsvc_ssim_l1_pair_backward(_lib.ptr(f), _lib.ptr(b), _lib.ptr(g), C_, H, W, _lib.ptr(grads), _lib.ptr(m0),
-                                                         _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(df), _lib.ptr(db),
-                                                         _lib.current_stream(f.device)), "gsvc_ssim_l1_pair_backward")
-        return df, db, None
+        d = torch.empty_like(a)
+        db = torch.empty_like(b) if ctx.pair else None
+        L, st = _lib.lib(), _lib.current_stream(a.device)
+        if ctx.pair:
+            _lib.check(L.gsvc_ssim_l1_pair_backward(_lib.ptr(a), _lib.ptr(b), _lib.ptr(g), C_, H, W, _lib.ptr(grads), _lib.ptr(m0),
+                                                    _lib.ptr(m1), _lib.ptr(m2), _lib.ptr(d), _lib.ptr(db), st), "gsvc_ssim_l1_pair_backward")
+        else:
+            _lib.check(L.gsvc_ssim_l1_backward(_lib.ptr(a), _lib.ptr(g), C_, H, W, _lib.ptr(grads), _lib.ptr(m0), _lib.ptr(m1),
+                                               _lib.ptr(m2), _lib.ptr(d), st), "gsvc_ssim_l1_backward")
+        return d, db, None
 
 
-def ssim_l1_pair(img_f, img_b, img2):
-    """(ssim_func(a, img2), l1_loss_func(a, img2), a.detach()) for a = (img_f + flip(img_b, W)) / 2, [3,H,W] CUDA images."""
-    return _SsimL1Pair.apply(img_f, img_b, img2)
-
-
-def ssim_l1(img1, img2):
-    """Fused (ssim_func(img1, img2), l1_loss_func(img1, img2)) for [3,H,W] CUDA images (one kernel each way)."""
-    return _SsimL1.apply(img1, img2)
+def ssim_l1(img, gt, img_b=None):
+    """Fused (ssim_func(x, gt), l1_loss_func(x, gt)) for [C,H,W] CUDA images (one kernel each way); the gradient goes to ``img`` (and
+    ``img_b``).  x = img, or with ``img_b`` the two-view frame x = (img + flip(img_b, W)) / 2, then also returned, detached, as a third
+    result."""
+    return _SsimL1.apply(img, img_b, gt)
 
 
 class _MsSsimL1(torch.autograd.Function):
@@ -148,24 +129,82 @@ def _check_ms_images(name, *imgs):
         raise ValueError(f"{name}: images must be [C, H, W] tensors of one shape")
 
 
-def ms_ssim_l1(img1, img2):
-    """(metrics.ms_ssim(img1, img2, data_range=1), l1_loss_func(img1, img2)) of [C,H,W] images, both sides > 160; the gradient goes
-    to img1.  CUDA tensors take the fused kernels of csrc/msssim_loss.hip (eleven launches forward, five backward); CPU tensors the
-    tensor expressions, differentiable through autograd."""
-    _check_ms_images("ms_ssim_l1", img1, img2)
-    if not img1.is_cuda:
-        from .metrics import ms_ssim
-        return ms_ssim(img1, img2, data_range=1), l1_loss_func(img1, img2)
-    return _MsSsimL1.apply(img1, None, img2)
+def ms_ssim_l1(img, gt, img_b=None):
+    """(metrics.ms_ssim(x, gt, data_range=1), l1_loss_func(x, gt)) of [C,H,W] images, both sides > 160; the gradient goes to ``img``
+    (and ``img_b``).  x = img, or with ``img_b`` the two-view frame x = (img + flip(img_b, W)) / 2, then also returned, detached, as a
+    third result.  CUDA tensors take the fused kernels of csrc/msssim_loss.hip (eleven launches forward, five backward); CPU tensors
+    the tensor expressions, differentiable through autograd."""
+    _check_ms_images("ms_ssim_l1", img, gt, *(() if img_b is None else (img_b,)))
+    if img.is_cuda:
+        return _MsSsimL1.apply(img, img_b, gt)
+    from .metrics import ms_ssim
+    x = img if img_b is None else (img + torch.flip(img_b, dims=[2])) / 2
+    terms = ms_ssim(x, gt, data_range=1), l1_loss_func(x, gt)
+    return terms if img_b is None else terms + (x.detach(),)
 
 
-def ms_ssim_l1_pair(img_f, img_b, img2):
-    """(ms_ssim, l1, a.detach()) of ms_ssim_l1(a, img2) for the two-view frame a = (img_f + flip(img_b, W)) / 2."""
-    _check_ms_images("ms_ssim_l1_pair", img_f, img_b, img2)
-    if not img_f.is_cuda:
-        a = (img_f + torch.flip(img_b, dims=[2])) / 2
-        return ms_ssim_l1(a, img2) + (a.detach(),)
-    return _MsSsimL1.apply(img_f, img_b, img2)
+DISTORTIONS = {"ssim": ssim_l1, "ms_ssim": ms_ssim_l1}      # OptimizationParams.distortion -> the structural term with its L1
+
+
+class StepDistortion:
+    """The distortion of a fitting step: where it is taken (``opt.loss_domain``: float RGB, or the Y'CbCr planes the codec delivers and
+    is measured on, gsvc_amd/yuv_loss.py) and its structural term (``opt.distortion``: single-scale SSIM, or MS-SSIM as
+    ``metrics.ms_ssim`` reports it), decided once against the dataset a Trainer is built on.  It keeps no dataset: the methods that
+    read one take the step's current one."""
+
+    def __init__(self, opt, dataset):
+        self.domain = opt.loss_domain
+        self.layout = yuv_loss.domain_layout(self.domain)          # of the planes; None in the rgb domain (an unknown name is refused here)
+        self.fmt = self.matrix = None
+        self.native_planes = False
+        if self.layout is not None:
+            yuv_loss.check_domain(self.domain, dataset.height, dataset.width)
+            yuv_loss.check_dataset(dataset, self.layout)
+            self.fmt = yuv_loss.FrameFormat(self.layout, yuv_loss.loss_matrix(dataset))
+            self.matrix = self.fmt.matrix
+            self.native_planes = yuv_loss.native_planes(dataset, self.layout)      # the targets come from the file's codes: no picture is read
+        self.name = opt.distortion
+        if self.name not in DISTORTIONS:
+            raise ValueError(f"unknown distortion {self.name!r} (one of {', '.join(DISTORTIONS)})")
+        if self.name == "ms_ssim":
+            if self.domain != "rgb":
+                raise ValueError(f"distortion 'ms_ssim' is taken on RGB pictures: loss_domain must be 'rgb' (got {self.domain!r})")
+            if min(int(dataset.height), int(dataset.width)) <= 160:
+                raise ValueError(f"distortion 'ms_ssim' needs picture sides above 160 pixels for 5 scales "
+                                 f"(got {int(dataset.height)} x {int(dataset.width)})")
+        self.structural = DISTORTIONS[self.name]
+
+    def frame(self, dataset, i):
+        """Frame i of the dataset; without its picture where the step's targets are the file's own planes (a fetch of a
+        ``VideoFileCube(resident="u8")`` would launch a conversion nobody reads)."""
+        return dataset.get_dummy_frame(i) if self.native_planes else dataset[i]
+
+    def target(self, dataset, frame, i, dev):
+        """The ground truth of frame i in the loss domain: the picture [3, H, W], or its planes (tY, tC)."""
+        if self.fmt is None:
+            return frame.image.to(dev).permute(0, 2, 1).contiguous()
+        picture = None if self.native_planes else frame.image.to(dev)
+        return yuv_loss.target_planes(dataset, i, self.layout, self.matrix, picture=picture)
+
+    def __call__(self, img_f, img_b, target):
+        """``(terms, image)`` of one frame: its scalar terms, all L1 terms first and then all structural terms — ``(l1, s)`` in rgb,
+        ``(l1_y, l1_c, s_y, s_c)`` on planes — and the two-view frame (img_f + flip(img_b, W)) / 2, detached, which the kernels form
+        themselves; ``img_b`` None: ``img_f`` is that frame already."""
+        if self.fmt is None:
+            out = self.structural(img_f, target, img_b)
+            return (out[1], out[0]), (img_f if img_b is None else out[2]).detach()
+        terms, avg = yuv_loss.plane_terms(self.structural, img_f, img_b, target, self.fmt)
+        return terms, (img_f if img_b is None else avg).detach()
+
+    @staticmethod
+    def image_terms(terms1, terms2):
+        """The step's image terms of its two frames' tuples, interleaved: ``[l1_1, l1_2, s_1, s_2]`` in rgb.  The loss is
+        ``dot(stack(terms), weights)``: the order is that of ``weights`` and decides the sum's bits."""
+        return [t for pair in zip(terms1, terms2) for t in pair]
+
+    def weights(self, lambda_dssim):
+        """``(weights, const)`` of ``image_terms``: ``yuv_loss.distortion_weights``."""
+        return yuv_loss.distortion_weights(self.domain, lambda_dssim)
 
 
 def l1_loss_func(network_output, gt):
@@ -200,8 +239,8 @@ def ssim_func(img1, img2, window_size=11, size_average=True):
     if img1.is_cuda and window_size == 11:
         # GPU tensors always take the fused HIP kernel (per image when a batch is given)
         if img1.dim() == 3:
-            return _SsimL1.apply(img1, img2)[0]
-        per = torch.stack([_SsimL1.apply(a, b)[0] for a, b in zip(img1, img2)])
+            return _SsimL1.apply(img1, None, img2)[0]
+        per = torch.stack([_SsimL1.apply(a, None, b)[0] for a, b in zip(img1, img2)])
         return per.mean() if size_average else per
     squeeze = img1.dim() == 3
     a = img1.unsqueeze(0) if squeeze else img1

@@ -18,9 +18,9 @@ import contextlib
 import torch
 
 from . import dist as gdist
-from . import schedule, switches, yuv_loss
+from . import schedule, switches
 from .generate import GenerateMode, region
-from .loss_utils import calc_optical_loss, ms_ssim_l1, ms_ssim_l1_pair, render_regs, ssim_l1, ssim_l1_pair
+from .loss_utils import StepDistortion, calc_optical_loss, render_regs
 from .optim import FusedAdam
 from .ortho_gaussian_renderer import plan_views, render, render_many
 from .rasterizer import resolve_deferred
@@ -37,6 +37,30 @@ class StepOutput:
     renders: tuple
     active_gaussians: torch.Tensor  # sum over the 4 renders of Gaussians with radius > 0 (device scalar)
     frame_idx: int
+
+
+@dataclass
+class _Step:
+    """One attempt of a step: what its stages (``Trainer._step_body``) hand to one another; each stage's docstring names the fields it
+    reads and sets.  It holds the attempt's autograd graph (terms, loss), so it lives in ``_step_body``'s frame only: not on the
+    Trainer, not in the StepOutput, not in a hook's closure."""
+    iteration: int
+    frame_idx: int
+    early: bool                         # this attempt may run the early tail (the repeat after an overflow may not)
+    mode: object                        # the phase's GenerateMode
+    zown: object = None                 # the z-range ownership in force, or None
+    plan: object = None                 # the StepPlan queued for this frame pair, when it still matches
+    frame1: object = None
+    frame2: object = None
+    renders: tuple = None               # (frame 1 front, back, frame 2 front, back)
+    batch: object = None                # the renders' StepBatch; None in the unbatched step
+    ovf_handle: object = None           # the replicas' overflow reduction in flight (batched step)
+    image1: torch.Tensor = None         # the two-view frames
+    image2: torch.Tensor = None
+    terms: list = None                  # the loss's scalar terms, the image terms first
+    weights: list = None                # their weights, as host values
+    const: float = 0.0
+    loss: torch.Tensor = None
 
 
 def _release_graph(renders):
@@ -125,40 +149,12 @@ def _mean_over_selected(values, r):
     return (values * w).sum() / w.sum()
 
 
-DISTORTIONS = ("ssim", "ms_ssim")      # OptimizationParams.distortion
-
-
 class Trainer:
-    def __init__(self, gaussians, dataset, opt, pipe, model_params, seed: int = 0, batched: bool = True, prefetch: bool = True,
-                 shard_optimizer=None):
-        if shard_optimizer is not None:      # removed in round 4 (the index-range sharded Adam): accepted and ignored for one release
-            import warnings
-            warnings.warn("Trainer(shard_optimizer=...) is ignored: the optimizer is replicated (gsvc_amd/dist.py)", DeprecationWarning,
-                          stacklevel=2)
+    def __init__(self, gaussians, dataset, opt, pipe, model_params, seed: int = 0, batched: bool = True, prefetch: bool = True):
+        # what the step's image terms are and where they are taken: refuses a loss domain or a structural term this dataset cannot have
+        self._distortion = StepDistortion(opt, dataset)
+        self.loss_domain, self.loss_matrix, self.distortion = self._distortion.domain, self._distortion.matrix, self._distortion.name
         self.batched = batched
-        # where the distortion is taken (gsvc_amd/yuv_loss.py): float RGB, or the Y'CbCr planes the codec delivers and is measured on
-        self.loss_domain = getattr(opt, "loss_domain", "rgb")
-        self._loss_fmt = None
-        self._native_planes = False
-        self.loss_matrix = None          # of the planes; None in the rgb domain
-        layout = yuv_loss.domain_layout(self.loss_domain)          # (an unknown name is refused here)
-        if layout is not None:
-            from .frames_out import FrameFormat
-            yuv_loss.check_domain(self.loss_domain, dataset.height, dataset.width)
-            yuv_loss.check_dataset(dataset, layout)
-            self._loss_fmt = FrameFormat(layout, yuv_loss.loss_matrix(dataset))
-            self.loss_matrix = self._loss_fmt.matrix
-            self._native_planes = yuv_loss.native_planes(dataset, layout)      # the targets come from the file's codes: no picture is read
-        # the structural term: single-scale SSIM, or MS-SSIM as metrics.ms_ssim reports it (csrc/msssim_loss.hip)
-        self.distortion = getattr(opt, "distortion", "ssim")
-        if self.distortion not in DISTORTIONS:
-            raise ValueError(f"unknown distortion {self.distortion!r} (one of {', '.join(DISTORTIONS)})")
-        if self.distortion == "ms_ssim":
-            if self.loss_domain != "rgb":
-                raise ValueError(f"distortion 'ms_ssim' is taken on RGB pictures: loss_domain must be 'rgb' (got {self.loss_domain!r})")
-            if min(int(dataset.height), int(dataset.width)) <= 160:
-                raise ValueError(f"distortion 'ms_ssim' needs picture sides above 160 pixels for 5 scales "
-                                 f"(got {int(dataset.height)} x {int(dataset.width)})")
         # prefetch: the next step's frame pair is drawn, its visibility test run and every data-dependent index list of its
         # generation pass queued at the END of a step (gsvc_amd.generate.StepPlan): the next step then starts with one wait
         # for nine counts instead of six device round trips with an idle GPU
@@ -193,8 +189,16 @@ class Trainer:
         gaussians._zown = self._zown      # gsvc_amd.generate._param_means reads the owners' means from it
         self._mask_reg_weight = 0.0
         self._ovf_handle = None
+        self._last_idx = None                  # the frame pair of the last attempted step (its repeat after an overflow takes it again)
+        self._early = None                     # (params, idx, mode, plan) of an early tail that ran inside this step's backward
+        self.repeated_steps = 0                # steps run twice because a rasterizer instance buffer overflowed
+        self.early_steps = 0                   # steps whose _scaling / _mask update and next plan ran from inside the backward
+        self._w_key = self._w = None           # the loss weights on the device, and the host values they were made from
+        self._logged_exchange = None           # which per-anchor gradient exchange the one-time log line last named
         # which side bounds the steps, measured (gsvc_amd.schedule.StepContext.gpu_bound_hint): the host's blocked time per step, smoothed
         self._blocked_ema = None
+        self._steps_seen = self._ema_n = 0     # steps, and steps that entered the average
+        self.bound_log = []                    # (step, gpu_bound, blocked ms) of the last 32 changes of the decision
         self._ctx = schedule.StepContext()      # this trainer's own measurement (made current for the duration of each of its steps)
         # the generators' and mlp_deform's parameters: the networks whose weight gradients may take a stream of their own
         self._chain_params = [p for m in (gaussians.get_opacity_mlp, gaussians.get_color_mlp, gaussians.get_cov_mlp, gaussians.get_deform_mlp)
@@ -228,7 +232,7 @@ class Trainer:
         ctx = self._ctx
         b = ctx.host_blocked_s
         ctx.host_blocked_s = 0.0
-        self._steps_seen = getattr(self, "_steps_seen", 0) + 1
+        self._steps_seen += 1
         if switches.NO_ADAPTIVE_BOUND or switches.DETERMINISTIC:
             # (deterministic mode: a wall-clock measurement must not pick between the separate and the multi-product layer launches —
             # they round differently — so the row count alone decides, the same way in every run)
@@ -237,7 +241,7 @@ class Trainer:
         if self._steps_seen <= 8:
             return
         self._blocked_ema = b if self._blocked_ema is None else 0.8 * self._blocked_ema + 0.2 * b
-        self._ema_n = getattr(self, "_ema_n", 0) + 1
+        self._ema_n += 1
         if self._steps_seen < 16 or self._ema_n < 8:
             # (the average needs a few steps of its own: a fit that leaves the deterministic mode, or follows a synchronisation, starts
             # it with ONE step's wait — bench.py's first timed steps after its frozen pretrain were decided by a 0.008 ms sample and ran
@@ -251,7 +255,7 @@ class Trainer:
         if ctx.gpu_bound_hint != before:
             # a wall-clock measurement changes which launches the step takes from here on: on record, so that runs can be compared
             ctx.flips += 1
-            self.bound_log = getattr(self, "bound_log", [])[-31:] + [(self._steps_seen, bool(ctx.gpu_bound_hint), 1e3 * self._blocked_ema)]
+            self.bound_log = self.bound_log[-31:] + [(self._steps_seen, bool(ctx.gpu_bound_hint), 1e3 * self._blocked_ema)]
 
     def step(self, iteration: int, frame_idx: int | None = None) -> StepOutput:
         # whatever this step's generation, waits and backward read and add to is this trainer's; outside a step, the default context
@@ -262,7 +266,7 @@ class Trainer:
             self._early = None
             out = self._step(iteration, frame_idx)
             if out is None:      # a rasterizer instance buffer overflowed (capacity now raised): repeat the step
-                self.repeated_steps = getattr(self, "repeated_steps", 0) + 1
+                self.repeated_steps += 1
                 dropped = None
                 if self._early is not None:
                     # the guarded early update saw the overflow word and wrote nothing: only its step counts moved.  The plan it
@@ -356,7 +360,7 @@ class Trainer:
                 self._add_mask_reg()
                 guards = [self._ovf_handle[2]]        # the MAX over the ranks of the four local words (this rank's included)
             pc.optimizer.step(only=params, guards=guards)
-            self.early_steps = getattr(self, "early_steps", 0) + 1
+            self.early_steps += 1
             idx = self.rng.randint(self.lo, max(self.lo, self.hi - 1))
             self._prefetch_frames(idx)
             mode = render_mode_at(self.controller.current_iteration + 1, self.opt)
@@ -375,23 +379,11 @@ class Trainer:
         return switches.DP_SPARSE == "1" or gdist.sparse_rows_pay(gdist.world_size(), int(self.pc._anchor.shape[0]),
                                                                                   plan.distinct_cap)
 
-    def _frame(self, i):
-        """Frame i of the dataset; without its picture where the step's targets are the file's own planes (a fetch of a
-        ``VideoFileCube(resident="u8")`` would launch a conversion nobody reads)."""
-        return self.dataset.get_dummy_frame(i) if self._native_planes else self.dataset[i]
-
-    def _targets(self, frame, i, dev):
-        """The ground truth of frame i in the loss domain: the picture [3, H, W], or its planes (tY, tC)."""
-        if self._loss_fmt is None:
-            return frame.image.to(dev).permute(0, 2, 1).contiguous()
-        picture = None if self._native_planes else frame.image.to(dev)
-        return yuv_loss.target_planes(self.dataset, i, self._loss_fmt.layout, self._loss_fmt.matrix, picture=picture)
-
     def _views(self, frame_idx):
         """The step's four views: (frame, frame seen from the opposite side) of the two adjacent frames."""
         import copy
         views = []
-        for fr in (self._frame(frame_idx), self._frame(frame_idx + 1)):
+        for fr in (self._distortion.frame(self.dataset, frame_idx), self._distortion.frame(self.dataset, frame_idx + 1)):
             back = copy.copy(fr)
             back.view_matrix, back.view_matrix_s = fr.view_matrix_s, fr.view_matrix
             views += [fr, back]
@@ -418,71 +410,82 @@ class Trainer:
                 g.step_cache = None
 
     def _step_body(self, iteration: int, frame_idx: int | None = None, early: bool = True):
-        opt, pc = self.opt, self.pc
-        dev = pc.device
-        pc.update_learning_rate(iteration)
+        self.pc.update_learning_rate(iteration)
         if frame_idx is None:
             frame_idx = self.rng.randint(self.lo, max(self.lo, self.hi - 1))
         self._last_idx = frame_idx
-        frame1, frame2 = self._frame(frame_idx), self._frame(frame_idx + 1)
-        mode = self.controller.render_mode
-        retain_grad = opt.update_until > iteration >= 0
+        st = _Step(iteration, frame_idx, early, self.controller.render_mode)
+        self._forward(st)
+        self._image_terms(st)
+        self._model_terms(st)
+        self._combine(st)
+        self._arm_exchange(st)
+        self._backward(st)
+        return self._finish(st)
 
-        zown = self._zown if (self._zown is not None and self.reducer.enabled) else None
+    def _forward(self, st):
+        """The four renders.  Reads iteration, frame_idx, mode; sets zown, plan, frame1, frame2, renders, batch, ovf_handle and, of the
+        unbatched step, image1, image2 (attached).  Starts the replicas' overflow reduction and orders this stream behind the uploads
+        of the pair's pictures."""
+        pc, dist = self.pc, self._distortion
+        frame_idx, mode = st.frame_idx, st.mode
+        st.frame1, st.frame2 = dist.frame(self.dataset, frame_idx), dist.frame(self.dataset, frame_idx + 1)
+        retain_grad = self.opt.update_until > st.iteration >= 0
+        zown = st.zown = self._zown if (self._zown is not None and self.reducer.enabled) else None
         pc._zown = zown
         if zown is not None:
             zown.update_means(pc)
         if self.batched:
             # one generation pass for the 4 views (frame1 f/b, frame2 f/b), then 4 rasterizations
-            plan = self._plan if (self._plan is not None and self._plan_idx == frame_idx and self._plan_mode == mode and
-                                  self._plan.matches(pc)) else None
+            plan = st.plan = self._plan if (self._plan is not None and self._plan_idx == frame_idx and self._plan_mode == mode and
+                                            self._plan.matches(pc)) else None
             views = plan.frames if plan is not None else self._views(frame_idx)
-            frame1, frame2 = views[0], views[2]
+            st.frame1, st.frame2 = views[0], views[2]
             with region('step.render_many'):
-                r1f, r1b, r2f, r2b = render_many(views, self.pc, self.pipe, self.background, retain_grad=retain_grad, mode=mode,
-                                                 dense=True, anchor_grad=self.anchor_grad, plan=plan)
-            image1 = image2 = None         # the two-view frames are formed inside the SSIM kernels below (ssim_l1_pair)
+                st.renders = tuple(render_many(views, self.pc, self.pipe, self.background, retain_grad=retain_grad, mode=mode,
+                                               dense=True, anchor_grad=self.anchor_grad, plan=plan))
+            st.batch = st.renders[0].generated_gaussians.batch
             # replicas: "did any rank's instance buffer overflow" is reduced right behind the forward kernels, so that
             # the end-of-step check does not have to wait for the backward (overflow word = second int32 of a binning blob)
-            ovf_handle = gdist.any_rank_start([r.raster_state.binning[4:8].view(torch.int32) for r in (r1f, r1b, r2f, r2b)])
-            self._ovf_handle = ovf_handle
+            st.ovf_handle = gdist.any_rank_start([r.raster_state.binning[4:8].view(torch.int32) for r in st.renders])
+            self._ovf_handle = st.ovf_handle
         else:
-            r1f, r1b, image1 = self._two_views(frame1, mode, retain_grad)
-            r2f, r2b, image2 = self._two_views(frame2, mode, retain_grad)
-        renders = (r1f, r1b, r2f, r2b)
+            r1f, r1b, st.image1 = self._two_views(st.frame1, mode, retain_grad)
+            r2f, r2b, st.image2 = self._two_views(st.frame2, mode, retain_grad)
+            st.renders = (r1f, r1b, r2f, r2b)
         ready = getattr(self.dataset, "ready", None)
         if ready is not None:          # pictures uploaded on a copy stream (HostResidentCube): their first readers come now
             ready(frame_idx)
             ready(frame_idx + 1)
-        gt1, gt2 = self._targets(frame1, frame_idx, dev), self._targets(frame2, frame_idx + 1, dev)
-        if self._loss_fmt is not None:
-            # the render's planes against the file's (or the picture's) planes: luma and the chroma pair are two calls of the SSIM / L1
-            # kernels per frame, chained into the transform (the two-view frame is formed inside the transform's kernel)
-            y1 = yuv_loss.yuv_ssim_l1(r1f.rendered_image if image1 is None else image1, r1b.rendered_image if image1 is None else None,
-                                      gt1, self._loss_fmt)
-            y2 = yuv_loss.yuv_ssim_l1(r2f.rendered_image if image2 is None else image2, r2b.rendered_image if image2 is None else None,
-                                      gt2, self._loss_fmt)
-            if image1 is None:
-                image1, image2 = y1[4], y2[4]
-            terms = [y1[1], y2[1], y1[3], y2[3], y1[0], y2[0], y1[2], y2[2]]
-        elif image1 is None:
-            pair_loss = ms_ssim_l1_pair if self.distortion == "ms_ssim" else ssim_l1_pair
-            ssim1, l1_1, image1 = pair_loss(r1f.rendered_image, r1b.rendered_image, gt1)
-            ssim2, l1_2, image2 = pair_loss(r2f.rendered_image, r2b.rendered_image, gt2)
-            terms = [l1_1, l1_2, ssim1, ssim2]
+
+    def _image_terms(self, st):
+        """The two frames' distortion, frame 1's kernels first.  Reads frame_idx, frame1, frame2, renders, image1, image2; sets terms,
+        weights, const, and image1, image2 to the detached two-view frames (the batched step's are formed inside the loss kernels)."""
+        dist, dev = self._distortion, self.pc.device
+        r1f, r1b, r2f, r2b = st.renders
+        gt1 = dist.target(self.dataset, st.frame1, st.frame_idx, dev)
+        gt2 = dist.target(self.dataset, st.frame2, st.frame_idx + 1, dev)
+        if self.batched:
+            terms1, st.image1 = dist(r1f.rendered_image, r1b.rendered_image, gt1)
+            terms2, st.image2 = dist(r2f.rendered_image, r2b.rendered_image, gt2)
         else:
-            image_loss = ms_ssim_l1 if self.distortion == "ms_ssim" else ssim_l1
-            ssim1, l1_1 = image_loss(image1, gt1)
-            ssim2, l1_2 = image_loss(image2, gt2)
-            terms = [l1_1, l1_2, ssim1, ssim2]
+            terms1, st.image1 = dist(st.image1, None, gt1)
+            terms2, st.image2 = dist(st.image2, None, gt2)
         # the loss is a weighted sum of scalar terms: they are collected and combined with one stack + dot (instead of
         # one tiny kernel per +, *, and their backward nodes)
-        weights, const = yuv_loss.distortion_weights(self.loss_domain, opt.lambda_dssim)
-        batch = r1f.generated_gaussians.batch if self.batched else None
-        # the terms below read the generation pass's tensors and parameters, not the images: a dozen small launches each way, issued
-        # on the small-work stream behind the generation pass's event so that they run under the compositing kernels (their backward
-        # too: autograd runs a node on its forward's stream) instead of behind the image losses
-        side = None
+        st.terms = dist.image_terms(terms1, terms2)
+        st.weights, st.const = dist.weights(self.opt.lambda_dssim)
+
+    def _model_terms(self, st):
+        """Regularisers, optical term, rates, hash-grid bits and mask term.  Reads frame_idx, renders, batch, plan, zown; appends to
+        terms and weights (and sets ``self._mask_reg_weight``).  These terms read the generation pass's tensors and parameters, not the
+        images: a dozen small launches each way, issued on the small-work stream behind the generation pass's event so that they run
+        under the compositing kernels (their backward too: autograd runs a node on its forward's stream) instead of behind the image
+        losses.  The step's stream waits for that stream before this returns."""
+        opt, pc = self.opt, self.pc
+        dev = pc.device
+        batch, renders, zown, terms, weights = st.batch, st.renders, st.zown, st.terms, st.weights
+        side = flow = None
         if batch is not None and batch.generated_event is not None:      # (recorded only when the batch's small_work is set)
             side = schedule.small_work_stream(dev)
             side.wait_event(batch.generated_event)
@@ -496,15 +499,15 @@ class Trainer:
                           sum((1 - r.neural_opacity).mean() for r in renders)]
             weights += [opt.scaling_reg, opt.opacity_reg]
             if opt.optical_lambda != 0:
-                flow = self.dataset.get_optical_flow(frame_idx)
-                terms.append(calc_optical_loss(r1f, r1b, r2f, r2b, flow, self.dataset.x_min, self.dataset.y_min,
+                flow = self.dataset.get_optical_flow(st.frame_idx)
+                terms.append(calc_optical_loss(*renders, flow, self.dataset.x_min, self.dataset.y_min,
                                                self.dataset.scale, self.dataset.width, self.dataset.height, pc.n_offsets))
                 weights.append(opt.optical_lambda)
             if self.controller.entropy_constrained:
                 assert all(r.entropy_constrained for r in renders)
                 denom = pc._anchor.shape[0] * (pc.feat_dim + 6 + 3 * pc.n_offsets)
-                # sparse data-parallel exchange (below): the regulariser's dense gradient is added after the exchange (_add_mask_reg)
-                sparse_dp = self._sparse_dp(plan if self.batched else None) or zown is not None
+                # sparse data-parallel exchange (_arm_exchange): the regulariser's dense gradient is added after the exchange (_add_mask_reg)
+                sparse_dp = self._sparse_dp(st.plan) or zown is not None
                 self._mask_reg_weight = 5e-4 if sparse_dp else 0.0
                 rate_sum = batch.bit_per_param_sum if batch is not None else None
                 # the renders' rates enter with one weight: their sum, when the batched generation already formed it, is one term
@@ -515,51 +518,70 @@ class Trainer:
         if side is not None:
             # what the terms above read of the step's stream's allocations (and saved for their backward on the small-work stream)
             schedule.record_on(side, batch.scaling, batch.neural_opacity, batch.mask, batch.world, batch.vis,
-                               [g.step_cache for g in grid_tables(pc)], flow if opt.optical_lambda != 0 else None)
+                               [g.step_cache for g in grid_tables(pc)], flow)
             main_stream = torch.cuda.current_stream(dev)
             main_stream.wait_stream(side)
             for t in terms[n_image_terms:]:
                 if t.is_cuda:
                     t.record_stream(main_stream)       # allocated on the small-work stream, combined on this one
-        key = tuple(weights)
-        if getattr(self, "_w_key", None) != key:      # the weights change only with the training phase
+
+    def _combine(self, st):
+        """The loss.  Reads terms, weights, const; sets loss = dot(stack(terms), weights) + const."""
+        key = tuple(st.weights)
+        if self._w_key != key:      # the weights change only with the training phase
             from .generate import host_values
-            self._w_key, self._w = key, host_values(weights, dev, torch.float32)
-        w = self._w
-        loss = torch.dot(torch.stack([t.reshape(()) for t in terms]), w) + const
+            self._w_key, self._w = key, host_values(st.weights, self.pc.device, torch.float32)
+        st.loss = torch.dot(torch.stack([t.reshape(()) for t in st.terms]), self._w) + st.const
+
+    def _arm_exchange(self, st):
+        """Data parallel: which gradients the reducer's hooks exchange in this backward, and how the per-anchor ones travel.  Reads
+        mode, plan, zown; sets nothing."""
+        pc, plan, zown = self.pc, st.plan, st.zown
         owned = {id(getattr(pc, n)) for n in gdist.PER_ANCHOR} if zown is not None else ()
-        self.reducer.arm([p for g in pc.optimizer.param_groups for p in g["params"] if id(p) not in owned], phase=mode)
+        self.reducer.arm([p for g in pc.optimizer.param_groups for p in g["params"] if id(p) not in owned], phase=st.mode)
         use_rows = bool(self.batched and self._sparse_dp(plan))
         if use_rows:
             # the per-anchor gradients are non-zero only in the rows of this rank's distinct visible anchors: exchanged as rows
             self.reducer.set_sparse(plan.distinct, plan.distinct_cap, [pc._offset, pc._mask, pc._anchor_feat, pc._scaling])
         else:
             self.reducer.set_sparse(None, 0, [])
-        if zown is not None and gdist.rank() == 0 and getattr(self, "_logged_exchange", None) != "zown":
+        if zown is not None and gdist.rank() == 0 and self._logged_exchange != "zown":
             import sys
             zown.ensure(pc)
             self._logged_exchange = "zown"
             sent, got = zown.halo_rows()
             sys.stderr.write(f"gsvc_amd.train: per-anchor tensors owned by z-range: rank 0 owns {int(zown.own_idx.shape[0])} of {int(pc._anchor.shape[0])} "
                              f"anchors, sends {sent} halo rows of gradients and returns {got} rows of parameters per step, {gdist.world_size()} ranks\n")
-        elif zown is None and gdist.active() and gdist.rank() == 0 and getattr(self, "_logged_exchange", None) != use_rows and plan is not None:
+        elif zown is None and gdist.active() and gdist.rank() == 0 and self._logged_exchange != use_rows and plan is not None:
             import sys
             self._logged_exchange = use_rows
             sys.stderr.write(f"gsvc_amd.train: per-anchor gradient exchange = {'rows of the distinct visible anchors (cap ' + str(plan.distinct_cap) + ')' if use_rows else 'dense all-reduce'}"
                              f" at {int(pc._anchor.shape[0])} anchors, {gdist.world_size()} ranks\n")
+
+    def _early_plan_pays(self, st):
+        """Whether this backward updates ``_scaling`` / ``_mask`` and queues the next step's plan from inside (``_early_tail``).  Reads
+        iteration, early, mode, zown, batch."""
+        opt, pc = self.opt, self.pc
+        return bool(st.early and self.batched and self.prefetch and pc._anchor.is_cuda
+                    and (not gdist.active() or (self.reducer.enabled and self.reducer._order is not None and st.zown is None))
+                    and not self.anchor_grad      # a trained anchor tensor moves behind the early plan's visibility test
+                    and st.mode is not None and st.iteration < opt.iterations and not self.controller.gaussian_adjust_anchor
+                    and isinstance(pc.optimizer, FusedAdam) and not switches.NO_EARLY_PLAN
+                    and pc._scaling.requires_grad and pc._mask.requires_grad
+                    # it pays when the GPU, not the host, bounds the step (the hook's work costs ~1 ms of host time more on the
+                    # autograd thread than at the end of the step: a 6 k-row step went 8.3 -> 9.7 ms, the 200 k-row step 11.95 -> 11.3)
+                    and (switches.EARLY_PLAN or st.batch.gpu_bound))
+
+    def _backward(self, st):
+        """The backward and the gradients' exchange.  Reads loss, renders, batch, mode, zown and what ``_early_plan_pays`` reads; sets nothing.
+        The hook below holds ``self``, the renders, the tensors it waits for and its counter — not the step record."""
+        pc, renders, batch, loss, zown = self.pc, st.renders, st.batch, st.loss, st.zown
+        dev = pc.device
         handles = []
-        if (early and self.batched and self.prefetch and pc._anchor.is_cuda
-                and (not gdist.active() or (self.reducer.enabled and self.reducer._order is not None and zown is None))
-                and not self.anchor_grad      # a trained anchor tensor moves behind the early plan's visibility test
-                and mode is not None and iteration < opt.iterations and not self.controller.gaussian_adjust_anchor
-                and isinstance(pc.optimizer, FusedAdam) and not switches.NO_EARLY_PLAN
-                and pc._scaling.requires_grad and pc._mask.requires_grad
-                # it pays when the GPU, not the host, bounds the step (the hook's work costs ~1 ms of host time more on the
-                # autograd thread than at the end of the step: a 6 k-row step went 8.3 -> 9.7 ms, the 200 k-row step 11.95 -> 11.3)
-                and (switches.EARLY_PLAN or batch.gpu_bound)):
+        if self._early_plan_pays(st):
             # STE_ENTROPY renders from detached attributes (reference guassian.py:205-207): _scaling receives no gradient there,
             # is not changed by the step, and its hook would never run
-            waited = [pc._mask] if mode == GenerateMode.TRAININ_STE_ENTROPY else [pc._scaling, pc._mask]
+            waited = [pc._mask] if st.mode == GenerateMode.TRAININ_STE_ENTROPY else [pc._scaling, pc._mask]
             pending = [len(waited)]
 
             def arrived(_p):
@@ -584,14 +606,18 @@ class Trainer:
         with region('step.reducer_finish'):
             self.reducer.finish()
             if zown is not None:
-                zown.exchange_grads(pc, self._zown_names(mode))
+                zown.exchange_grads(pc, self._zown_names(st.mode))
             self._add_mask_reg()
 
+    def _finish(self, st):
+        """Counters and the overflow verdict (None: the step is to be repeated), densification statistics, anchor adjustment,
+        optimizer, and the graph-free StepOutput.  Reads iteration, frame_idx, mode, zown, renders, ovf_handle, loss, image1, image2."""
+        opt, pc, renders, zown = self.opt, self.pc, st.renders, st.zown
         if self.batched:
             # the only host synchronisation of the step after the visibility test: the 4 renders' instance counters
             with region('step.resolve_counters'):
                 _, overflowed = resolve_deferred([r.raster_state for r in renders])
-            if gdist.any_rank_finish(ovf_handle, overflowed):      # replicas repeat the step together (their collectives must pair up)
+            if gdist.any_rank_finish(st.ovf_handle, overflowed):      # replicas repeat the step together (their collectives must pair up)
                 return None
             for r in renders:
                 r.num_rendered = r.raster_state.counters()[0]
@@ -603,19 +629,17 @@ class Trainer:
                 else:
                     for r in renders:
                         pc.training_statis(r)
-            adjusted = False
             if self.controller.gaussian_adjust_anchor:
-                self._adjust_anchor(iteration)
-                adjusted = True
+                self._adjust_anchor(st.iteration)
             if self.controller.clean_denorm:
                 pc.opacity_accum = pc.offset_gradient_accum = pc.offset_denom = None
-            if iteration < opt.iterations:
+            if st.iteration < opt.iterations:
                 with region('step.optimizer'):
                     pc.optimizer.step()
                     pc.optimizer.zero_grad(set_to_none=True)
                     if zown is not None:
-                        zown.refresh_params(pc, self._zown_names(mode))
+                        zown.refresh_params(pc, self._zown_names(st.mode))
         active = sum(r.active_gaussains for r in renders)
         _release_graph(renders)      # at every size: a StepOutput never carries the step's autograd graph (see _release_graph)
-        return StepOutput(loss=loss.detach(), image1=image1.detach(), image2=image2.detach(), renders=renders,
-                          active_gaussians=active, frame_idx=frame_idx)
+        return StepOutput(loss=st.loss.detach(), image1=st.image1, image2=st.image2, renders=renders,
+                          active_gaussians=active, frame_idx=st.frame_idx)

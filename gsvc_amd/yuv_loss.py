@@ -35,7 +35,8 @@ def check_domain(domain: str, H: int, W: int):
 
 
 def distortion_weights(domain: str, lambda_dssim: float):
-    """``(weights, const)`` of the image terms of a step's two frames: the loss takes ``dot(terms, weights) + const``.
+    """``(weights, const)`` of the image terms of a step's two frames: the loss takes ``dot(terms, weights) + const``.  The terms are
+    the two frames' tuples of ``loss_utils.StepDistortion`` — a frame's L1 terms, then its structural terms — interleaved.
 
     ``"rgb"``: terms ``[l1_1, l1_2, ssim_1, ssim_2]``, D = (1 - l) L1 + l (1 - SSIM) per frame.  A yuv domain: terms ``[l1_y1, l1_y2,
     l1_c1, l1_c2, ssim_y1, ssim_y2, ssim_c1, ssim_c2]`` and D = 0.75 D_Y + 0.25 D_C per frame, D_C over both chroma planes: the 6:1:1
@@ -125,16 +126,22 @@ def yuv_planes(img_f, img_b=None, layout: str = "yuv420p", matrix: str = "bt709"
     return _YuvPlanes.apply(img_f, img_b, layout, matrix)
 
 
-def yuv_ssim_l1(img_f, img_b, target, fmt: FrameFormat):
-    """``(ssim_y, l1_y, ssim_c, l1_c, a)``: mean SSIM and mean |difference| of the luma plane and of the two chroma planes of the
-    two-view frame against ``target = (tY, tC)`` (``target_planes``, ``frame_planes`` + ``split_planes``) in the layout and matrix of
-    ``fmt``.  The SSIM / L1 kernels are those of ``loss_utils.ssim_l1`` with C = 1 and C = 2; autograd chains their backward into the
-    transform's."""
-    from .loss_utils import ssim_l1
+def plane_terms(structural, img_f, img_b, target, fmt: FrameFormat):
+    """``((l1_y, l1_c, s_y, s_c), a)``: ``structural(x, gt) -> (s, l1)`` (``loss_utils.ssim_l1``) taken of the luma plane (C = 1) and
+    of the two chroma planes (C = 2) of the two-view frame against ``target = (tY, tC)`` (``target_planes``, ``frame_planes`` +
+    ``split_planes``) in the layout and matrix of ``fmt``; autograd chains the terms' backward into the transform's."""
     tY, tC = target
     Y, C, avg = yuv_planes(img_f, img_b, fmt.layout, fmt.matrix)
-    ssim_y, l1_y = ssim_l1(Y, tY)
-    ssim_c, l1_c = ssim_l1(C, tC)
+    s_y, l1_y = structural(Y, tY)
+    s_c, l1_c = structural(C, tC)
+    return (l1_y, l1_c, s_y, s_c), avg
+
+
+def yuv_ssim_l1(img_f, img_b, target, fmt: FrameFormat):
+    """``(ssim_y, l1_y, ssim_c, l1_c, a)``: ``plane_terms`` with mean SSIM (the kernels of ``loss_utils.ssim_l1``) as the structural
+    term."""
+    from .loss_utils import ssim_l1
+    (l1_y, l1_c, ssim_y, ssim_c), avg = plane_terms(ssim_l1, img_f, img_b, target, fmt)
     return ssim_y, l1_y, ssim_c, l1_c, avg
 
 

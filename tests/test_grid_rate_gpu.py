@@ -403,14 +403,14 @@ def test_fused_ssim_l1_matches_torch_and_reference(H, W):
 @pytest.mark.gpu
 @pytest.mark.parametrize("H,W", [(48, 64), (70, 100)])
 def test_ssim_l1_pair_equals_the_averaged_frame(H, W):
-    """ssim_l1_pair forms the two-view frame (f + flip_W(b)) / 2 inside the kernels: same losses, same frame and the same gradients
-    for both views as averaging first and calling ssim_l1."""
+    """ssim_l1 with ``img_b`` forms the two-view frame (f + flip_W(b)) / 2 inside the kernels: same losses, same frame and the same gradients
+    for both views as averaging first and calling it without."""
     from gsvc_amd import loss_utils as LU
     gen = torch.Generator().manual_seed(H + W)
     f = torch.rand(3, H, W, generator=gen).cuda().requires_grad_(True)
     b = torch.rand(3, H, W, generator=gen).cuda().requires_grad_(True)
     gt = torch.rand(3, H, W, generator=gen).cuda()
-    s, l, avg = LU.ssim_l1_pair(f, b, gt)
+    s, l, avg = LU.ssim_l1(f, gt, img_b=b)
     (0.2 * (1 - s) + 0.8 * l).backward()
     got = (f.grad.clone(), b.grad.clone())
     f.grad = b.grad = None

@@ -1,6 +1,6 @@
 """MS-SSIM as a fitting loss, without a GPU: the float64 restatement of tests/_msssim_loss_ref.py against ``metrics.ms_ssim``, the
-backward formula of csrc/msssim_loss.hip written out by hand against float64 autograd, the CPU path of ``ms_ssim_l1`` /
-``ms_ssim_l1_pair``, the ``distortion`` switch of the step and of the tools, and the host-side checks of the C entries."""
+backward formula of csrc/msssim_loss.hip written out by hand against float64 autograd, the CPU path of ``ms_ssim_l1`` (plain and
+with ``img_b``), the ``distortion`` switch of the step and of the tools, and the host-side checks of the C entries."""
 import ctypes as C
 import os
 import sys
@@ -48,7 +48,7 @@ def test_backward_formula_on_a_clipped_plane():
 
 
 def test_cpu_path_is_the_restatement_and_differentiable():
-    from gsvc_amd.loss_utils import ms_ssim_l1, ms_ssim_l1_pair
+    from gsvc_amd.loss_utils import ms_ssim_l1
     H, W, P = 161, 170, 2
     x, y = mr.pictures(H, W, P, 0.1)
     ref_ms, ref_l1 = mr.ms_ssim_l1(x, y)
@@ -62,7 +62,7 @@ def test_cpu_path_is_the_restatement_and_differentiable():
     # the pair form: the two-view frame formed by tensor expressions, gradients to both views
     f = x.float().requires_grad_(True)
     b = torch.flip(x.float(), dims=[2]).requires_grad_(True)
-    ms2, l12, avg = ms_ssim_l1_pair(f, b, y.float())
+    ms2, l12, avg = ms_ssim_l1(f, y.float(), img_b=b)
     assert not avg.requires_grad and torch.equal(avg, x.float())
     assert torch.equal(ms2.detach(), ms.detach()) and torch.equal(l12.detach(), l1.detach())
     (-0.2 * ms2 + 0.8 * l12).backward()

@@ -1,4 +1,4 @@
-"""MS-SSIM as a fitting loss on the GPU: ``ms_ssim_l1`` / ``ms_ssim_l1_pair`` (csrc/msssim_loss.hip) against the float64 restatement of
+"""MS-SSIM as a fitting loss on the GPU: ``ms_ssim_l1``, plain and with ``img_b`` (csrc/msssim_loss.hip), against the float64 restatement of
 tests/_msssim_loss_ref.py, the step with ``distortion = "ms_ssim"``, and tools/gsvc_encode.py --distortion ms_ssim.
 
 Error rule: the kernels' error against float64 is at most TWICE the error of the same function as float32 tensor expressions
@@ -110,13 +110,13 @@ def test_clipped_plane():
 
 @pytest.mark.parametrize("H,W,P", [mr.SHAPES[1], mr.SHAPES[3]], ids=[mr.SHAPE_IDS[1], mr.SHAPE_IDS[3]])
 def test_pair_form_is_the_plain_form_of_the_averaged_frame(H, W, P):
-    from gsvc_amd.loss_utils import ms_ssim_l1_pair
+    from gsvc_amd.loss_utils import ms_ssim_l1
     f, gt, _ = _case(H, W, P, 0.1)
     b = _case(H, W, P, 0.02)[0].roll(3, dims=2)
     avg_t = 0.5 * (f + torch.flip(b, dims=[2]))
     ms, l1, g = _loss_and_grad(avg_t, gt)
     ff, bb = f.clone().requires_grad_(True), b.clone().requires_grad_(True)
-    ms_p, l1_p, avg = ms_ssim_l1_pair(ff, bb, gt)
+    ms_p, l1_p, avg = ms_ssim_l1(ff, gt, img_b=bb)
     assert not avg.requires_grad
     (G_MS * ms_p + G_L1 * l1_p).backward()
     assert _same_bits(avg, avg_t) and _same_bits(ms_p.detach(), ms) and _same_bits(l1_p.detach(), l1)

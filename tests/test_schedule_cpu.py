@@ -73,6 +73,17 @@ def test_a_trainers_context_is_current_inside_its_steps_only(monkeypatch):
     b.close()
 
 
+def test_a_fresh_trainer_has_its_state_declared(monkeypatch):
+    """What tools and the benchmark read of a Trainer exists from its constructor on, and a removed argument is an error."""
+    from gsvc_amd.arguments import ModelParams, OptimizationParams, PipelineParams
+    from gsvc_amd.train import Trainer
+    tr = _trainer(monkeypatch, 0.0, [])
+    assert tr.repeated_steps == 0 and tr.early_steps == 0 and tr.bound_log == [] and tr._last_idx is None
+    with pytest.raises(TypeError):
+        Trainer(tr.pc, tr.dataset, OptimizationParams(), PipelineParams(), ModelParams(), prefetch=False, shard_optimizer=True)
+    tr.close()
+
+
 def test_a_failing_step_restores_the_previous_context(monkeypatch):
     from gsvc_amd import schedule
     default = schedule.step_context

@@ -343,6 +343,40 @@ def test_early_plan_steps_equal_plain_steps(monkeypatch, phase):
         assert off < 5e-3, (n, off)
 
 
+def test_a_step_leaves_no_tensor_in_a_reference_cycle(monkeypatch):
+    """What a step builds dies by reference count when the step returns: with the cycle collector off, three steps (early tail on, the
+    previous output held as a training loop holds it) leave no tensor for the collector to find.  A tensor in a cycle would keep the
+    step's autograd graph, and the memory under it, alive until a collection happens to run."""
+    import gc
+    monkeypatch.setenv("GSVC_EARLY_PLAN", "1")              # a step this small does not take the early path by itself
+    pc, cube, opt, pipe, mp, Trainer = _setup(anchors=3000, H=48, W=64, T=8, seed=2)
+    (opt.full_precision_training_total, opt.quantized_training_total, opt.entropy_constrained_train_total,
+     opt.ste_entropy_constrained_train_total) = 0, 0, 1000, 0
+    opt.start_stat, opt.update_until, opt.pause_densification, opt.update_from = 0, 10 ** 9, 0, 10 ** 9
+    pc.training_setup(opt)
+    tr = Trainer(pc, cube, opt, pipe, mp)
+    out = tr.step(1)                     # first launches, allocator growth, lazy imports
+    gc.collect()
+    was_enabled, flags = gc.isenabled(), gc.get_debug()
+    gc.disable()
+    try:
+        for it in range(2, 5):
+            out = tr.step(it)
+        torch.cuda.synchronize()
+        gc.set_debug(gc.DEBUG_SAVEALL)
+        gc.collect()
+        tensors = [o for o in gc.garbage if isinstance(o, torch.Tensor)]
+        n, shapes = len(tensors), sorted({tuple(t.shape) for t in tensors})[:8]
+        del tensors
+    finally:
+        gc.set_debug(flags)
+        gc.garbage.clear()
+        if was_enabled:
+            gc.enable()
+    assert tr.early_steps == 4 and np.isfinite(float(out.loss))
+    assert n == 0, (n, shapes)
+
+
 def test_rate_on_the_small_work_stream_equals_the_rate_inside_the_generation_pass(monkeypatch):
     """TRAINING_ENTROPY steps with the sampled rate issued behind the rasterizer's launches on a stream of its own
     (gsvc_amd/generate.py finish_deferred_rate: its kernels run under the compositing kernels, forward and backward) against

@@ -1,6 +1,7 @@
 """The Y'CbCr loss domain without a GPU: the references of tests/_yuv_loss_ref.py pinned against the frame oracle of
 tests/_frames_ref.py, the distortion weights, and everything that is refused before a kernel is launched."""
 import ctypes as C
+from types import SimpleNamespace
 
 import numpy as np
 import pytest
@@ -81,6 +82,25 @@ def test_distortion_weights(lam):
         assert w[0] == pytest.approx(3.0 * w[2]) and w[4] == pytest.approx(3.0 * w[6])
 
 
+@pytest.mark.parametrize("domain", ["rgb", "yuv420", "yuv444"])
+def test_interleaved_frame_terms_are_in_the_order_of_the_weights(domain):
+    """A frame's tuple is its L1 terms, then its structural terms; the step interleaves the two frames' tuples.  That list is the one
+    ``distortion_weights`` documents its weights for, name by name."""
+    import re
+
+    from gsvc_amd.loss_utils import StepDistortion
+    from gsvc_amd.yuv_loss import distortion_weights
+    documented = [re.split(r",\s*", m) for m in re.findall(r"``\[([^\]]+)\]``", distortion_weights.__doc__)]
+    assert [len(d) for d in documented] == [4, 8]
+    names = documented[0] if domain == "rgb" else documented[1]
+    per_frame = ("l1_{}", "ssim_{}") if domain == "rgb" else ("l1_y{}", "l1_c{}", "ssim_y{}", "ssim_c{}")
+    value = {n: 1.0 + 0.25 * k for k, n in enumerate(sorted(names))}          # a distinct constant per term
+    frames = [tuple(value[n.format(k)] for n in per_frame) for k in (1, 2)]
+    terms = StepDistortion.image_terms(*frames)
+    assert terms == [value[n] for n in names]
+    assert len(terms) == len(distortion_weights(domain, 0.2)[0])
+
+
 def test_default_domain_is_rgb():
     from gsvc_amd.arguments import OptimizationParams, cfg_20240919
     assert OptimizationParams().loss_domain == "rgb"
@@ -127,6 +147,55 @@ def test_yuv444_on_a_420_file_is_refused():
         _trainer(cube, "yuv444")
     with pytest.raises(ValueError, match="yuv444.*yuv420p file"):
         target_planes(cube, 0, "yuv444p", "bt709")
+
+
+class _Stub(_Cube):
+    """A dataset that records what is asked of it; every sample it hands out has the value ``mark``."""
+
+    def __init__(self, mark, H, W, fmt=None):
+        super().__init__(H, W, fmt, planes=fmt is not None)
+        self.mark, self.calls = float(mark), []
+        if fmt is not None:
+            self.yuv_planes = self._planes
+
+    def __getitem__(self, i):
+        self.calls.append(("item", i))
+        return SimpleNamespace(image=torch.full((3, self.width, self.height), self.mark))      # (the cubes keep pictures transposed)
+
+    def get_dummy_frame(self, i):
+        self.calls.append(("dummy", i))
+        return SimpleNamespace(image=None)
+
+    def _planes(self, i):
+        self.calls.append(("planes", i))
+        return torch.full((self.height * self.width * 3 // 2,), self.mark)
+
+
+@pytest.mark.parametrize("native", [False, True])
+def test_the_step_distortion_reads_the_dataset_it_is_handed(native):
+    """Built against stub A, it takes frame and target from stub B: the frame without its picture where the targets are the file's
+    own planes, ``B[i]`` otherwise; and it keeps no dataset."""
+    from gsvc_amd.arguments import OptimizationParams
+    from gsvc_amd.frames_out import FrameFormat
+    from gsvc_amd.loss_utils import StepDistortion
+    H, W = 6, 10
+    fmt = FrameFormat("yuv420p") if native else None
+    a, b = _Stub(0.25, H, W, fmt), _Stub(0.75, H, W, fmt)
+    opt = OptimizationParams()
+    opt.loss_domain = "yuv420" if native else "rgb"
+    dist = StepDistortion(opt, a)
+    assert dist.native_planes == native and dist.layout == ("yuv420p" if native else None)
+    a.calls.clear()
+    frame = dist.frame(b, 2)
+    target = dist.target(b, frame, 2, torch.device("cpu"))
+    assert a.calls == []
+    if native:
+        assert b.calls == [("dummy", 2), ("planes", 2)]
+        assert [tuple(t.shape) for t in target] == [(1, H, W), (2, H // 2, W // 2)] and all(bool((t == b.mark).all()) for t in target)
+    else:
+        assert b.calls == [("item", 2)]
+        assert tuple(target.shape) == (3, H, W) and target.is_contiguous() and bool((target == b.mark).all())
+    assert not any(isinstance(v, _Cube) for v in vars(dist).values())
 
 
 def test_python_argument_checks():

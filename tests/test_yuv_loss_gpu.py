@@ -309,12 +309,12 @@ def test_step_loss_is_its_terms_and_is_deterministic(clip, monkeypatch):
     losses = []
     for resident in ("u8", "u8", "float"):
         cube, opt, pc, trainer = _fit(clip, "yuv420", resident)
-        assert trainer.loss_domain == "yuv420" and trainer.loss_matrix == "bt709" and trainer._native_planes
+        assert trainer.loss_domain == "yuv420" and trainer.loss_matrix == "bt709" and trainer._distortion.native_planes
         out = trainer.step(1, frame_idx=2)
         torch.cuda.synchronize()
         losses.append(out.loss.clone())
         # by hand: the image terms from the step's own renders and the file's planes, the two regularisers from the step's batch
-        fmt = trainer._loss_fmt
+        fmt = trainer._distortion.fmt
         r1f, r1b, r2f, r2b = out.renders
         with torch.no_grad():
             y1 = yuv_ssim_l1(r1f.rendered_image, r1b.rendered_image, target_planes(cube, 2, fmt.layout, fmt.matrix), fmt)
@@ -407,8 +407,8 @@ def test_domains_on_datasets_without_native_planes(clip, tmp_path):
         configure_fit(mp_, opt, cube, 100, 0.004, 8.0, 2e-5)
         opt.loss_domain = domain
         pc, trainer = new_fit(cube, mp_, opt, pipe, 3000, torch.device("cuda", 0))
-        assert (trainer._native_planes, trainer.loss_matrix) == (native, matrix)
-        layout = trainer._loss_fmt.layout
+        assert (trainer._distortion.native_planes, trainer.loss_matrix) == (native, matrix)
+        layout = trainer._distortion.fmt.layout
         tY, tC = target_planes(cube, 3, layout, matrix)
         if native:
             wY, wC = split_planes(cube.yuv_planes(3), H_, W_, layout)

@@ -80,7 +80,7 @@ def device_kernels(fn):
 
 
 def bench_loss(groups, dev):
-    from gsvc_amd.loss_utils import ms_ssim_l1, ms_ssim_l1_pair
+    from gsvc_amd.loss_utils import ms_ssim_l1
     from tests import _msssim_loss_ref as mr
     sets = max(2, -(-CACHE // (3 * 4 * P * H * W)))
     ys = [mr.pictures(H, W, P, 0.1, seed=k)[1].float().to(dev) for k in range(sets)]
@@ -94,7 +94,7 @@ def bench_loss(groups, dev):
 
     def fused_pair(k):
         i = k % sets
-        ms, l1, _ = ms_ssim_l1_pair(xs[i], bs[i], ys[i])
+        ms, l1, _ = ms_ssim_l1(xs[i], ys[i], img_b=bs[i])
         torch.autograd.grad(G_MS * ms + G_L1 * l1, (xs[i], bs[i]))
 
     def expressions(k):

@@ -193,7 +193,7 @@ def main(argv=None):
                           "anchors": int(pc._anchor.shape[0]), "loss_tail": float(np.mean(losses[-20:])) if losses else None})
     print(json.dumps(log["phases"][-1]), flush=True)
     log["fit_seconds"] = time.perf_counter() - t0
-    log["repeated_steps"] = int(getattr(trainer, "repeated_steps", 0))
+    log["repeated_steps"] = int(trainer.repeated_steps)
     trainer.sync_replicas()          # z-range ownership (GSVC_DP_ZOWN=1): every replica whole before the model is read as a whole
     log["data_parallel"] = {"ranks": world, "backend": torch.distributed.get_backend() if world > 1 else None,
                             "per_anchor_exchange": "z-range ownership" if trainer._zown is not None else ("rows / dense" if world > 1 else None)}
