@@ -120,6 +120,11 @@ class DeformGradsC(C.Structure):
     _fields_ = [("W", C.c_void_p * 5), ("b", C.c_void_p * 5)]
 
 
+class GrainParamsC(C.Structure):
+    """gsvc_grain_params: the seed, the strengths [3][17] and the taps of gsvc_grain_apply (gsvc_amd/grain.py, GrainParams)."""
+    _fields_ = [("seed", C.c_uint64), ("scale", (C.c_uint16 * 17) * 3), ("kx", C.c_int8 * 3), ("ky", C.c_int8 * 3)]
+
+
 class RasterSizesC(C.Structure):
     _fields_ = [("geom_bytes", C.c_uint64), ("binning_bytes", C.c_uint64), ("image_bytes", C.c_uint64)]
 
@@ -283,6 +288,11 @@ _SIGNATURES = {
     "gsvc_frames_detail": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "gsvc_detail_sample": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, C.c_uint32, _vp, _vp,
                                      _vp]),
+    # film grain (csrc/grain.hip): synthesis in place on delivered frames, and the encoder's flat-block statistics
+    "gsvc_grain_apply": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(GrainParamsC),
+                                   C.POINTER(C.c_int64), _vp]),
+    "gsvc_grain_stats": (C.c_int, [_vp, _i64, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp,
+                                   _vp]),
     "gsvc_flow_workspace_bytes": (_i64, [C.c_int32] * 5),
     "gsvc_flow_estimate": (C.c_int, [_vp, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _vp,
                                      _vp, _vp]),

@@ -16,6 +16,9 @@ VERSION is refused.  Sections of version 1:
     SLAB   per z-slab the feature, scaling and offsets streams, each behind a uint64 length
     PHSH   optional: the name of the FrameFormat the hashes were taken in (+ matrix, range, rounding) and uint64 [frames, 3] picture
            hashes (``metrics.picture_hash``: include/gsvc_hip.h, gsvc_picture_hash)
+    GRAN   optional: the film-grain parameters (``grain.GrainParams.pack``, 122 bytes) a decoder synthesises grain from on the delivered
+           frames, AFTER their picture hashes are taken: PHSH stays the hash of the ungrained picture.  A
+           decoder that does not know the tag skips it and delivers the ungrained pictures.
 
 A clip of several groups of pictures is a sequence file of such file images: gsvc_amd/sequence.py.
 
@@ -34,7 +37,7 @@ MAGIC = b"GSVC"
 VERSION = 1
 _PREFIX = struct.Struct("<4sHH")           # magic, version, number of sections
 _ENTRY = struct.Struct("<4sQI")            # tag, payload length, CRC-32 of the payload
-KNOWN_TAGS = (b"HEAD", b"MLPS", b"ANCH", b"MASK", b"HASH", b"SLAB", b"PHSH")
+KNOWN_TAGS = (b"HEAD", b"MLPS", b"ANCH", b"MASK", b"HASH", b"SLAB", b"PHSH", b"GRAN")
 REQUIRED_TAGS = KNOWN_TAGS[:6]
 
 
@@ -281,8 +284,9 @@ _HEAD_FIELDS = ("W", "H", "frames", "fps_num", "fps_den", "scale", "x_min", "y_m
 # ----------------------------------------------------------------------------------------------------------------------------
 # the file
 # ----------------------------------------------------------------------------------------------------------------------------
-def bitstream_bytes(pc, pack, cube_geometry: CubeGeometry, mlp_bytes: bytes, hashes=None) -> bytes:
-    """The bytes ``write_bitstream`` writes.  ``hashes``: None, or ``(FrameFormat, uint64 / int64 [frames, 3])``."""
+def bitstream_bytes(pc, pack, cube_geometry: CubeGeometry, mlp_bytes: bytes, hashes=None, grain=None) -> bytes:
+    """The bytes ``write_bitstream`` writes.  ``hashes``: None, or ``(FrameFormat, uint64 / int64 [frames, 3])``; ``grain``: None, or
+    the ``grain.GrainParams`` of section GRAN."""
     from . import anchor_codec
     head = make_header(pc, pack, cube_geometry)
     for name in ("prob_masks", "prob_hash"):
@@ -293,6 +297,8 @@ def bitstream_bytes(pc, pack, cube_geometry: CubeGeometry, mlp_bytes: bytes, has
                 (b"HASH", pack.hash), (b"SLAB", _pack_slabs(pack))]
     if hashes is not None:
         sections.append((b"PHSH", _pack_hashes(*hashes)))
+    if grain is not None:
+        sections.append((b"GRAN", grain.pack()))
     return pack_sections(sections)
 
 
@@ -313,6 +319,15 @@ def with_hashes(blob: bytes, fmt, hashes) -> bytes:
     return pack_sections(sections)
 
 
+def with_grain(blob: bytes, params) -> bytes:
+    """The bytes of a file with its GRAN section set to these film-grain parameters (``grain.GrainParams``; None: removed); every other
+    section, known or not, is kept as it is."""
+    sections = [(t, p) for t, p in unpack_sections(blob) if t != b"GRAN"]
+    if params is not None:
+        sections.append((b"GRAN", params.pack()))
+    return pack_sections(sections)
+
+
 @dataclass
 class Bitstream:
     header: dict
@@ -320,6 +335,7 @@ class Bitstream:
     mlp_bytes: bytes
     hash_format: object = None                # FrameFormat of PHSH, or None
     hashes: object = None                     # uint64 [frames, 3], or None
+    grain: object = None                      # grain.GrainParams of GRAN, or None
     section_bytes: dict = field(default_factory=dict)
     file_bytes: int = 0
 
@@ -432,6 +448,9 @@ def parse_bitstream(blob: bytes) -> Bitstream:
         except (ValueError, KeyError) as e:
             raise BitstreamError("PHSH", f"unknown frame format ({e})") from e
         bs.hashes = hashes
+    if b"GRAN" in found:
+        from .grain import GrainParams
+        bs.grain = GrainParams.unpack(found[b"GRAN"])
     return bs
 
 
@@ -463,22 +482,34 @@ def _same_format(a, b) -> bool:
     return (a.layout, a.depth, a.matrix, a.range, a.rounding_used) == (b.layout, b.depth, b.matrix, b.range, b.rounding_used)
 
 
-def hashed_frames(frames, pc, pipe, bg, H: int, W: int, fmt, batch: int, hashes_out):
+def hashed_frames(frames, pc, pipe, bg, H: int, W: int, fmt, batch: int, hashes_out, grain=None, first_frame: int = 0):
     """``render_frames_u8(..., to_host=True)`` with the picture hash of every batch taken ON THE DEVICE, before the host copy: yields the
-    frames as host tensors and appends one int64 ``[n, 3]`` device tensor per batch to ``hashes_out`` (None: no hashes are taken)."""
+    frames as host tensors and appends one int64 ``[n, 3]`` device tensor per batch to ``hashes_out`` (None: no hashes are taken).
+    ``grain`` (``grain.GrainParams``): film grain is added to every batch behind its hashes; ``first_frame``: the index of ``frames[0]``
+    in the whole clip."""
     from .frames_out import render_frames_u8
     from .metrics import picture_hash
     hook = None if hashes_out is None else (lambda rows: hashes_out.append(picture_hash(rows, H, W, fmt)))
-    return render_frames_u8(frames, pc, pipe, bg, fmt=fmt, batch=batch, to_host=True, on_device_batch=hook)
+    return render_frames_u8(frames, pc, pipe, bg, fmt=fmt, batch=batch, to_host=True, on_device_batch=hook, grain=grain,
+                            first_frame=first_frame)
 
 
-def decode_video(bitstream_or_path, sink, fmt=None, batch: int = 8, verify: bool = True, strict: bool = False, device="cuda") -> dict:
+def grain_to_apply(bs, fmt, film_grain: bool):
+    """The ``GrainParams`` a decode of ``bs`` into ``fmt`` applies: the file's, unless it has none, ``film_grain`` is off or ``fmt`` is
+    ``rgb24`` (grain lives in the delivered Y'CbCr domain)."""
+    return bs.grain if film_grain and bs.grain is not None and fmt.layout != "rgb24" else None
+
+
+def decode_video(bitstream_or_path, sink, fmt=None, batch: int = 8, verify: bool = True, strict: bool = False, device="cuda",
+                 film_grain: bool = True) -> dict:
     """Decode a bitstream file to frames of ``fmt`` (default: the file's PHSH format, else yuv420p) into ``sink`` (``write`` / ``close``:
     ``frames_out.open_sink``, ``NullSink``).  With ``verify`` the picture hash of every frame is taken on the device before the host
     copy and, where the file carries PHSH in the same format, compared.  Returns {"frames", "bytes", "seconds", "fps", "format",
     "hashes" (uint64 [frames, 3], with ``verify``), "verified" (bool), "frames_verified", "frames_mismatched", "mismatched" (indices),
-    "verify_skipped" (why nothing was compared, or None)}.  ``strict``: a mismatch raises ``BitstreamError`` (after the frames were
-    written), and so does a file without comparable hashes."""
+    "verify_skipped" (why nothing was compared, or None), "film_grain" (whether grain was added)}.  ``strict``: a mismatch raises
+    ``BitstreamError`` (after the frames were written), and so does a file without comparable hashes.  ``film_grain``: a file with a GRAN
+    section has its grain synthesised on the delivered frames (``grain.apply_grain``) behind the picture hashes, which stay those of
+    the ungrained pictures; False, a file without GRAN or an ``rgb24`` decode deliver the pictures as they are."""
     import torch
 
     from .frames_out import FrameFormat, write_frames
@@ -488,9 +519,11 @@ def decode_video(bitstream_or_path, sink, fmt=None, batch: int = 8, verify: bool
     pc, frames, pipe, bg = bs.build_model(device)
     H, W = bs.header["H"], bs.header["W"]
     per_batch = [] if verify else None
+    grain = grain_to_apply(bs, fmt, film_grain)
     with torch.no_grad():
-        res = write_frames(hashed_frames(frames, pc, pipe, bg, H, W, fmt, int(batch), per_batch), sink)
+        res = write_frames(hashed_frames(frames, pc, pipe, bg, H, W, fmt, int(batch), per_batch, grain=grain), sink)
     res["format"] = fmt.name
+    res["film_grain"] = grain is not None
     res.update(verified=False, frames_verified=0, frames_mismatched=0, mismatched=[], verify_skipped=None)
     if not verify:
         res["verify_skipped"] = "verification was turned off"

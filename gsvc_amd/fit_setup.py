@@ -64,17 +64,56 @@ def new_fit(cube, mp_, opt, pipe, anchors: int, device, init: str = "uniform", i
     return pc, trainer
 
 
+def grain_statistics(bs, source_frames, H: int, W: int, fmt, device, batch: int = 8, flat_threshold=None, max_residual=None):
+    """The film-grain statistics of a file image against its source: ``bs`` (a parsed ``Bitstream``) is decoded into ``fmt``, the SOURCE's
+    own format, batch by batch, each batch's ``grain.grain_stats`` against the source's codes (``source_frames``: the host array
+    ``[T, frame_bytes]`` of ``frames_in.open_video``, uploaded a batch at a time) is taken on the device, and the batches are summed on
+    the host as Python ints -> nested lists ``[3][16][6]``.  ``flat_threshold``, ``max_residual``: the two rejection thresholds of
+    ``grain.grain_stats`` (None: its defaults, which are starting values)."""
+    from .frames_out import render_frames_u8
+    from .grain import BINS, DEFAULT_FLAT_THRESHOLD, DEFAULT_MAX_RESIDUAL, grain_stats
+    flat = DEFAULT_FLAT_THRESHOLD if flat_threshold is None else int(flat_threshold)
+    worst = DEFAULT_MAX_RESIDUAL if max_residual is None else int(max_residual)
+    total = [[[0] * 6 for _ in range(BINS)] for _ in range(3)]
+    pc, cams, pipe, bg = bs.build_model(device)
+    at = [0]
+
+    def take(rows):
+        n = int(rows.shape[0])
+        src = torch.from_numpy(np.ascontiguousarray(source_frames[at[0]:at[0] + n])).to(rows.device)
+        part = grain_stats(src, rows, H, W, fmt, flat_threshold=flat, max_residual=worst).cpu().tolist()
+        for p in range(3):
+            for b in range(BINS):
+                for j in range(6):
+                    total[p][b][j] += int(part[p][b][j])
+        at[0] += n
+
+    with torch.no_grad():
+        for _ in render_frames_u8(cams, pc, pipe, bg, fmt=fmt, batch=int(batch), to_host=False, on_device_batch=take):
+            pass
+    if at[0] != int(source_frames.shape[0]):
+        raise ValueError(f"grain_statistics: the file decodes to {at[0]} frames, the source has {int(source_frames.shape[0])}")
+    return total
+
+
 def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float = 0.004, anchors: int = 100_000, slab_frames: float = 16.0,
                densify_grad_threshold=None, estimate_flow: bool = False, flow_dir=None, video_size=(None, None), video_format=None,
                hash_format=None, loss_domain: str = "rgb", init: str = "uniform", init_cell: int = 8, init_mix: float = 0.25,
-               distortion: str = "ssim"):
+               distortion: str = "ssim", film_grain: bool = False, grain_gain: float = 1.0, grain_seed=None,
+               grain_flat_threshold=None, grain_max_residual=None):
     """One group of pictures of a video file -> ``(the bytes of a complete GSVC file, log)``: what tools/gsvc_encode.py does with a whole
     clip, for the frames ``frame_range = (first, stop)`` of it (None: all).  VideoFileCube (optionally with the flow estimated from the
     frames) -> the fit -> ``conduct_stream_encoding`` with 8-bit MLPs -> the file image; that image is then decoded into a null sink by
     the function, batch size and format the decoder will use (``decode_video``), which yields the picture hashes it is given as its PHSH
     section.  The trainer, the cube and the model are released before this returns.  ``loss_domain``: where the fit takes its
     distortion (``OptimizationParams.loss_domain``; the bitstream and the decoder are the same for every domain); ``distortion``: its
-    structural term, "ssim" or "ms_ssim" (``OptimizationParams.distortion``).  ``init``,
+    structural term, "ssim" or "ms_ssim" (``OptimizationParams.distortion``).  ``film_grain``: after the verification decode the file
+    image is decoded once more, into the SOURCE's own format, and the flat-block statistics of the source's codes against it
+    (``grain_statistics``) are fitted to film-grain parameters (``grain.fit_grain`` with ``grain_gain``; ``grain_seed`` None: a seed
+    derived from the file image; ``grain_flat_threshold``, ``grain_max_residual`` None: the defaults of ``grain.grain_stats``), which the
+    file carries as its GRAN section; the picture hashes stay those of the ungrained
+    pictures, and an ``rgb24`` source is a ``ValueError`` before the fit starts.  The log then has "grain": {"seed", "scale", "kx", "ky",
+    "source", "blocks", "gain"}.  ``init``,
     ``init_cell``, ``init_mix``: where the fit's first anchors come from (``new_fit``; anchors are coded wherever they are).  ``log``:
     {"W", "H", "frames", "steps", "init", ("init_cell", "init_mix": with init="detail" only), "anchors_initial": the anchors after the
     voxel merge of ``create_from_points``, "loss_domain", "loss_matrix", "distortion", "anchors_coded", "fit_seconds", "hash_format",
@@ -92,6 +131,9 @@ def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float 
     mp_, opt, pipe = cfg_20240919()
     cube = VideoFileCube(video, optical_flow_dir=flow_dir, W=video_size[0], H=video_size[1], fmt=video_format, device=device,
                          frame_range=frame_range)
+    if film_grain and cube.fmt.layout == "rgb24":
+        raise ValueError("encode_gop: film grain is measured and synthesised in the delivered Y'CbCr domain; an rgb24 source has none")
+    source_fmt = cube.fmt
     log = {"W": cube.width, "H": cube.height, "frames": cube.len_z_frames, "steps": int(steps)}
     geometry_source = cube
     if estimate_flow:
@@ -135,5 +177,23 @@ def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float 
     gc.collect()
     torch.cuda.empty_cache()
     log["hash_format"], log["verify_decode_fps"] = fmt.name, res["fps"]
+    if film_grain:
+        import hashlib
+
+        from .bitstream import with_grain
+        from .frames_in import open_video
+        from .grain import blocks_used, fit_grain
+        _, source = open_video(video, video_size[0], video_size[1], video_format)
+        if frame_range is not None:
+            source = source[int(frame_range[0]):int(frame_range[1])]
+        stats = grain_statistics(parse_bitstream(blob), source, log["H"], log["W"], source_fmt, device, flat_threshold=grain_flat_threshold,
+                                 max_residual=grain_max_residual)
+        seed = int.from_bytes(hashlib.sha256(blob).digest()[:8], "little") if grain_seed is None else int(grain_seed)
+        params = fit_grain(stats, seed, gain=float(grain_gain), source=source_fmt)
+        blob = with_grain(blob, params)
+        log["grain"] = dict(params.summary(), blocks=blocks_used(stats), gain=float(grain_gain))
+        del source
+        gc.collect()
+        torch.cuda.empty_cache()
     log["sections"] = {t.decode("ascii"): len(p) for t, p in unpack_sections(blob)}
     return blob, log

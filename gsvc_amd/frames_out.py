@@ -190,7 +190,7 @@ def delivered_images(images, fmt: FrameFormat = FrameFormat(), chroma: str = "bi
 
 
 def render_frames_u8(frames, pc, pipe, bg_color, fmt: FrameFormat = FrameFormat(), batch: int = 8, to_host: bool = True,
-                     scaling_modifier=1.0, mode=None, on_device_batch=None):
+                     scaling_modifier=1.0, mode=None, on_device_batch=None, grain=None, first_frame: int = 0):
     """The decoder's render loop with frames of bytes as output (8-bit samples, or little-endian 16-bit samples for a deep ``fmt``): a
     generator over ``render_frames`` that converts each render batch with one
     launch and yields one flat uint8 frame (``frame_bytes`` long; ``planes`` splits it) per video frame, in order.
@@ -202,7 +202,11 @@ def render_frames_u8(frames, pc, pipe, bg_color, fmt: FrameFormat = FrameFormat(
     ``to_host=False``: yields device tensors, rows of a per-batch tensor that is never written again.
     ``on_device_batch``: called with every batch's converted frames, uint8 ``[n, frame_bytes]`` in device memory, on the current stream
     before they are yielded or copied to the host (``bitstream.decode_video`` takes their picture hashes there); what it launches on
-    that stream is ordered before the buffer is written again."""
+    that stream is ordered before the buffer is written again.
+    ``grain`` (``grain.GrainParams``; YUV formats only): film grain is added to every batch in place on the device
+    (``grain.apply_grain``), behind ``on_device_batch`` — the hook sees the ungrained pictures — and before the batch is yielded or
+    copied; ``first_frame`` is the index of ``frames[0]`` in the whole clip, which the grain of a frame is a function of.  Without
+    ``grain`` the launches and events are what they were."""
     import torch
 
     from .generate import GenerateMode
@@ -215,6 +219,10 @@ def render_frames_u8(frames, pc, pipe, bg_color, fmt: FrameFormat = FrameFormat(
     batch = int(batch)
     if batch < 1:
         raise ValueError("render_frames_u8: batch must be at least 1")
+    if grain is not None:
+        from .grain import apply_grain
+        if fmt.layout == "rgb24":
+            raise ValueError("render_frames_u8: rgb24 frames take no film grain (it lives in the delivered Y'CbCr domain)")
     source = render_frames(frames, pc, pipe, bg_color, scaling_modifier=scaling_modifier, mode=mode, batch=batch)
     dev = pc._anchor.device
     ring = None           # to_host: two (device buffer, pinned buffer, copied event)
@@ -227,6 +235,8 @@ def render_frames_u8(frames, pc, pipe, bg_color, fmt: FrameFormat = FrameFormat(
             rows = frames_to_u8(images, fmt)
             if on_device_batch is not None:
                 on_device_batch(rows)
+            if grain is not None:
+                apply_grain(rows, images[0].shape[1], images[0].shape[2], fmt, grain, first_frame=int(first_frame) + i)
             yield from rows.unbind(0)
             continue
         if ring is None:
@@ -240,9 +250,15 @@ def render_frames_u8(frames, pc, pipe, bg_color, fmt: FrameFormat = FrameFormat(
             cur.wait_event(copied)              # the copy of batch j - 2 out of this device buffer
         frames_to_u8(images, fmt, out=on_dev[:n])
         converted = torch.cuda.Event()
-        converted.record(cur)
-        if on_device_batch is not None:
-            on_device_batch(on_dev[:n])     # (behind the event: the copy does not wait for it)
+        if grain is None:
+            converted.record(cur)
+            if on_device_batch is not None:
+                on_device_batch(on_dev[:n])     # (behind the event: the copy does not wait for it)
+        else:                                   # the hook reads the ungrained pictures, the copy takes the grained ones
+            if on_device_batch is not None:
+                on_device_batch(on_dev[:n])
+            apply_grain(on_dev[:n], images[0].shape[1], images[0].shape[2], fmt, grain, first_frame=int(first_frame) + i)
+            converted.record(cur)
         with torch.cuda.stream(copy_stream):
             copy_stream.wait_event(converted)
             on_host[:n].copy_(on_dev[:n], non_blocking=True)

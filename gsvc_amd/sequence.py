@@ -23,8 +23,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .bitstream import (_ENTRY, _PREFIX, MAGIC, VERSION, Bitstream, BitstreamError, CubeGeometry, _same_format, hashed_frames, pack_fields,
-                        parse_bitstream, unpack_fields)
+from .bitstream import (_ENTRY, _PREFIX, MAGIC, VERSION, Bitstream, BitstreamError, CubeGeometry, _same_format, grain_to_apply, hashed_frames,
+                        pack_fields, parse_bitstream, unpack_fields)
 
 SEQ_MAGIC = b"GSVS"
 SEQ_VERSION = 1
@@ -212,14 +212,18 @@ def open_sequence(path) -> Sequence:
                     gops=list(zip(firsts, counts)), cuts=[int(c) for c in cuts], file_bytes=size, _entries=entries)
 
 
-def decode_sequence(path_or_seq, sink, fmt=None, batch: int = 8, verify: bool = True, strict: bool = False, device="cuda", frames=None) -> dict:
+def decode_sequence(path_or_seq, sink, fmt=None, batch: int = 8, verify: bool = True, strict: bool = False, device="cuda", frames=None,
+                    film_grain: bool = True) -> dict:
     """``bitstream.decode_video`` of a sequence file, GOP by GOP into the ONE ``sink``: a GOP's bytes are read, its model built, its
     frames rendered, hashed on the device, compared with the GOP's PHSH and written; the model is dropped before the next GOP is
     built, so the peak device memory is one GOP's.  ``frames=(a, b)``: only the GOPs that overlap ``[a, b)`` are read and built and,
     within them, only those frames are compared and written; they are rendered in the render batches of a decode of the whole GOP (up
     to ``batch - 1`` frames more on either side), so that a frame has the bits it has there.  Returns the keys of ``decode_video`` with
     ``mismatched`` as indices into the whole sequence and ``hashes`` of the frames decoded, plus ``"gops"``: per GOP decoded {"gop",
-    "first", "frames" (of the GOP), "decoded", "rendered", "bytes", "seconds", "frames_verified"}.  ``strict`` as in ``decode_video``."""
+    "first", "frames" (of the GOP), "decoded", "rendered", "bytes", "seconds", "frames_verified", "film_grain"}.  ``strict`` as in
+    ``decode_video``.  ``film_grain``: a GOP with a GRAN section has ITS grain synthesised on its frames (behind the picture hashes), every
+    frame under its index in the WHOLE clip, so that ``frames=(a, b)`` yields the bytes the same frames have in a full decode;
+    ``"film_grain"`` of the result says whether any GOP decoded had grain added."""
     import gc
 
     import torch
@@ -248,8 +252,10 @@ def decode_sequence(path_or_seq, sink, fmt=None, batch: int = 8, verify: bool = 
             r0, r1 = lo // step * step, min(-(-hi // step) * step, count)
             pc, cams, pipe, bg = bs.build_model(device)
             per_batch = [] if verify else None
+            grain = grain_to_apply(bs, used, film_grain)
             with torch.no_grad():
-                for j, picture in enumerate(hashed_frames(cams[r0:r1], pc, pipe, bg, seq.H, seq.W, used, step, per_batch)):
+                for j, picture in enumerate(hashed_frames(cams[r0:r1], pc, pipe, bg, seq.H, seq.W, used, step, per_batch, grain=grain,
+                                                          first_frame=first + r0)):
                     if lo <= r0 + j < hi:
                         yield picture
             ok = 0
@@ -272,12 +278,13 @@ def decode_sequence(path_or_seq, sink, fmt=None, batch: int = 8, verify: bool = 
             del pc, cams, pipe, bg, bs, per_batch
             gc.collect()
             state["gops"].append({"gop": k, "first": first, "frames": count, "decoded": hi - lo, "rendered": r1 - r0, "bytes": seq.gop_bytes(k),
-                                  "seconds": time.perf_counter() - t0, "frames_verified": ok})
+                                  "seconds": time.perf_counter() - t0, "frames_verified": ok, "film_grain": grain is not None})
 
     res = write_frames(run(), sink)
     used = state["fmt"]
     res["format"] = used.name
-    res.update(verified=False, frames_verified=0, frames_mismatched=0, mismatched=[], verify_skipped=None, gops=state["gops"])
+    res.update(verified=False, frames_verified=0, frames_mismatched=0, mismatched=[], verify_skipped=None, gops=state["gops"],
+               film_grain=any(g["film_grain"] for g in state["gops"]))
     if not verify:
         res["verify_skipped"] = "verification was turned off"
     else:

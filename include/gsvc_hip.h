@@ -1160,6 +1160,52 @@ int gsvc_detail_sample(const int64_t *cdf, int64_t cells, int32_t T, int32_t H, 
                        uint32_t mix24, float *points, int32_t *cell_of, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * [INTERNAL] Film grain (csrc/grain.hip, gsvc_amd/grain.py): grain synthesised on delivered Y'CbCr frames from a
+ * few dozen bytes of parameters (section GRAN of a bitstream file), and the statistics an encoder fits those parameters to.  Integers
+ * only; gsvc_amd/grain.py's docstring states the synthesis sample by sample, tests/_grain_ref.py restates it in numpy.
+ *
+ * gsvc_grain_apply: adds grain IN PLACE to n (1 .. 16) frames (frame k at frames + k * stride) of GSVC_FRAMES_YUV444P / _YUV420P,
+ * depth 8, 10, 12 or 16.  frame_ids_host: host array of n frame indices in the whole clip, each 0 .. 2^32 - 1 (they travel in the
+ * kernel arguments).  With GOLD = 0x9E3779B97F4A7C15 and mix(z) the splitmix64 finaliser of gsvc_detail_sample, for plane p (0 Y, 1 U,
+ * 2 V) of frame f and the sample (y, x) of the plane's own grid, y and x from -1 to the plane's height / width (the hash is defined
+ * outside the picture: edges have no special case):
+ *     key  = mix(seed + (3 f + p + 1) GOLD)
+ *     h    = mix(key + (((y + 1) << 32) | ((x + 1) >> 1)) GOLD);     w = the upper 32 bits of h if (x + 1) is odd, else the lower
+ *     g    = the sum of the four bytes of w - 510                                       (-510 .. 510, variance 21845)
+ *     t    = kx[p] (g(y, x - 1) + g(y, x + 1)) + 64 g(y, x);     v = ky[p] (t(y - 1, x) + t(y + 1, x)) + 64 t(y, x)
+ *     n    = (v + 2048) >> 12                                                           (arithmetic shift)
+ *     l    = min(m >> (depth - 8), 255), m = the co-located UNGRAINED luma code (4:2:0 chroma: (a + b + c + d + 2) >> 2 of its four)
+ *     s    = (scale[p][i] (16 - r) + scale[p][i + 1] r + 8) >> 4,  i = l >> 4,  r = l & 15
+ *     grain = (n s + 2^(S - 1)) >> S,  S = 24 - depth       (scale: Q16 multipliers of n in 8-bit codes; a deep format gets 2^(depth - 8) times)
+ *     out  = min(max(c + grain, min(lo, c)), max(hi, c))     lo .. hi: LIMITED 16 .. 235 (luma) / 16 .. 240 (chroma) times 2^(depth - 8),
+ *                                                            FULL 0 .. 2^depth - 1: grain never moves a sample out of the nominal range,
+ *                                                            and a sample whose grain is 0 keeps its code
+ * A workgroup owns a 128 x 16 luma tile and the chroma tiles under it and reads nothing outside them: in place is safe.  Bytes of a
+ * frame's row beyond the frame are not touched.  Refused with an error before any launch: a NULL pointer, rgb24 or an unknown layout,
+ * a depth other than 8, 10, 12, 16, an unknown range, n outside 1 .. 16, an odd H or W for 4:2:0, a stride below the frame's bytes
+ * (gsvc_frames_bytes), an odd base or stride for a deep format, a tap outside -32 .. 32, a frame index outside 0 .. 2^32 - 1.
+ *
+ * gsvc_grain_stats: out (uint64 [3, 16, 6], 8-byte aligned; the bits of int64 sums) over the n (1 .. 65535) frame pairs of two buffers, src
+ * the source's codes and dec the decoder's.  Every plane is cut into whole 8 x 8 blocks of its own grid (partial blocks at the right and
+ * bottom edges are skipped).  Per block: r = src - dec; A = the sum of the 112 absolute differences of horizontally and vertically
+ * adjacent dec codes inside the block; bin = min((the sum of the dec LUMA codes of the co-located 8 x 8 region, 16 x 16 for 4:2:0 chroma)
+ * >> (6 or 8) >> (depth - 8), 255) >> 4.  A block with A <= flat_threshold 2^(depth - 8) and every |r| <= max_residual 2^(depth - 8) adds
+ * to out[plane][bin]:  1,  S1 = sum r,  S2 = sum r^2,  S1^2,  Px = sum r(x, y) r(x + 1, y) (56 pairs),  Py = sum r(x, y) r(x, y + 1).
+ * Integer sums (64-bit atomics): the same bits in every run and for every launch shape.  The call zeroes out on the stream.  Refused
+ * before any launch: as gsvc_picture_hash for both buffers, rgb24, a depth other than 8, 10, 12, 16, flat_threshold outside 0 .. 65535,
+ * max_residual outside 0 .. 255.  Neither call synchronises.
+ * ---------------------------------------------------------------------------------------------------- */
+typedef struct {
+    uint64_t seed;
+    uint16_t scale[3][17];        /* per plane, at 8-bit-normalised luma 0, 16, .., 256 */
+    int8_t kx[3], ky[3];          /* per plane, -32 .. 32 (Q6) */
+} gsvc_grain_params;
+int gsvc_grain_apply(uint8_t *frames, int64_t stride, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t depth, int32_t range,
+                     const gsvc_grain_params *params, const int64_t *frame_ids_host, void *stream);
+int gsvc_grain_stats(const uint8_t *src, int64_t src_stride, const uint8_t *dec, int64_t dec_stride, int32_t n, int32_t H, int32_t W,
+                     int32_t layout, int32_t depth, int32_t flat_threshold, int32_t max_residual, uint64_t *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Dense optical flow of adjacent frames (csrc/flow.hip): coarse-to-fine Horn-Schunck with warping.  No weights, stencils only: the
  * same bits in every run, for every batch size and launch geometry.
  *

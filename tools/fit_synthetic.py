@@ -90,6 +90,9 @@ def main(argv=None):
     ap.add_argument("--optical-lambda", type=float, default=None, help="weight of the flow-guided loss (default: the configuration's)")
     ap.add_argument("--video-resident", choices=("float", "u8"), default="float",
                     help="keep the video on the device as float32 pictures, or as the file's bytes (converted one frame per fetch)")
+    ap.add_argument("--film-grain", action="store_true",
+                    help="with a Y'CbCr --video: measure the grain the fit removed against the file's codes and fit film-grain parameters "
+                         "(gsvc_amd/grain.py): log['grain'], and the GRAN section of --write-bitstream")
     ap.add_argument("--distortion", choices=("ssim", "ms_ssim"), default="ssim",
                     help="the structural term of the distortion: single-scale SSIM, or MS-SSIM (rgb domain, sides above 160 pixels)")
     ap.add_argument("--loss-domain", choices=("rgb", "yuv420", "yuv444"), default="rgb",
@@ -105,6 +108,8 @@ def main(argv=None):
         ap.error("--init-cell and --init-mix need --init detail")
     if args.init_mix is not None and not 0.0 <= args.init_mix <= 1.0:
         ap.error("--init-mix must lie in 0 .. 1")
+    if args.film_grain and not args.video:
+        ap.error("--film-grain needs --video (a Y'CbCr file)")
 
     from gsvc_amd.arguments import cfg_20240919
     from gsvc_amd.frame import SyntheticFrameCube
@@ -130,6 +135,8 @@ def main(argv=None):
         vw, vh = (int(v) for v in args.video_size.lower().split("x")) if args.video_size else (None, None)
         vfmt = _frame_format(args.video_format) if args.video_format else None
         cube = VideoFileCube(args.video, optical_flow_dir=args.flow_dir, W=vw, H=vh, fmt=vfmt, device=dev, resident=args.video_resident)
+        if args.film_grain and cube.fmt.layout == "rgb24":
+            raise ValueError("--film-grain: grain is measured in the delivered Y'CbCr domain; an rgb24 --video has none")
         H, W, T = cube.height, cube.width, cube.len_z_frames          # the file says what is fitted
         flow_source = "files" if args.flow_dir is not None else "none"
         if args.flow_dir is None and not args.estimate_flow:
@@ -289,6 +296,22 @@ def main(argv=None):
                 with open(mlp_file, "rb") as f:
                     written = write_bitstream(args.write_bitstream, q, pack_q, CubeGeometry.of(cube, mp_, pipe, bg.tolist()), f.read())
                 log["bitstream_bytes"], log["bitstream_sections"] = int(written["bytes"]), written["sections"]
+            if args.film_grain:
+                from gsvc_amd import grain as G
+                from gsvc_amd.bitstream import CubeGeometry, bitstream_bytes, parse_bitstream, unpack_sections, with_grain
+                from gsvc_amd.fit_setup import grain_statistics
+                from gsvc_amd.frames_in import open_video
+                with open(mlp_file, "rb") as f:
+                    image = bitstream_bytes(q, pack_q, CubeGeometry.of(cube, mp_, pipe, bg.tolist()), f.read())
+                stats = grain_statistics(parse_bitstream(image), open_video(args.video, vw, vh, vfmt)[1], H, W, cube.fmt, dev)
+                grain = G.fit_grain(stats, int.from_bytes(image[-8:], "little"), source=cube.fmt)
+                log["grain"] = dict(grain.summary(), blocks=G.blocks_used(stats))
+                if args.write_bitstream:
+                    image = with_grain(image, grain)
+                    with open(args.write_bitstream, "wb") as f:
+                        f.write(image)
+                    log["bitstream_bytes"] = len(image)
+                    log["bitstream_sections"] = {t.decode("ascii"): len(p) for t, p in unpack_sections(image)}
         lp = None
         if args.lpips_weights:
             from gsvc_amd.lpips import lpips_fn_from

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Decode a bitstream file (tools/gsvc_encode.py; gsvc_amd/bitstream.py) to a video.  The file is all it reads:
 
-    python tools/gsvc_decode.py clip.gsvc -o out.y4m [--format yuv420p10le] [--no-verify | --strict]
+    python tools/gsvc_decode.py clip.gsvc -o out.y4m [--format yuv420p10le] [--no-verify | --strict] [--no-film-grain]
     python tools/gsvc_decode.py long.gsvs -o part.y4m --frames 300:364
 
 The file is a bitstream file (magic GSVC) or a sequence file of several groups of pictures (magic GSVS; gsvc_amd/sequence.py, DESIGN.md
@@ -10,7 +10,9 @@ hold them are read and built.
 
 -o: .y4m / .yuv (yuv420p unless --format says otherwise), .rgb (rgb24), else a directory of PNGs.  The picture hash of every frame is
 taken on the device and, where the file carries hashes of the format decoded to, compared: the JSON line printed says how many frames
-were verified and which did not match.  --strict: exit status 1 on a mismatch, or when nothing could be verified.
+were verified and which did not match.  --strict: exit status 1 on a mismatch, or when nothing could be verified.  A file with
+film-grain parameters (section GRAN) has its grain synthesised on the delivered frames, behind the hashes, which stay those of the
+ungrained pictures; --no-film-grain delivers the pictures as they are.
 """
 import argparse
 import json
@@ -32,6 +34,7 @@ def main(argv=None):
     mode = ap.add_mutually_exclusive_group()
     mode.add_argument("--no-verify", action="store_true", help="do not take picture hashes")
     mode.add_argument("--strict", action="store_true", help="fail when a frame's picture hash differs from the file's, or nothing could be verified")
+    ap.add_argument("--no-film-grain", action="store_true", help="do not synthesise the file's film grain (section GRAN) on the frames")
     args = ap.parse_args(argv)
 
     from gsvc_amd.bitstream import BitstreamError
@@ -65,7 +68,8 @@ def main(argv=None):
         raise SystemExit(f"--frames {args.frames}: not a non-empty range inside the file's {seq.frames} frames")
     sink, fmt = open_sink(args.output, seq.W, seq.H, fps=tuple(seq.fps), fmt=fmt)
     try:
-        res = decode_sequence(seq, sink, fmt=fmt, batch=args.batch, verify=not args.no_verify, strict=args.strict, frames=frames)
+        res = decode_sequence(seq, sink, fmt=fmt, batch=args.batch, verify=not args.no_verify, strict=args.strict, frames=frames,
+                              film_grain=not args.no_film_grain)
     except BitstreamError as e:
         print(f"gsvc_decode: {args.bitstream}: {e}", file=sys.stderr)
         return 1

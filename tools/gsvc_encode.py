@@ -5,13 +5,15 @@ the video in another process, with nothing else:
     python tools/gsvc_encode.py clip.y4m -o clip.gsvc [--steps 2000 --lmbda 0.004 --anchors 100000 --estimate-flow]
                                 [--video-format yuv420p,bt601,full] [--video-size WxH] [--hash-format yuv420p]
                                 [--loss-domain rgb|yuv420|yuv444] [--distortion ssim|ms_ssim] [--init detail [--init-cell 8 --init-mix 0.25]]
+                                [--film-grain [--film-grain-gain 1.0 --film-grain-seed N]]
     python tools/gsvc_decode.py clip.gsvc -o out.y4m --strict
     python tools/gsvc_encode.py long.y4m -o long.gsvs --gop-frames 32 [--scene-cuts --cut-threshold 0.5 --min-gop 4]
 
 VideoFileCube (optionally with the flow estimated from the frames) -> the fit (the schedule and set-up of tools/fit_synthetic.py:
 gsvc_amd/fit_setup.py) -> conduct_stream_encoding with 8-bit MLPs -> the file.  The file is then read back and decoded into a null sink
 by the function, batch size and format the decoder will use (``decode_video``), which yields the picture hashes; the file is rewritten
-with them (section PHSH).  Prints one JSON line: bytes per section, the file's size, and bpp = 8 x FILE SIZE / (H W T).
+with them (section PHSH).  With --film-grain the grain the fit removed is measured against the source and a few dozen bytes of
+parameters are added (section GRAN; gsvc_amd/grain.py): the decoder synthesises grain from them on its frames.  Prints one JSON line: bytes per section, the file's size, and bpp = 8 x FILE SIZE / (H W T).
 
 With --gop-frames the clip is cut into groups of pictures (GOPs) of at most that many frames (gsvc_amd/scene.py, ``plan_gops``; with
 --scene-cuts also where the luma histogram of the frames changes), every GOP is fitted and verified on its own (``fit_setup.encode_gop``;
@@ -66,7 +68,13 @@ def main(argv=None):
     ap.add_argument("--init-cell", type=int, choices=(4, 8, 16), default=None, help="with --init detail: the cell of the detail map in pixels (default 8)")
     ap.add_argument("--init-mix", type=float, default=None, metavar="X",
                     help="with --init detail: the share of the points that is still drawn uniformly, 0 .. 1 (default 0.25)")
+    ap.add_argument("--film-grain", action="store_true",
+                    help="measure the grain the fit removed and ship its parameters (section GRAN); YUV sources only (gsvc_amd/grain.py)")
+    ap.add_argument("--film-grain-gain", type=float, default=None, metavar="X", help="with --film-grain: scale the fitted strengths (default 1.0)")
+    ap.add_argument("--film-grain-seed", type=int, default=None, metavar="N", help="with --film-grain: the 64-bit seed (default: derived from the file)")
     args = ap.parse_args(argv)
+    if not args.film_grain and (args.film_grain_gain is not None or args.film_grain_seed is not None):
+        ap.error("--film-grain-gain and --film-grain-seed need --film-grain")
     if args.init != "detail" and (args.init_cell is not None or args.init_mix is not None):
         ap.error("--init-cell and --init-mix need --init detail")
     if args.init_mix is not None and not 0.0 <= args.init_mix <= 1.0:
@@ -86,6 +94,8 @@ def main(argv=None):
                video_size=(vw, vh), video_format=video_fmt, hash_format=_frame_format(args.hash_format), loss_domain=args.loss_domain,
                distortion=args.distortion, init=args.init, init_cell=8 if args.init_cell is None else args.init_cell,
                init_mix=0.25 if args.init_mix is None else args.init_mix)
+    if args.film_grain:
+        fit.update(film_grain=True, grain_gain=1.0 if args.film_grain_gain is None else args.film_grain_gain, grain_seed=args.film_grain_seed)
     if args.gop_frames is None:
         blob, log = encode_gop(args.video, dev, **fit)
         with open(args.output, "wb") as f:
@@ -114,7 +124,7 @@ def main(argv=None):
         fit_seconds += one["fit_seconds"]
         gops.append({"first": first, "frames": count, "bytes": len(blob), "bpp": 8.0 * len(blob) / (H * W * count),
                      "fit_seconds": one["fit_seconds"], "cut": int(cut), "anchors_initial": one["anchors_initial"], "anchors_coded": one["anchors_coded"],
-                     "sections": one["sections"]})
+                     "sections": one["sections"], **({"grain": one["grain"]} if "grain" in one else {})})
     fps = header.get("fps") or (30, 1)
     write_sequence(args.output, blobs, W, H, fps, flags)
     log = {"output": args.output, "W": W, "H": H, "frames": T, "steps": args.steps, "fit_seconds": fit_seconds,
