@@ -293,6 +293,11 @@ _SIGNATURES = {
                                    C.POINTER(C.c_int64), _vp]),
     "gsvc_grain_stats": (C.c_int, [_vp, _i64, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp,
                                    _vp]),
+    # temporal prefilter (csrc/tfilter.hip): the filter on the codes of a resident clip, and the noise sums of its strength
+    "gsvc_tfilter_frames": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp,
+                                      C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), _vp, _i64,
+                                      _vp]),
+    "gsvc_noise_sums": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "gsvc_flow_workspace_bytes": (_i64, [C.c_int32] * 5),
     "gsvc_flow_estimate": (C.c_int, [_vp, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _vp,
                                      _vp, _vp]),

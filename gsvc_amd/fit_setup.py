@@ -100,7 +100,7 @@ def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float 
                densify_grad_threshold=None, estimate_flow: bool = False, flow_dir=None, video_size=(None, None), video_format=None,
                hash_format=None, loss_domain: str = "rgb", init: str = "uniform", init_cell: int = 8, init_mix: float = 0.25,
                distortion: str = "ssim", film_grain: bool = False, grain_gain: float = 1.0, grain_seed=None,
-               grain_flat_threshold=None, grain_max_residual=None):
+               grain_flat_threshold=None, grain_max_residual=None, denoise=None, denoise_gain: float = 1.0):
     """One group of pictures of a video file -> ``(the bytes of a complete GSVC file, log)``: what tools/gsvc_encode.py does with a whole
     clip, for the frames ``frame_range = (first, stop)`` of it (None: all).  VideoFileCube (optionally with the flow estimated from the
     frames) -> the fit -> ``conduct_stream_encoding`` with 8-bit MLPs -> the file image; that image is then decoded into a null sink by
@@ -113,7 +113,11 @@ def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float 
     derived from the file image; ``grain_flat_threshold``, ``grain_max_residual`` None: the defaults of ``grain.grain_stats``), which the
     file carries as its GRAN section; the picture hashes stay those of the ungrained
     pictures, and an ``rgb24`` source is a ``ValueError`` before the fit starts.  The log then has "grain": {"seed", "scale", "kx", "ky",
-    "source", "blocks", "gain"}.  ``init``,
+    "source", "blocks", "gain"}.  ``denoise``: None (the default: the source as it is), "auto" or a noise sigma in codes: the frames of
+    ``frame_range`` are first put through the motion-compensated temporal prefilter (``tfilter.denoise_frames`` with ``denoise_gain``; one
+    GOP, so nothing is filtered across its ends) and the fit is given the filtered frames; an ``rgb24`` source is a ``ValueError``.  The log
+    then has "denoise": {"sigma", "q", "source", "gain", "psnr_y"}.  With ``film_grain`` as well the grain statistics stay measured
+    against the ORIGINAL source (``video`` is reopened for them), so the grain the prefilter removed is what the decoder puts back.  ``init``,
     ``init_cell``, ``init_mix``: where the fit's first anchors come from (``new_fit``; anchors are coded wherever they are).  ``log``:
     {"W", "H", "frames", "steps", "init", ("init_cell", "init_mix": with init="detail" only), "anchors_initial": the anchors after the
     voxel merge of ``create_from_points``, "loss_domain", "loss_matrix", "distortion", "anchors_coded", "fit_seconds", "hash_format",
@@ -129,12 +133,33 @@ def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float 
     from .frames_out import FrameFormat
     from .stream_codec import conduct_stream_encoding
     mp_, opt, pipe = cfg_20240919()
+    filtered, denoise_log = None, None
+    if denoise is not None:
+        from .frames_in import open_video
+        from .tfilter import denoise_range
+        hdr, source = open_video(video, video_size[0], video_size[1], video_format)
+        if hdr["fmt"].layout == "rgb24":
+            raise ValueError("encode_gop: the temporal prefilter works on Y'CbCr codes; an rgb24 source has none")
+        if frame_range is not None:
+            try:
+                first, stop = (int(v) for v in frame_range)
+            except (TypeError, ValueError):
+                raise ValueError(f"encode_gop: frame_range must be (first, stop) (got {frame_range!r})") from None
+            if not 0 <= first < stop <= int(source.shape[0]):          # (what VideoFileCube refuses, before anything is filtered)
+                raise ValueError(f"encode_gop: frame_range ({first}, {stop}) is not a non-empty range inside the {int(source.shape[0])} "
+                                 f"frames of {video}")
+            source = source[first:stop]
+        filtered, denoise_log = denoise_range(source, int(hdr["H"]), int(hdr["W"]), hdr["fmt"], device, sigma=denoise, gain=float(denoise_gain))
+        del source
     cube = VideoFileCube(video, optical_flow_dir=flow_dir, W=video_size[0], H=video_size[1], fmt=video_format, device=device,
-                         frame_range=frame_range)
+                         frame_range=frame_range, frames=filtered)
+    del filtered
     if film_grain and cube.fmt.layout == "rgb24":
         raise ValueError("encode_gop: film grain is measured and synthesised in the delivered Y'CbCr domain; an rgb24 source has none")
     source_fmt = cube.fmt
     log = {"W": cube.width, "H": cube.height, "frames": cube.len_z_frames, "steps": int(steps)}
+    if denoise_log is not None:
+        log["denoise"] = denoise_log
     geometry_source = cube
     if estimate_flow:
         from .flow import EstimatedFlowCube

@@ -146,10 +146,13 @@ class VideoFileCube:
     ``frame_range=(first, stop)``: the cube of the file's frames ``first .. stop - 1`` alone (one group of pictures of a long clip,
     gsvc_amd/scene.py): only those frames are uploaded, frame i of the cube is file frame ``first + i``, and ``len``, ``scale``,
     ``x_min``, ``y_min`` and ``z_min`` are those of a clip of ``stop - first`` frames; the flow files used are those of the pairs
-    inside the range.  None: all frames."""
+    inside the range.  None: all frames.
+
+    ``frames``: a uint8 array ``[len, frame_bytes]`` that stands in for the payload of the file's frames (those of ``frame_range``): a
+    prefiltered source (gsvc_amd/tfilter.py).  The file still supplies size, format and count.  None: the file's own."""
 
     def __init__(self, path, optical_flow_dir=None, W: int | None = None, H: int | None = None, fmt: FrameFormat | None = None,
-                 chroma: str = "bilinear", device="cuda", resident: str = "float", frame_range=None):
+                 chroma: str = "bilinear", device="cuda", resident: str = "float", frame_range=None, frames=None):
         import pathlib
 
         import torch
@@ -157,6 +160,7 @@ class VideoFileCube:
             raise ValueError(f"VideoFileCube: resident must be 'float' or 'u8' (got {resident!r})")
         _chroma_id(chroma)
         self.path, self.chroma, self.resident = str(path), chroma, resident
+        given = frames
         self.header, frames = open_video(path, W, H, fmt)
         self.fmt = self.header["fmt"]
         self.height, self.width, self.len = int(self.header["H"]), int(self.header["W"]), int(frames.shape[0])
@@ -173,6 +177,12 @@ class VideoFileCube:
                                  f"{self.path}")
             self.frame_range = (first, stop)
             frames, self.len = frames[first:stop], stop - first
+        if given is not None:
+            given = np.asarray(given)
+            if given.dtype != np.uint8 or given.shape != (self.len, int(self.header["frame_bytes"])):
+                raise ValueError(f"VideoFileCube: frames must be uint8 [{self.len}, {int(self.header['frame_bytes'])}] (got {given.dtype} "
+                                 f"{given.shape})")
+            frames = given
         self.scale = max(self.height, self.width, self.len) / 2
         self.x_min = -self.width / 2 / self.scale
         self.y_min = -self.height / 2 / self.scale

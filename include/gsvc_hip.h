@@ -1206,6 +1206,47 @@ int gsvc_grain_stats(const uint8_t *src, int64_t src_stride, const uint8_t *dec,
                      int32_t layout, int32_t depth, int32_t flat_threshold, int32_t max_residual, uint64_t *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * [INTERNAL] Motion-compensated temporal prefilter of source frames (csrc/tfilter.hip, gsvc_amd/tfilter.py).  Integers
+ * only; gsvc_amd/tfilter.py's docstring states the filter sample by sample, tests/_tfilter_ref.py restates it in numpy.
+ *
+ * gsvc_tfilter_frames: filters the n (1 .. 16) target frames first .. first + n - 1 of a resident clip of T (1 .. 65535) frames (frame t
+ * at frames + t * stride) of GSVC_FRAMES_YUV444P / _YUV420P, depth 8, 10, 12 or 16, H, W >= 8, into out (target k at out + k *
+ * out_stride; it may not overlap the clip).  flows: float32 [n, 4, 2, H, W] on the device; slot j of target k holds the flow from frame
+ * t = first + k to frame t + d, d = (-2, -1, +1, +2)[j], as gsvc_flow_estimate writes it.  A slot whose t + d lies outside 0 .. T - 1 is
+ * never read and its neighbour contributes nothing.  With // the floor division, per neighbour d:
+ *     mv    = clamp(rint(4 f), -32768, 32767) per component (the float32 product, rounded half to even): quarter luma pels
+ *             (flows should be finite: +-inf clamps like any large value and a NaN component is read as -32768 — memory-safe, as every
+ *             position is clamped, but meaningless; nothing checks them)
+ *     pred  : for an h x w plane with `unit` sub-positions per sample, px = clamp(unit x + mvx, 0, unit (w - 1)), x0 = min(px // unit,
+ *             w - 2), fx = px - unit x0 (py, y0, fy likewise), and over the codes a of frame t + d
+ *             pred = ((unit - fx)(unit - fy) a00 + fx (unit - fy) a01 + (unit - fx) fy a10 + fx fy a11 + unit^2 / 2) // unit^2
+ *             luma and 4:4:4 chroma: unit 4, the pixel's own mv; 4:2:0 chroma: unit 8, the mv of luma pixel (2y, 2x)
+ *     i_b   = min(63, 2048 SSE // (n_B q[0]^2)), SSE = the sum of (Y_t - pred)^2 over the n_B pixels of the sample's 8 x 8 luma block
+ *             (partial blocks at the right and bottom edges count the pixels they have; chroma: the block holding (2y, 2x), 4:4:4 (y, x))
+ *     i_p   = min(63, 128 |c - pred| // q[p])
+ *     w_d   = (wt[|d| - 1] lut_b[i_b] lut_p[i_p] + 2^15) >> 16
+ *     out   = (256 c + sum_d w_d pred_d + Wt // 2) // Wt,   Wt = 256 + sum_d w_d
+ * q_host (3), wt_host (2), lut_b_host and lut_p_host (64 each) are host arrays that travel in the kernel arguments.  Every sampled
+ * position is clamped into its plane: no flow value makes the kernel read outside a frame.  No atomics, no workspace; the result does
+ * not depend on the launch geometry.  Bytes of an output row beyond the frame are not touched.  Refused with an error before any
+ * launch: a NULL pointer, rgb24 or an unknown layout, a depth other than 8, 10, 12, 16, n outside 1 .. 16, T outside 1 .. 65535,
+ * first < 0 or first + n > T, a side below 8, an odd H or W for 4:2:0, a stride below the frame's bytes (gsvc_frames_bytes), an odd base
+ * or stride for a deep format, flows not 4-byte aligned, an output that overlaps the clip, q outside 1 .. 65535, wt or a table entry
+ * above 256.
+ *
+ * gsvc_noise_sums: out[k, p] (uint64 [n, 3], 8-byte aligned; n 1 .. 16) = over the interior samples (1 <= y <= h - 2, 1 <= x <= w - 2) of
+ * plane p of frame k the sum of
+ *     |c(y-1,x-1) - 2 c(y-1,x) + c(y-1,x+1) - 2 c(y,x-1) + 4 c(y,x) - 2 c(y,x+1) + c(y+1,x-1) - 2 c(y+1,x) + c(y+1,x+1)|
+ * (Immerkaer's noise estimator before its scaling).  Integer sums: the same bits in every run and for every launch shape.  The call
+ * zeroes out on the stream.  Formats and refusals as gsvc_tfilter_frames.  Neither call synchronises.
+ * ---------------------------------------------------------------------------------------------------- */
+int gsvc_tfilter_frames(const uint8_t *frames, int64_t stride, int32_t T, int32_t first, int32_t n, int32_t H, int32_t W, int32_t layout,
+                        int32_t depth, const float *flows, const uint32_t *q_host, const uint32_t *wt_host, const uint16_t *lut_b_host,
+                        const uint16_t *lut_p_host, uint8_t *out, int64_t out_stride, void *stream);
+int gsvc_noise_sums(const uint8_t *frames, int64_t stride, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t depth, uint64_t *out,
+                    void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Dense optical flow of adjacent frames (csrc/flow.hip): coarse-to-fine Horn-Schunck with warping.  No weights, stencils only: the
  * same bits in every run, for every batch size and launch geometry.
  *

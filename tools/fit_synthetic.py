@@ -27,6 +27,9 @@ usage: python tools/fit_synthetic.py [--steps 2000] [--height 1080 --width 1920 
                                      video's analytic flow or a video file's --flow-dir)
        python tools/fit_synthetic.py --init detail [--init-cell 8 --init-mix 0.25] ...      (the first anchors drawn where the luma has detail,
                                      gsvc_amd/detail.py, instead of uniformly in the cube)
+       python tools/fit_synthetic.py --video clip.y4m --denoise auto|SIGMA [--denoise-gain 1.0] ...      (the fit is given the file's motion-
+                                     compensated temporally filtered frames, gsvc_amd/tfilter.py; every metric reported is still taken
+                                     against the UNFILTERED file, and log["denoise"] says so)
 """
 import argparse
 import copy
@@ -50,7 +53,8 @@ def _frame_format(text):
     return FrameFormat.from_name(name, **dict(zip(("matrix", "range"), rest)))
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    from gsvc_amd.tfilter import parse_sigma          # (the one reader of an {auto,SIGMA} option; needs neither torch nor the library)
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--height", type=int, default=1080)
@@ -103,14 +107,26 @@ def main(argv=None):
     ap.add_argument("--init-cell", type=int, choices=(4, 8, 16), default=None, help="with --init detail: the cell of the detail map in pixels (default 8)")
     ap.add_argument("--init-mix", type=float, default=None, metavar="X",
                     help="with --init detail: the share of the points that is still drawn uniformly, 0 .. 1 (default 0.25)")
+    ap.add_argument("--denoise", type=parse_sigma, default=None, metavar="{auto,SIGMA}",
+                    help="with a Y'CbCr --video: fit its motion-compensated temporally filtered frames (gsvc_amd/tfilter.py; 'auto' estimates "
+                         "the noise, a number gives its sigma in codes).  Every metric is still reported against the UNFILTERED file")
+    ap.add_argument("--denoise-gain", type=float, default=None, metavar="X", help="with --denoise: scale the filter's strength (default 1.0)")
     args = ap.parse_args(argv)
+    if args.denoise is not None and not args.video:
+        ap.error("--denoise needs --video (a Y'CbCr file)")
+    if args.denoise is None and args.denoise_gain is not None:
+        ap.error("--denoise-gain needs --denoise")
     if args.init != "detail" and (args.init_cell is not None or args.init_mix is not None):
         ap.error("--init-cell and --init-mix need --init detail")
     if args.init_mix is not None and not 0.0 <= args.init_mix <= 1.0:
         ap.error("--init-mix must lie in 0 .. 1")
     if args.film_grain and not args.video:
         ap.error("--film-grain needs --video (a Y'CbCr file)")
+    return args
 
+
+def main(argv=None):
+    args = parse_args(argv)
     from gsvc_amd.arguments import cfg_20240919
     from gsvc_amd.frame import SyntheticFrameCube
     from gsvc_amd.generate import GenerateMode
@@ -129,12 +145,26 @@ def main(argv=None):
     rank, world, _ = gdist.init_from_env(os.environ.get("GSVC_DIST_BACKEND") or None)
     H, W, T, N = args.height, args.width, args.frames, args.steps
     mp_, opt, pipe = cfg_20240919()
+    denoise_log = None
     if args.video:
         from gsvc_amd.frames_in import VideoFileCube
         from gsvc_amd.frames_out import FrameFormat
         vw, vh = (int(v) for v in args.video_size.lower().split("x")) if args.video_size else (None, None)
         vfmt = _frame_format(args.video_format) if args.video_format else None
-        cube = VideoFileCube(args.video, optical_flow_dir=args.flow_dir, W=vw, H=vh, fmt=vfmt, device=dev, resident=args.video_resident)
+        filtered = None
+        if args.denoise is not None:
+            # the fit sees the filtered frames only; the file as it is becomes the cube again once the fit is over (below)
+            from gsvc_amd.frames_in import open_video
+            from gsvc_amd.tfilter import denoise_range
+            hdr, source = open_video(args.video, vw, vh, vfmt)
+            if hdr["fmt"].layout == "rgb24":
+                raise ValueError("--denoise: the temporal prefilter works on Y'CbCr codes; an rgb24 --video has none")
+            filtered, denoise_log = denoise_range(source, int(hdr["H"]), int(hdr["W"]), hdr["fmt"], dev, sigma=args.denoise,
+                                                  gain=1.0 if args.denoise_gain is None else args.denoise_gain)
+            del source
+        cube = VideoFileCube(args.video, optical_flow_dir=args.flow_dir, W=vw, H=vh, fmt=vfmt, device=dev, resident=args.video_resident,
+                             frames=filtered)
+        del filtered
         if args.film_grain and cube.fmt.layout == "rgb24":
             raise ValueError("--film-grain: grain is measured in the delivered Y'CbCr domain; an rgb24 --video has none")
         H, W, T = cube.height, cube.width, cube.len_z_frames          # the file says what is fitted
@@ -176,6 +206,8 @@ def main(argv=None):
     if args.video:
         log["video"] = {"path": args.video, "frames": T, "W": W, "H": H, "layout": cube.fmt.layout, "matrix": cube.fmt.matrix,
                         "range": cube.fmt.range, "chroma": cube.chroma, "resident": cube.resident, "optical_lambda": opt.optical_lambda}
+    if denoise_log is not None:
+        log["denoise"] = dict(denoise_log, metrics_against="the unfiltered source")
     eval_ids = [int(round(i)) for i in np.linspace(0, T - 1, args.eval_frames)]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -205,6 +237,11 @@ def main(argv=None):
     log["data_parallel"] = {"ranks": world, "backend": torch.distributed.get_backend() if world > 1 else None,
                             "per_anchor_exchange": "z-range ownership" if trainer._zown is not None else ("rows / dense" if world > 1 else None)}
     trainer.close()
+    if denoise_log is not None:
+        # the fit is over and the filtered frames are released: every figure below is taken against the unfiltered file
+        del trainer, cube
+        torch.cuda.empty_cache()
+        cube = VideoFileCube(args.video, W=vw, H=vh, fmt=vfmt, device=dev, resident=args.video_resident)
     if world > 1:
         torch.distributed.barrier()
         if rank != 0:

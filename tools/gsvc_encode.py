@@ -5,7 +5,7 @@ the video in another process, with nothing else:
     python tools/gsvc_encode.py clip.y4m -o clip.gsvc [--steps 2000 --lmbda 0.004 --anchors 100000 --estimate-flow]
                                 [--video-format yuv420p,bt601,full] [--video-size WxH] [--hash-format yuv420p]
                                 [--loss-domain rgb|yuv420|yuv444] [--distortion ssim|ms_ssim] [--init detail [--init-cell 8 --init-mix 0.25]]
-                                [--film-grain [--film-grain-gain 1.0 --film-grain-seed N]]
+                                [--film-grain [--film-grain-gain 1.0 --film-grain-seed N]] [--denoise auto|SIGMA [--denoise-gain 1.0]]
     python tools/gsvc_decode.py clip.gsvc -o out.y4m --strict
     python tools/gsvc_encode.py long.y4m -o long.gsvs --gop-frames 32 [--scene-cuts --cut-threshold 0.5 --min-gop 4]
 
@@ -13,7 +13,9 @@ VideoFileCube (optionally with the flow estimated from the frames) -> the fit (t
 gsvc_amd/fit_setup.py) -> conduct_stream_encoding with 8-bit MLPs -> the file.  The file is then read back and decoded into a null sink
 by the function, batch size and format the decoder will use (``decode_video``), which yields the picture hashes; the file is rewritten
 with them (section PHSH).  With --film-grain the grain the fit removed is measured against the source and a few dozen bytes of
-parameters are added (section GRAN; gsvc_amd/grain.py): the decoder synthesises grain from them on its frames.  Prints one JSON line: bytes per section, the file's size, and bpp = 8 x FILE SIZE / (H W T).
+parameters are added (section GRAN; gsvc_amd/grain.py): the decoder synthesises grain from them on its frames.
+With --denoise the fit is given the motion-compensated temporally filtered source (gsvc_amd/tfilter.py; per GOP
+with --gop-frames); the grain statistics of --film-grain are still taken against the original.  Prints one JSON line: bytes per section, the file's size, and bpp = 8 x FILE SIZE / (H W T).
 
 With --gop-frames the clip is cut into groups of pictures (GOPs) of at most that many frames (gsvc_amd/scene.py, ``plan_gops``; with
 --scene-cuts also where the luma histogram of the frames changes), every GOP is fitted and verified on its own (``fit_setup.encode_gop``;
@@ -37,7 +39,8 @@ def _frame_format(text):
     return FrameFormat.from_name(name, **dict(zip(("matrix", "range"), rest)))
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    from gsvc_amd.tfilter import parse_sigma          # (the one reader of an {auto,SIGMA} option; needs neither torch nor the library)
     ap = argparse.ArgumentParser()
     ap.add_argument("video", help="8-bit or 10 / 12 / 16-bit video file: .y4m, or raw .yuv / .rgb with --video-size")
     ap.add_argument("-o", "--output", required=True, metavar="PATH", help="the bitstream file to write (.gsvc)")
@@ -72,7 +75,13 @@ def main(argv=None):
                     help="measure the grain the fit removed and ship its parameters (section GRAN); YUV sources only (gsvc_amd/grain.py)")
     ap.add_argument("--film-grain-gain", type=float, default=None, metavar="X", help="with --film-grain: scale the fitted strengths (default 1.0)")
     ap.add_argument("--film-grain-seed", type=int, default=None, metavar="N", help="with --film-grain: the 64-bit seed (default: derived from the file)")
+    ap.add_argument("--denoise", type=parse_sigma, default=None, metavar="{auto,SIGMA}",
+                    help="fit a motion-compensated temporally filtered source (gsvc_amd/tfilter.py): 'auto' estimates the noise per GOP, "
+                         "a number gives its sigma in codes; YUV sources only.  --film-grain still measures against the original source")
+    ap.add_argument("--denoise-gain", type=float, default=None, metavar="X", help="with --denoise: scale the filter's strength (default 1.0)")
     args = ap.parse_args(argv)
+    if args.denoise is None and args.denoise_gain is not None:
+        ap.error("--denoise-gain needs --denoise")
     if not args.film_grain and (args.film_grain_gain is not None or args.film_grain_seed is not None):
         ap.error("--film-grain-gain and --film-grain-seed need --film-grain")
     if args.init != "detail" and (args.init_cell is not None or args.init_mix is not None):
@@ -81,7 +90,11 @@ def main(argv=None):
         ap.error("--init-mix must lie in 0 .. 1")
     if args.gop_frames is None and (args.scene_cuts or args.cut_threshold is not None or args.min_gop is not None):
         ap.error("--scene-cuts, --cut-threshold and --min-gop need --gop-frames")
+    return args
 
+
+def main(argv=None):
+    args = parse_args(argv)
     import torch
 
     from gsvc_amd.fit_setup import encode_gop
@@ -96,6 +109,8 @@ def main(argv=None):
                init_mix=0.25 if args.init_mix is None else args.init_mix)
     if args.film_grain:
         fit.update(film_grain=True, grain_gain=1.0 if args.film_grain_gain is None else args.film_grain_gain, grain_seed=args.film_grain_seed)
+    if args.denoise is not None:
+        fit.update(denoise=args.denoise, denoise_gain=1.0 if args.denoise_gain is None else args.denoise_gain)
     if args.gop_frames is None:
         blob, log = encode_gop(args.video, dev, **fit)
         with open(args.output, "wb") as f:
@@ -124,7 +139,8 @@ def main(argv=None):
         fit_seconds += one["fit_seconds"]
         gops.append({"first": first, "frames": count, "bytes": len(blob), "bpp": 8.0 * len(blob) / (H * W * count),
                      "fit_seconds": one["fit_seconds"], "cut": int(cut), "anchors_initial": one["anchors_initial"], "anchors_coded": one["anchors_coded"],
-                     "sections": one["sections"], **({"grain": one["grain"]} if "grain" in one else {})})
+                     "sections": one["sections"], **({"grain": one["grain"]} if "grain" in one else {}),
+                     **({"denoise": one["denoise"]} if "denoise" in one else {})})
     fps = header.get("fps") or (30, 1)
     write_sequence(args.output, blobs, W, H, fps, flags)
     log = {"output": args.output, "W": W, "H": H, "frames": T, "steps": args.steps, "fit_seconds": fit_seconds,
