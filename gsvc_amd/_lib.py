@@ -298,6 +298,9 @@ _SIGNATURES = {
                                       C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), _vp, _i64,
                                       _vp]),
     "gsvc_noise_sums": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
+    # Lanczos-3 resampler on the codes (csrc/resample.hip): four tables (first, coef, nt): luma x, luma y, chroma x, chroma y
+    "gsvc_resample_frames": (C.c_int, [_vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _i64, C.c_int32, C.c_int32]
+                             + [_vp, _vp, C.c_int32] * 4 + [_vp]),
     "gsvc_flow_workspace_bytes": (_i64, [C.c_int32] * 5),
     "gsvc_flow_estimate": (C.c_int, [_vp, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, _f, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _f, _vp,
                                      _vp, _vp]),

@@ -19,6 +19,11 @@ VERSION is refused.  Sections of version 1:
     GRAN   optional: the film-grain parameters (``grain.GrainParams.pack``, 122 bytes) a decoder synthesises grain from on the delivered
            frames, AFTER their picture hashes are taken: PHSH stays the hash of the ungrained picture.  A
            decoder that does not know the tag skips it and delivers the ungrained pictures.
+    DISP   optional: typed fields display_W, display_H and filter (1: the Lanczos-3 of gsvc_amd/resample.py).  HEAD's W x H is the
+           CODED size, the size the model renders at; a file with DISP was fitted to a resampled source and its decoder resamples
+           every decoded picture to display_W x display_H, AFTER its picture hash is taken: PHSH stays the hash of the coded-size
+           picture, which does not depend on the resampler's tables.  An unknown filter id is refused.  A
+           decoder that does not know the tag skips it and delivers the coded size.
 
 A clip of several groups of pictures is a sequence file of such file images: gsvc_amd/sequence.py.
 
@@ -37,7 +42,7 @@ MAGIC = b"GSVC"
 VERSION = 1
 _PREFIX = struct.Struct("<4sHH")           # magic, version, number of sections
 _ENTRY = struct.Struct("<4sQI")            # tag, payload length, CRC-32 of the payload
-KNOWN_TAGS = (b"HEAD", b"MLPS", b"ANCH", b"MASK", b"HASH", b"SLAB", b"PHSH", b"GRAN")
+KNOWN_TAGS = (b"HEAD", b"MLPS", b"ANCH", b"MASK", b"HASH", b"SLAB", b"PHSH", b"DISP", b"GRAN")          # (a set: sections are found by tag, in any file order)
 REQUIRED_TAGS = KNOWN_TAGS[:6]
 
 
@@ -328,6 +333,34 @@ def with_grain(blob: bytes, params) -> bytes:
     return pack_sections(sections)
 
 
+def pack_display(W: int, H: int, filter_id: int = 1) -> bytes:
+    """The payload of a DISP section."""
+    return pack_fields({"display_W": int(W), "display_H": int(H), "filter": int(filter_id)})
+
+
+def unpack_display(payload: bytes) -> tuple:
+    """A DISP payload -> ``(W, H)``; a missing field, a size below 2 or an unknown filter id is a ``BitstreamError("DISP", ...)``."""
+    from .resample import FILTER_IDS
+    f = unpack_fields(payload, "DISP")
+    for name in ("display_W", "display_H", "filter"):
+        if not isinstance(f.get(name), int) or isinstance(f.get(name), bool):
+            raise BitstreamError("DISP", f"field {name} is missing or not an integer")
+    if f["filter"] not in FILTER_IDS:
+        raise BitstreamError("DISP", f"unknown filter id {f['filter']} (this decoder knows {sorted(FILTER_IDS)})")
+    if f["display_W"] < 2 or f["display_H"] < 2:
+        raise BitstreamError("DISP", f"the display size {f['display_W']} x {f['display_H']} is not a picture size")
+    return f["display_W"], f["display_H"]
+
+
+def with_display(blob: bytes, size) -> bytes:
+    """The bytes of a file with its DISP section set to the display size ``(W, H)`` (None: removed); every other section, known or not,
+    is kept as it is."""
+    sections = [(t, p) for t, p in unpack_sections(blob) if t != b"DISP"]
+    if size is not None:
+        sections.append((b"DISP", pack_display(size[0], size[1])))
+    return pack_sections(sections)
+
+
 @dataclass
 class Bitstream:
     header: dict
@@ -336,6 +369,7 @@ class Bitstream:
     hash_format: object = None                # FrameFormat of PHSH, or None
     hashes: object = None                     # uint64 [frames, 3], or None
     grain: object = None                      # grain.GrainParams of GRAN, or None
+    display: object = None                    # (W, H) of DISP, or None
     section_bytes: dict = field(default_factory=dict)
     file_bytes: int = 0
 
@@ -346,6 +380,16 @@ class Bitstream:
                             z_min=float(h["z_min"]), threshold=float(h["threshold"]), background=tuple(float(v) for v in h["background"]),
                             fps=(h["fps_num"], h["fps_den"]), sh_degree=h["sh_degree"], raster_flags=h["raster_flags"],
                             raster_low_pass=float(h["raster_low_pass"]))
+
+    @property
+    def coded_size(self) -> tuple:
+        """``(W, H)`` of HEAD: the size the model renders at."""
+        return int(self.header["W"]), int(self.header["H"])
+
+    @property
+    def display_size(self) -> tuple:
+        """``(W, H)`` a decode delivers by default: DISP's where the file has one, else the coded size."""
+        return self.display if self.display is not None else self.coded_size
 
     def frames(self):
         """The T frames a renderer takes (``Frame`` without a picture), from the header's geometry: what ``get_dummy_frame`` builds."""
@@ -451,6 +495,8 @@ def parse_bitstream(blob: bytes) -> Bitstream:
     if b"GRAN" in found:
         from .grain import GrainParams
         bs.grain = GrainParams.unpack(found[b"GRAN"])
+    if b"DISP" in found:
+        bs.display = unpack_display(found[b"DISP"])
     return bs
 
 
@@ -482,16 +528,16 @@ def _same_format(a, b) -> bool:
     return (a.layout, a.depth, a.matrix, a.range, a.rounding_used) == (b.layout, b.depth, b.matrix, b.range, b.rounding_used)
 
 
-def hashed_frames(frames, pc, pipe, bg, H: int, W: int, fmt, batch: int, hashes_out, grain=None, first_frame: int = 0):
+def hashed_frames(frames, pc, pipe, bg, H: int, W: int, fmt, batch: int, hashes_out, grain=None, first_frame: int = 0, out_size=None):
     """``render_frames_u8(..., to_host=True)`` with the picture hash of every batch taken ON THE DEVICE, before the host copy: yields the
     frames as host tensors and appends one int64 ``[n, 3]`` device tensor per batch to ``hashes_out`` (None: no hashes are taken).
     ``grain`` (``grain.GrainParams``): film grain is added to every batch behind its hashes; ``first_frame``: the index of ``frames[0]``
-    in the whole clip."""
+    in the whole clip.  ``out_size=(H, W)``: every batch is resampled to this size behind its hashes (and before its grain)."""
     from .frames_out import render_frames_u8
     from .metrics import picture_hash
     hook = None if hashes_out is None else (lambda rows: hashes_out.append(picture_hash(rows, H, W, fmt)))
     return render_frames_u8(frames, pc, pipe, bg, fmt=fmt, batch=batch, to_host=True, on_device_batch=hook, grain=grain,
-                            first_frame=first_frame)
+                            first_frame=first_frame, out_size=out_size)
 
 
 def grain_to_apply(bs, fmt, film_grain: bool):
@@ -500,8 +546,31 @@ def grain_to_apply(bs, fmt, film_grain: bool):
     return bs.grain if film_grain and bs.grain is not None and fmt.layout != "rgb24" else None
 
 
+def delivered_size(coded, display, size, fmt, what: str) -> tuple:
+    """``(W, H)`` a decode into ``fmt`` delivers for ``size`` = "display" (``display``, the size of DISP, when the file has one), "coded"
+    or ``(W, H)``.  An ``rgb24`` decode delivers the coded size whatever was asked (the resampler works on Y'CbCr codes; the convention
+    of film grain); otherwise a size other than the coded one must be one the resampler takes (``resample.check_sizes``)."""
+    from .resample import check_sizes
+    coded = (int(coded[0]), int(coded[1]))
+    if isinstance(size, str):
+        if size not in ("display", "coded"):
+            raise ValueError(f"{what}: size is 'display', 'coded' or (W, H) (got {size!r})")
+        want = coded if size == "coded" or display is None else (int(display[0]), int(display[1]))
+    else:
+        try:
+            want = tuple(int(v) for v in size)
+        except (TypeError, ValueError):
+            want = ()
+        if len(want) != 2:
+            raise ValueError(f"{what}: size is 'display', 'coded' or (W, H) (got {size!r})")
+    if fmt.layout == "rgb24" or want == coded:
+        return coded
+    check_sizes(coded[1], coded[0], want[1], want[0], fmt, what)
+    return want
+
+
 def decode_video(bitstream_or_path, sink, fmt=None, batch: int = 8, verify: bool = True, strict: bool = False, device="cuda",
-                 film_grain: bool = True) -> dict:
+                 film_grain: bool = True, size="display") -> dict:
     """Decode a bitstream file to frames of ``fmt`` (default: the file's PHSH format, else yuv420p) into ``sink`` (``write`` / ``close``:
     ``frames_out.open_sink``, ``NullSink``).  With ``verify`` the picture hash of every frame is taken on the device before the host
     copy and, where the file carries PHSH in the same format, compared.  Returns {"frames", "bytes", "seconds", "fps", "format",
@@ -509,21 +578,29 @@ def decode_video(bitstream_or_path, sink, fmt=None, batch: int = 8, verify: bool
     "verify_skipped" (why nothing was compared, or None), "film_grain" (whether grain was added)}.  ``strict``: a mismatch raises
     ``BitstreamError`` (after the frames were written), and so does a file without comparable hashes.  ``film_grain``: a file with a GRAN
     section has its grain synthesised on the delivered frames (``grain.apply_grain``) behind the picture hashes, which stay those of
-    the ungrained pictures; False, a file without GRAN or an ``rgb24`` decode deliver the pictures as they are."""
+    the ungrained pictures; False, a file without GRAN or an ``rgb24`` decode deliver the pictures as they are.  ``size``: "display" (the
+    default: the size of the file's DISP section when it has one, else the coded size), "coded" (HEAD's size, as the model renders), or
+    ``(W, H)``: any size within the resampler's ratio limit, for any file (a preview decode).  A delivered size other than the coded one
+    is reached by ``resample.resample_frames`` on the device behind the picture hashes — PHSH and ``strict`` speak of the coded-size
+    pictures — and before the grain.  An ``rgb24`` decode delivers the coded-size pictures.  The result has "W", "H" (of the frames
+    delivered) and "resampled" (whether they were resampled)."""
     import torch
 
     from .frames_out import FrameFormat, write_frames
     bs = bitstream_or_path if isinstance(bitstream_or_path, Bitstream) else read_bitstream(bitstream_or_path)
     if fmt is None:
         fmt = bs.hash_format or FrameFormat("yuv420p")
-    pc, frames, pipe, bg = bs.build_model(device)
     H, W = bs.header["H"], bs.header["W"]
+    out_W, out_H = delivered_size((W, H), bs.display, size, fmt, "decode_video")          # (a size that cannot be had: before the model is built)
+    out_size = None if (out_W, out_H) == (W, H) else (out_H, out_W)
+    pc, frames, pipe, bg = bs.build_model(device)
     per_batch = [] if verify else None
     grain = grain_to_apply(bs, fmt, film_grain)
     with torch.no_grad():
-        res = write_frames(hashed_frames(frames, pc, pipe, bg, H, W, fmt, int(batch), per_batch, grain=grain), sink)
+        res = write_frames(hashed_frames(frames, pc, pipe, bg, H, W, fmt, int(batch), per_batch, grain=grain, out_size=out_size), sink)
     res["format"] = fmt.name
     res["film_grain"] = grain is not None
+    res.update(W=out_W, H=out_H, resampled=out_size is not None)
     res.update(verified=False, frames_verified=0, frames_mismatched=0, mismatched=[], verify_skipped=None)
     if not verify:
         res["verify_skipped"] = "verification was turned off"

@@ -149,10 +149,15 @@ class VideoFileCube:
     inside the range.  None: all frames.
 
     ``frames``: a uint8 array ``[len, frame_bytes]`` that stands in for the payload of the file's frames (those of ``frame_range``): a
-    prefiltered source (gsvc_amd/tfilter.py).  The file still supplies size, format and count.  None: the file's own."""
+    prefiltered source (gsvc_amd/tfilter.py).  The file still supplies size, format and count.  None: the file's own.
+
+    ``frame_size=(W, H)`` (with ``frames`` only): the payload has this size instead of the file's — a resampled source
+    (gsvc_amd/resample.py) — and the cube's ``width``, ``height``, ``scale``, ``x_min`` and ``y_min`` are those of ``frame_size``; the
+    file still supplies format and count.  ``yuv_planes`` and ``luma_detail`` then read the payload given, which is kept on the host (the
+    file's own frames have another size).  None: the payload has the file's size."""
 
     def __init__(self, path, optical_flow_dir=None, W: int | None = None, H: int | None = None, fmt: FrameFormat | None = None,
-                 chroma: str = "bilinear", device="cuda", resident: str = "float", frame_range=None, frames=None):
+                 chroma: str = "bilinear", device="cuda", resident: str = "float", frame_range=None, frames=None, frame_size=None):
         import pathlib
 
         import torch
@@ -177,12 +182,24 @@ class VideoFileCube:
                                  f"{self.path}")
             self.frame_range = (first, stop)
             frames, self.len = frames[first:stop], stop - first
+        self.frame_bytes = int(self.header["frame_bytes"])          # of the payload: the file's, or that of ``frame_size``
+        self._payload = None
+        if frame_size is not None:
+            if given is None:
+                raise ValueError("VideoFileCube: frame_size describes a payload given with frames=")
+            try:
+                self.width, self.height = (int(v) for v in frame_size)
+            except (TypeError, ValueError):
+                raise ValueError(f"VideoFileCube: frame_size must be (W, H) (got {frame_size!r})") from None
+            self.frame_bytes = frame_bytes(self.height, self.width, self.fmt)
         if given is not None:
             given = np.asarray(given)
-            if given.dtype != np.uint8 or given.shape != (self.len, int(self.header["frame_bytes"])):
-                raise ValueError(f"VideoFileCube: frames must be uint8 [{self.len}, {int(self.header['frame_bytes'])}] (got {given.dtype} "
+            if given.dtype != np.uint8 or given.shape != (self.len, self.frame_bytes):
+                raise ValueError(f"VideoFileCube: frames must be uint8 [{self.len}, {self.frame_bytes}] (got {given.dtype} "
                                  f"{given.shape})")
             frames = given
+            if frame_size is not None:
+                self._payload = given
         self.scale = max(self.height, self.width, self.len) / 2
         self.x_min = -self.width / 2 / self.scale
         self.y_min = -self.height / 2 / self.scale
@@ -201,7 +218,7 @@ class VideoFileCube:
 
     def _upload(self, frames):
         import torch
-        T, H, W, nbytes = self.len, self.height, self.width, int(self.header["frame_bytes"])
+        T, H, W, nbytes = self.len, self.height, self.width, self.frame_bytes
         chunk = min(MAX_BATCH, T)
         staging = torch.empty((chunk, nbytes), dtype=torch.uint8, pin_memory=True)
         host = staging.numpy()
@@ -272,16 +289,24 @@ class VideoFileCube:
             self._planes = self._convert_planes()
         return self._planes[image_id]
 
+    def _host_frames(self):
+        """The host bytes of the cube's frames for a second upload: the file's frames of ``frame_range``, or the payload of
+        ``frame_size``."""
+        if self._payload is not None:
+            return self._payload
+        _, frames = open_video(self.path, self.width, self.height, self.fmt)
+        if self.frame_range is not None:
+            frames = frames[self.frame_range[0]:self.frame_range[1]]
+        return frames
+
     def _convert_planes(self):
         """Every frame's plane buffer, for ``resident="float"``: the file's bytes are uploaded again in chunks of up to 16 frames
         through one pinned staging buffer (the float pictures cannot give the un-interpolated chroma back)."""
         import torch
 
         from .yuv_loss import frame_planes
-        _, frames = open_video(self.path, self.width, self.height, self.fmt)
-        if self.frame_range is not None:
-            frames = frames[self.frame_range[0]:self.frame_range[1]]
-        T, nbytes = self.len, int(self.header["frame_bytes"])
+        frames = self._host_frames()
+        T, nbytes = self.len, self.frame_bytes
         chunk = min(MAX_BATCH, T)
         staging = torch.empty((chunk, nbytes), dtype=torch.uint8, pin_memory=True)
         host = staging.numpy()
@@ -309,9 +334,7 @@ class VideoFileCube:
             raise ValueError(f"{self.path}: {self.fmt.layout} frames hold no luma plane")
         if self._u8 is not None:
             return detail.luma_detail(self._u8, self.height, self.width, self.fmt, cell)
-        _, frames = open_video(self.path, self.width, self.height, self.fmt)
-        if self.frame_range is not None:
-            frames = frames[self.frame_range[0]:self.frame_range[1]]
+        frames = self._host_frames()
         return detail.file_detail(frames, self.height, self.width, self.fmt, cell, self.device)
 
     def ready(self, image_id):

@@ -190,7 +190,7 @@ def delivered_images(images, fmt: FrameFormat = FrameFormat(), chroma: str = "bi
 
 
 def render_frames_u8(frames, pc, pipe, bg_color, fmt: FrameFormat = FrameFormat(), batch: int = 8, to_host: bool = True,
-                     scaling_modifier=1.0, mode=None, on_device_batch=None, grain=None, first_frame: int = 0):
+                     scaling_modifier=1.0, mode=None, on_device_batch=None, grain=None, first_frame: int = 0, out_size=None):
     """The decoder's render loop with frames of bytes as output (8-bit samples, or little-endian 16-bit samples for a deep ``fmt``): a
     generator over ``render_frames`` that converts each render batch with one
     launch and yields one flat uint8 frame (``frame_bytes`` long; ``planes`` splits it) per video frame, in order.
@@ -206,7 +206,10 @@ def render_frames_u8(frames, pc, pipe, bg_color, fmt: FrameFormat = FrameFormat(
     ``grain`` (``grain.GrainParams``; YUV formats only): film grain is added to every batch in place on the device
     (``grain.apply_grain``), behind ``on_device_batch`` — the hook sees the ungrained pictures — and before the batch is yielded or
     copied; ``first_frame`` is the index of ``frames[0]`` in the whole clip, which the grain of a frame is a function of.  Without
-    ``grain`` the launches and events are what they were."""
+    ``grain`` the launches and events are what they were.
+    ``out_size=(H, W)`` (YUV formats only): behind ``on_device_batch`` — the hook sees the pictures at the size they were rendered at —
+    every batch is resampled on the device to this size (``resample.resample_frames``) into a buffer of its own; the pinned host
+    buffers and the yielded frames have that size, and ``grain`` is applied after the resample, at that size.  None: nothing changes."""
     import torch
 
     from .generate import GenerateMode
@@ -223,6 +226,11 @@ def render_frames_u8(frames, pc, pipe, bg_color, fmt: FrameFormat = FrameFormat(
         from .grain import apply_grain
         if fmt.layout == "rgb24":
             raise ValueError("render_frames_u8: rgb24 frames take no film grain (it lives in the delivered Y'CbCr domain)")
+    if out_size is not None:
+        from .resample import resample_frames
+        if fmt.layout == "rgb24":
+            raise ValueError("render_frames_u8: rgb24 frames are not resampled (the resampler works on planar Y'CbCr codes)")
+        out_H, out_W = (int(v) for v in out_size)
     source = render_frames(frames, pc, pipe, bg_color, scaling_modifier=scaling_modifier, mode=mode, batch=batch)
     dev = pc._anchor.device
     ring = None           # to_host: two (device buffer, pinned buffer, copied event)
@@ -235,26 +243,42 @@ def render_frames_u8(frames, pc, pipe, bg_color, fmt: FrameFormat = FrameFormat(
             rows = frames_to_u8(images, fmt)
             if on_device_batch is not None:
                 on_device_batch(rows)
+            gH, gW = images[0].shape[1], images[0].shape[2]
+            if out_size is not None:
+                rows, gH, gW = resample_frames(rows, gH, gW, fmt, out_H, out_W), out_H, out_W
             if grain is not None:
-                apply_grain(rows, images[0].shape[1], images[0].shape[2], fmt, grain, first_frame=int(first_frame) + i)
+                apply_grain(rows, gH, gW, fmt, grain, first_frame=int(first_frame) + i)
             yield from rows.unbind(0)
             continue
         if ring is None:
-            nbytes = frame_bytes(images[0].shape[1], images[0].shape[2], fmt)
+            rH, rW = images[0].shape[1], images[0].shape[2]
+            nbytes = frame_bytes(rH, rW, fmt) if out_size is None else frame_bytes(out_H, out_W, fmt)
             ring = [(torch.empty((batch, nbytes), dtype=torch.uint8, device=dev),
                      torch.empty((batch, nbytes), dtype=torch.uint8, pin_memory=True), torch.cuda.Event()) for _ in range(2)]
             copy_stream = torch.cuda.Stream(dev)
+            # out_size: ONE buffer at the rendered size; its writer (the conversion) and its readers (the hook, the resample) all
+            # run on the current stream
+            rendered = None if out_size is None else torch.empty((batch, frame_bytes(rH, rW, fmt)), dtype=torch.uint8, device=dev)
         on_dev, on_host, copied = ring[j % 2]
         cur = torch.cuda.current_stream(dev)
         if j >= 2:
             cur.wait_event(copied)              # the copy of batch j - 2 out of this device buffer
-        frames_to_u8(images, fmt, out=on_dev[:n])
         converted = torch.cuda.Event()
-        if grain is None:
+        if out_size is not None:                # the hook reads the rendered pictures, the copy takes the resampled (and grained) ones
+            frames_to_u8(images, fmt, out=rendered[:n])
+            if on_device_batch is not None:
+                on_device_batch(rendered[:n])
+            resample_frames(rendered[:n], rH, rW, fmt, out_H, out_W, out=on_dev[:n])
+            if grain is not None:
+                apply_grain(on_dev[:n], out_H, out_W, fmt, grain, first_frame=int(first_frame) + i)
+            converted.record(cur)
+        elif grain is None:
+            frames_to_u8(images, fmt, out=on_dev[:n])
             converted.record(cur)
             if on_device_batch is not None:
                 on_device_batch(on_dev[:n])     # (behind the event: the copy does not wait for it)
         else:                                   # the hook reads the ungrained pictures, the copy takes the grained ones
+            frames_to_u8(images, fmt, out=on_dev[:n])
             if on_device_batch is not None:
                 on_device_batch(on_dev[:n])
             apply_grain(on_dev[:n], images[0].shape[1], images[0].shape[2], fmt, grain, first_frame=int(first_frame) + i)

@@ -8,6 +8,9 @@ framing is that of the bitstream file under another magic:
            the GOP starts at a detected scene cut)
     GOPU   one per GOP, in order: a COMPLETE ``GSVC`` version-1 file image — its own table, CRCs and picture hashes (PHSH)
 
+SEQH's W x H is the CODED size, that of every GOP's HEAD; a sequence coded at a reduced size carries its display size in every GOP's DISP
+section, the same in all of them (``Sequence.display_size``; ``decode_sequence`` refuses a file whose GOPs disagree).
+
 A reader skips tags it does not know; a newer version is refused.  ``open_sequence`` reads the prefix, the table and SEQH only; a GOP's
 bytes are read when ``Sequence.gop(k)`` asks for them.  A plain ``GSVC`` file opens as a sequence of one GOP.
 
@@ -23,8 +26,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .bitstream import (_ENTRY, _PREFIX, MAGIC, VERSION, Bitstream, BitstreamError, CubeGeometry, _same_format, grain_to_apply, hashed_frames,
-                        pack_fields, parse_bitstream, unpack_fields)
+from .bitstream import (_ENTRY, _PREFIX, MAGIC, VERSION, Bitstream, BitstreamError, CubeGeometry, _same_format, delivered_size, grain_to_apply,
+                        hashed_frames, pack_fields, parse_bitstream, unpack_fields)
 
 SEQ_MAGIC = b"GSVS"
 SEQ_VERSION = 1
@@ -166,6 +169,16 @@ class Sequence:
         """The format of the first GOP's picture hashes, or None."""
         return self.gop(0).hash_format
 
+    @property
+    def display(self):
+        """``(W, H)`` of the first GOP's DISP section, or None: what every GOP of the file must say."""
+        return self.gop(0).display
+
+    @property
+    def display_size(self) -> tuple:
+        """``(W, H)`` a decode delivers by default: the first GOP's DISP where it has one, else the coded size of SEQH."""
+        return self.display or (int(self.W), int(self.H))
+
 
 def open_sequence(path) -> Sequence:
     """Open a ``.gsvs`` sequence file, or a plain ``.gsvc`` bitstream file as a sequence of one GOP: the prefix, the section table and
@@ -213,7 +226,7 @@ def open_sequence(path) -> Sequence:
 
 
 def decode_sequence(path_or_seq, sink, fmt=None, batch: int = 8, verify: bool = True, strict: bool = False, device="cuda", frames=None,
-                    film_grain: bool = True) -> dict:
+                    film_grain: bool = True, size="display") -> dict:
     """``bitstream.decode_video`` of a sequence file, GOP by GOP into the ONE ``sink``: a GOP's bytes are read, its model built, its
     frames rendered, hashed on the device, compared with the GOP's PHSH and written; the model is dropped before the next GOP is
     built, so the peak device memory is one GOP's.  ``frames=(a, b)``: only the GOPs that overlap ``[a, b)`` are read and built and,
@@ -223,7 +236,9 @@ def decode_sequence(path_or_seq, sink, fmt=None, batch: int = 8, verify: bool = 
     "first", "frames" (of the GOP), "decoded", "rendered", "bytes", "seconds", "frames_verified", "film_grain"}.  ``strict`` as in
     ``decode_video``.  ``film_grain``: a GOP with a GRAN section has ITS grain synthesised on its frames (behind the picture hashes), every
     frame under its index in the WHOLE clip, so that ``frames=(a, b)`` yields the bytes the same frames have in a full decode;
-    ``"film_grain"`` of the result says whether any GOP decoded had grain added."""
+    ``"film_grain"`` of the result says whether any GOP decoded had grain added.  ``size``: as in ``decode_video`` ("display": the DISP
+    size of the file's GOPs, else the coded size; "coded"; or ``(W, H)``); a GOP whose DISP section differs from the first GOP's is a
+    ``BitstreamError`` whatever ``size`` says, and the result has "W", "H" and "resampled"."""
     import gc
 
     import torch
@@ -234,7 +249,8 @@ def decode_sequence(path_or_seq, sink, fmt=None, batch: int = 8, verify: bool = 
     if not 0 <= a < b <= seq.frames:
         raise ValueError(f"decode_sequence: frames ({a}, {b}) is not a non-empty range inside the {seq.frames} frames of the file")
     todo = [(k, first, count) for k, (first, count) in enumerate(seq.gops) if first < b and first + count > a]
-    state = {"fmt": fmt, "got": [], "skipped": None, "bad": [], "verified": 0, "compared": 0, "gops": []}
+    state = {"fmt": fmt, "got": [], "skipped": None, "bad": [], "verified": 0, "compared": 0, "gops": [], "size": None}
+    display = seq.display
     step = int(batch)
     if step < 1:
         raise ValueError("decode_sequence: batch must be at least 1")
@@ -246,6 +262,12 @@ def decode_sequence(path_or_seq, sink, fmt=None, batch: int = 8, verify: bool = 
             if state["fmt"] is None:
                 state["fmt"] = bs.hash_format or FrameFormat("yuv420p")
             used = state["fmt"]
+            if bs.display != display:
+                raise BitstreamError(f"GOPU[{k}]", f"section DISP: the display size {bs.display} disagrees with that of GOP 0 ({display})")
+            if state["size"] is None:
+                state["size"] = delivered_size((seq.W, seq.H), display, size, used, "decode_sequence")
+            out_W, out_H = state["size"]
+            out_size = None if (out_W, out_H) == (seq.W, seq.H) else (out_H, out_W)
             lo, hi = max(a, first) - first, min(b, first + count) - first
             # rendered in the batches a decode of the whole GOP renders — [r0, r1) is [lo, hi) widened to multiples of ``batch`` —: the last
             # bit of a picture can depend on which frames share its generation batch; handed on and compared: [lo, hi)
@@ -255,7 +277,7 @@ def decode_sequence(path_or_seq, sink, fmt=None, batch: int = 8, verify: bool = 
             grain = grain_to_apply(bs, used, film_grain)
             with torch.no_grad():
                 for j, picture in enumerate(hashed_frames(cams[r0:r1], pc, pipe, bg, seq.H, seq.W, used, step, per_batch, grain=grain,
-                                                          first_frame=first + r0)):
+                                                          first_frame=first + r0, out_size=out_size)):
                     if lo <= r0 + j < hi:
                         yield picture
             ok = 0
@@ -285,6 +307,7 @@ def decode_sequence(path_or_seq, sink, fmt=None, batch: int = 8, verify: bool = 
     res["format"] = used.name
     res.update(verified=False, frames_verified=0, frames_mismatched=0, mismatched=[], verify_skipped=None, gops=state["gops"],
                film_grain=any(g["film_grain"] for g in state["gops"]))
+    res.update(W=state["size"][0], H=state["size"][1], resampled=tuple(state["size"]) != (int(seq.W), int(seq.H)))
     if not verify:
         res["verify_skipped"] = "verification was turned off"
     else:

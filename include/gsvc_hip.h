@@ -1247,6 +1247,36 @@ int gsvc_noise_sums(const uint8_t *frames, int64_t stride, int32_t n, int32_t H,
                     void *stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * [INTERNAL] Lanczos-3 resampler on the sample codes of planar frames (csrc/resample.hip, gsvc_amd/resample.py).
+ * Integers only; gsvc_amd/resample.py's docstring states the taps and the arithmetic, tests/_resample_ref.py restates it in numpy.
+ *
+ * gsvc_resample_frames: resamples n (1 .. 16) frames (frame k at src + k * src_stride) of GSVC_FRAMES_YUV444P / _YUV420P, depth d = 8,
+ * 10, 12 or 16, from H x W to out_H x out_W (frame k at dst + k * dst_stride), every plane on its own between its own dimensions
+ * (4:2:0 chroma: (H / 2, W / 2) -> (out_H / 2, out_W / 2)).  A table (first, coef, nt) describes one axis of one plane size: for output
+ * index j, first[j] (int32 [dst]) is the first source index and coef[j, 0 .. nt - 1] (int16 [dst, GSVC_RESAMPLE_TAPS], Q14, summing to
+ * 16384, sum of magnitudes <= 32767; zeros behind a row's own taps) its weights; nt (1 .. 24) is the largest tap count of the table and
+ * slots at or beyond it are never read.  Tables are device arrays: lx / ly for the luma columns / rows, cx / cy for the chroma ones
+ * (4:4:4: the same arrays again).  gsvc_amd/resample.py builds them (filter_taps: Lanczos-3, widened by the ratio when downscaling,
+ * centre-aligned).  With >> the arithmetic shift and every tap index clamped into the plane, clamp(first + k, 0, src - 1):
+ *     t(y, j)   = sum_k cx[j, k] a(y, clamp(fx[j] + k))                                   |t| < 2^31
+ *     m(y, j)   = (t + 2^(d - 3)) >> (d - 2)                                              not clamped
+ *     u(i, j)   = sum_k cy[i, k] m(clamp(fy[i] + k), j)                                   exact, 64-bit
+ *     out(i, j) = clamp((u + 2^(29 - d)) >> (30 - d), 0, 2^d - 1)
+ * Codes are read as they are (a word above 2^d - 1 in a deep frame is not masked).  An axis with src == dst has one coefficient of
+ * 16384 per row, so a 1:1 call copies the frames.  The intermediate m lives in LDS only; no atomics, no workspace; the result does not
+ * depend on the launch geometry; bytes of an output row beyond the frame are not touched.  Every index the kernel derives from a
+ * table is clamped, so no table content makes it read outside a plane.  Refused with an error before any launch: a NULL pointer, rgb24
+ * or an unknown layout, a depth other than 8, 10, 12, 16, n outside 1 .. 16, an odd side for 4:2:0, a side below 2, a ratio above 4
+ * either way, nt outside 1 .. 24, a stride below the frame's bytes (gsvc_frames_bytes), an odd base or stride for a deep format, a
+ * table not aligned to its element, an output that overlaps the input.  Does not synchronise.
+ * ---------------------------------------------------------------------------------------------------- */
+#define GSVC_RESAMPLE_TAPS 24
+int gsvc_resample_frames(const uint8_t *src, int64_t src_stride, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t depth, uint8_t *dst,
+                         int64_t dst_stride, int32_t out_H, int32_t out_W, const int32_t *lx_first, const int16_t *lx_coef, int32_t lx_nt,
+                         const int32_t *ly_first, const int16_t *ly_coef, int32_t ly_nt, const int32_t *cx_first, const int16_t *cx_coef,
+                         int32_t cx_nt, const int32_t *cy_first, const int16_t *cy_coef, int32_t cy_nt, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------
  * Dense optical flow of adjacent frames (csrc/flow.hip): coarse-to-fine Horn-Schunck with warping.  No weights, stencils only: the
  * same bits in every run, for every batch size and launch geometry.
  *

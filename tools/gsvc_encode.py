@@ -6,6 +6,7 @@ the video in another process, with nothing else:
                                 [--video-format yuv420p,bt601,full] [--video-size WxH] [--hash-format yuv420p]
                                 [--loss-domain rgb|yuv420|yuv444] [--distortion ssim|ms_ssim] [--init detail [--init-cell 8 --init-mix 0.25]]
                                 [--film-grain [--film-grain-gain 1.0 --film-grain-seed N]] [--denoise auto|SIGMA [--denoise-gain 1.0]]
+                                [--coded-size WxH]
     python tools/gsvc_decode.py clip.gsvc -o out.y4m --strict
     python tools/gsvc_encode.py long.y4m -o long.gsvs --gop-frames 32 [--scene-cuts --cut-threshold 0.5 --min-gop 4]
 
@@ -15,7 +16,11 @@ by the function, batch size and format the decoder will use (``decode_video``), 
 with them (section PHSH).  With --film-grain the grain the fit removed is measured against the source and a few dozen bytes of
 parameters are added (section GRAN; gsvc_amd/grain.py): the decoder synthesises grain from them on its frames.
 With --denoise the fit is given the motion-compensated temporally filtered source (gsvc_amd/tfilter.py; per GOP
-with --gop-frames); the grain statistics of --film-grain are still taken against the original.  Prints one JSON line: bytes per section, the file's size, and bpp = 8 x FILE SIZE / (H W T).
+with --gop-frames); the grain statistics of --film-grain are still taken against the original.  With --coded-size WxH the fit is given the
+source resampled to that size (gsvc_amd/resample.py; per GOP with --gop-frames; after --denoise), the file says
+which size to display (section DISP, the same in every GOP; SEQH and every HEAD carry the coded size) and the decoder resamples its
+pictures back; the log's "display" entry says what the delivered pictures keep of the source, and bpp is then taken over DISPLAY
+pixels.  YUV sources only, not with --flow-dir or --film-grain.  Prints one JSON line: bytes per section, the file's size, and bpp = 8 x FILE SIZE / (H W T).
 
 With --gop-frames the clip is cut into groups of pictures (GOPs) of at most that many frames (gsvc_amd/scene.py, ``plan_gops``; with
 --scene-cuts also where the luma histogram of the frames changes), every GOP is fitted and verified on its own (``fit_setup.encode_gop``;
@@ -40,6 +45,7 @@ def _frame_format(text):
 
 
 def parse_args(argv=None):
+    from gsvc_amd.resample import parse_size          # (likewise for a WxH option)
     from gsvc_amd.tfilter import parse_sigma          # (the one reader of an {auto,SIGMA} option; needs neither torch nor the library)
     ap = argparse.ArgumentParser()
     ap.add_argument("video", help="8-bit or 10 / 12 / 16-bit video file: .y4m, or raw .yuv / .rgb with --video-size")
@@ -79,7 +85,12 @@ def parse_args(argv=None):
                     help="fit a motion-compensated temporally filtered source (gsvc_amd/tfilter.py): 'auto' estimates the noise per GOP, "
                          "a number gives its sigma in codes; YUV sources only.  --film-grain still measures against the original source")
     ap.add_argument("--denoise-gain", type=float, default=None, metavar="X", help="with --denoise: scale the filter's strength (default 1.0)")
+    ap.add_argument("--coded-size", type=parse_size, default=None, metavar="WxH",
+                    help="fit the source resampled to this size (Lanczos-3 on the codes, a ratio of at most 4 per side) and let the decoder "
+                         "resample back to the source's size (section DISP); YUV sources only, not with --flow-dir or --film-grain")
     args = ap.parse_args(argv)
+    if args.coded_size is not None and (args.flow_dir is not None or args.film_grain):
+        ap.error("--coded-size does not go with --flow-dir (those flows are at the source's size) or --film-grain")
     if args.denoise is None and args.denoise_gain is not None:
         ap.error("--denoise-gain needs --denoise")
     if not args.film_grain and (args.film_grain_gain is not None or args.film_grain_seed is not None):
@@ -111,13 +122,16 @@ def main(argv=None):
         fit.update(film_grain=True, grain_gain=1.0 if args.film_grain_gain is None else args.film_grain_gain, grain_seed=args.film_grain_seed)
     if args.denoise is not None:
         fit.update(denoise=args.denoise, denoise_gain=1.0 if args.denoise_gain is None else args.denoise_gain)
+    if args.coded_size is not None:
+        fit.update(coded_size=args.coded_size)
     if args.gop_frames is None:
         blob, log = encode_gop(args.video, dev, **fit)
         with open(args.output, "wb") as f:
             f.write(blob)
         log = dict({"output": args.output}, **log)
         log["total_bytes"] = int(os.path.getsize(args.output))
-        log["bpp"] = 8.0 * log["total_bytes"] / (log["H"] * log["W"] * log["frames"])
+        shown = log.get("display", log)          # (bits per DISPLAY pixel where the coded picture is a reduced one)
+        log["bpp"] = 8.0 * log["total_bytes"] / (shown["H"] * shown["W"] * log["frames"])
         print(json.dumps(log))
         return log
 
@@ -131,6 +145,7 @@ def main(argv=None):
     cuts = scene.detect_cuts((header, frames), dev, threshold)[0] if args.scene_cuts else []
     del frames
     plan = scene.plan_gops(T, cuts, args.gop_frames, min_gop)
+    cW, cH = args.coded_size or (W, H)          # SEQH and every GOP's HEAD carry the coded size; bpp is taken over display pixels
     flags = scene.gop_cut_flags(plan, cuts)
     blobs, gops, fit_seconds = [], [], 0.0
     for (first, count), cut in zip(plan, flags):
@@ -140,10 +155,10 @@ def main(argv=None):
         gops.append({"first": first, "frames": count, "bytes": len(blob), "bpp": 8.0 * len(blob) / (H * W * count),
                      "fit_seconds": one["fit_seconds"], "cut": int(cut), "anchors_initial": one["anchors_initial"], "anchors_coded": one["anchors_coded"],
                      "sections": one["sections"], **({"grain": one["grain"]} if "grain" in one else {}),
-                     **({"denoise": one["denoise"]} if "denoise" in one else {})})
+                     **({"denoise": one["denoise"]} if "denoise" in one else {}), **({"display": one["display"]} if "display" in one else {})})
     fps = header.get("fps") or (30, 1)
-    write_sequence(args.output, blobs, W, H, fps, flags)
-    log = {"output": args.output, "W": W, "H": H, "frames": T, "steps": args.steps, "fit_seconds": fit_seconds,
+    write_sequence(args.output, blobs, cW, cH, fps, flags)
+    log = {"output": args.output, "W": cW, "H": cH, **({"display": {"W": W, "H": H, "filter": "lanczos3"}} if args.coded_size else {}), "frames": T, "steps": args.steps, "fit_seconds": fit_seconds,
            "loss_domain": one["loss_domain"], "loss_matrix": one["loss_matrix"], "distortion": one["distortion"],
            **{k: one[k] for k in ("init", "init_cell", "init_mix") if k in one},
            "hash_format": _frame_format(args.hash_format).name, "gop_frames": args.gop_frames, "min_gop": min_gop,
