@@ -169,6 +169,11 @@ _SIGNATURES = {
     "gsvc_ssim_l1_backward": (C.c_int, [_vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gsvc_ssim_l1_pair_forward": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "gsvc_ssim_l1_pair_backward": (C.c_int, [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # spatially weighted distortion (csrc/wdist.hip): a weight per cell in the SSIM + L1 pair, and the per-cell luma SSE behind wPSNR
+    "gsvc_wssim_workspace_floats": (_i64, [C.c_int32, C.c_int32, C.c_int32]),
+    "gsvc_wssim_l1_forward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gsvc_wssim_l1_backward": (C.c_int, [_vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "gsvc_frames_block_sse": (C.c_int, [_vp, _vp, _i64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, _vp]),
     "gsvc_ste_binary_count": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
     "gsvc_rate_normalise_scratch_bytes": (_i64, []),
     "gsvc_rate_normalise_forward": (C.c_int, [_vp, _vp, C.c_int32, _vp, _i64, C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_float), _vp, _vp,

@@ -32,13 +32,20 @@ def configure_fit(mp_, opt, cube, steps: int, lmbda: float, slab_frames: float, 
             setattr(opt, name, N)
 
 
-def new_fit(cube, mp_, opt, pipe, anchors: int, device, init: str = "uniform", init_cell: int = 8, init_mix: float = 0.25):
+def new_fit(cube, mp_, opt, pipe, anchors: int, device, init: str = "uniform", init_cell: int = 8, init_mix: float = 0.25,
+            weighting=None, weight_strength: float = 0.5, weight_cell=None, roi=None, weight_file=None, roi_base_hw=None):
     """Seed the generators, build the model of configuration ``mp_`` with ``anchors`` initial points and its Trainer -> ``(pc, trainer)``.
       ``init="uniform"``  the points are drawn uniformly inside the cube (reference frame_cube/utils.py:6-15, init_point_cloud, bleed 0.1).
       ``init="detail"``   they are drawn where the clip's luma has detail (gsvc_amd/detail.py, ``detail_points``: cells of ``init_cell``
                           pixels, a share ``init_mix`` of the points uniform; both defaults are starting values, not measured ones).
-    Either way ``create_from_points`` merges the points of a voxel and sets every anchor's scale from its 3-NN distance."""
-    from . import detail
+    Either way ``create_from_points`` merges the points of a voxel and sets every anchor's scale from its 3-NN distance.
+      ``weighting="activity"``, ``roi=[(x, y, w, h, weight), ...]``, ``weight_file``: spatially weighted distortion (gsvc_amd/wdist.py,
+                          ``fit_weights``: cells of ``weight_cell`` pixels, None = 8; ``weight_strength`` of the activity map; rectangles in
+                          the pixels of ``roi_base_hw = (H, W)``, None = the cube's).  The maps are built on the cube's own frames before
+                          anything is seeded, and the Trainer carries them (``trainer.weight_maps`` on the device, ``trainer.weighting``:
+                          what a log says of them).  Without these arguments nothing changes and ``trainer.weighting`` is None."""
+    from . import detail, wdist
+    maps, weighting_info = wdist.fit_weights(cube, weighting, weight_strength, weight_cell, roi, weight_file, roi_base_hw=roi_base_hw)
     if init not in detail.INITS:
         raise ValueError(f"new_fit: init must be one of {', '.join(detail.INITS)} (got {init!r})")
     if init == "detail":
@@ -60,7 +67,11 @@ def new_fit(cube, mp_, opt, pipe, anchors: int, device, init: str = "uniform", i
     pc.update_anchor_bound(cube.x_min, cube.y_min, cube.z_min)
     pc.training_setup(opt)
     gdist.broadcast_parameters(pc)
-    trainer = Trainer(pc, cube, opt, pipe, mp_, seed=0)
+    if maps is None:
+        trainer = Trainer(pc, cube, opt, pipe, mp_, seed=0)
+    else:
+        trainer = Trainer(pc, cube, opt, pipe, mp_, seed=0, weight_maps=maps, weight_cell=weighting_info["cell"])
+    trainer.weighting = weighting_info
     return pc, trainer
 
 
@@ -125,11 +136,38 @@ def display_psnr(bs, source_frames, fmt, device, batch: int = 8):
     return p[0], (6.0 * p[0] + p[1] + p[2]) / 8.0
 
 
+def coded_wpsnr(bs, fit_frames, fmt, weight_maps, cell: int, device, batch: int = 8):
+    """What a weighted fit bought, on the delivered codes: ``bs`` (a parsed ``Bitstream``) is decoded into ``fmt``, the format of the frames
+    the fit was given, at the size it was fitted at, batch by batch, and each batch's ``wdist.block_sse`` against those frames
+    (``fit_frames``: the host array ``[T, frame_bytes]``, uploaded a batch at a time) is kept -> ``(psnr_y, wpsnr_y)`` pooled over the
+    frames: the plain luma PSNR and ``wdist.weighted_psnr_y`` under ``weight_maps`` ``[T, Hc, Wc]``."""
+    from .frames_out import render_frames_u8
+    from .wdist import block_sse, weighted_psnr_y
+    W, H = bs.coded_size
+    pc, cams, pipe, bg = bs.build_model(device)
+    blocks, rows, got = [], [], 0
+    with torch.no_grad():
+        for row in render_frames_u8(cams, pc, pipe, bg, fmt=fmt, batch=int(batch), to_host=False):
+            rows.append(row)
+            if len(rows) == int(batch) or got + len(rows) == len(cams):
+                src = torch.from_numpy(np.ascontiguousarray(fit_frames[got:got + len(rows)])).to(row.device)
+                blocks.append(block_sse(torch.stack(rows), src, H, W, fmt, cell).cpu())
+                got += len(rows)
+                rows = []
+    if got != int(fit_frames.shape[0]):
+        raise ValueError(f"coded_wpsnr: the file decodes to {got} frames, the fit saw {int(fit_frames.shape[0])}")
+    sse = torch.cat(blocks)
+    _, plain = weighted_psnr_y(sse, torch.ones(sse.shape, dtype=torch.float64), fmt.depth, H, W)
+    _, weighted = weighted_psnr_y(sse, weight_maps, fmt.depth, H, W)
+    return plain, weighted
+
+
 def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float = 0.004, anchors: int = 100_000, slab_frames: float = 16.0,
                densify_grad_threshold=None, estimate_flow: bool = False, flow_dir=None, video_size=(None, None), video_format=None,
                hash_format=None, loss_domain: str = "rgb", init: str = "uniform", init_cell: int = 8, init_mix: float = 0.25,
                distortion: str = "ssim", film_grain: bool = False, grain_gain: float = 1.0, grain_seed=None,
-               grain_flat_threshold=None, grain_max_residual=None, denoise=None, denoise_gain: float = 1.0, coded_size=None):
+               grain_flat_threshold=None, grain_max_residual=None, denoise=None, denoise_gain: float = 1.0, coded_size=None,
+               weighting=None, weight_strength: float = 0.5, weight_cell=None, roi=None, weight_file=None):
     """One group of pictures of a video file -> ``(the bytes of a complete GSVC file, log)``: what tools/gsvc_encode.py does with a whole
     clip, for the frames ``frame_range = (first, stop)`` of it (None: all).  VideoFileCube (optionally with the flow estimated from the
     frames) -> the fit -> ``conduct_stream_encoding`` with 8-bit MLPs -> the file image; that image is then decoded into a null sink by
@@ -158,7 +196,13 @@ def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float 
     ``init_cell``, ``init_mix``: where the fit's first anchors come from (``new_fit``; anchors are coded wherever they are).  ``log``:
     {"W", "H", "frames", "steps", "init", ("init_cell", "init_mix": with init="detail" only), "anchors_initial": the anchors after the
     voxel merge of ``create_from_points``, "loss_domain", "loss_matrix", "distortion", "anchors_coded", "fit_seconds", "hash_format",
-    "verify_decode_fps", "sections"}."""
+    "verify_decode_fps", "sections"}.  ``weighting="activity"`` (with ``weight_strength``), ``roi=[(x, y, w, h, weight), ...]`` in the
+    SOURCE's pixels, ``weight_file`` (a ``.npy``), all at cells of ``weight_cell`` pixels (None: 8): spatially weighted distortion
+    (``new_fit``, gsvc_amd/wdist.py).  The maps are built on the frames the fit sees — of this ``frame_range`` alone, filtered and at
+    coded size where those are asked for, rectangles scaled to it — and only shape the fit: the file's sections are what they were.  The
+    file image is then decoded once more, into the format and size of those frames, and the log has "weighting": {"sources", "cell",
+    ("strength", "clamp": activity), ("roi": the scaled rectangles), "min", "max", "psnr_y", "wpsnr_y": ``coded_wpsnr``}; an ``rgb24``
+    source is a ``ValueError`` before the fit starts.  Without these arguments the log has no such entry."""
     import gc
     import os
     import tempfile
@@ -171,6 +215,7 @@ def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float 
     from .stream_codec import conduct_stream_encoding
     mp_, opt, pipe = cfg_20240919()
     filtered, denoise_log, frame_size = None, None, None
+    weighted = weighting is not None or bool(roi) or weight_file is not None
     if coded_size is not None:
         try:
             frame_size = tuple(int(v) for v in coded_size)
@@ -212,7 +257,10 @@ def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float 
         del source
     cube = VideoFileCube(video, optical_flow_dir=flow_dir, W=video_size[0], H=video_size[1], fmt=video_format, device=device,
                          frame_range=frame_range, frames=filtered, frame_size=frame_size)
+    fit_frames = filtered if weighted else None          # what the fit sees, for the weighted PSNR of the file image
     del filtered
+    if weighted and cube.fmt.layout == "rgb24":
+        raise ValueError("encode_gop: the weighted PSNR of a weighted fit is taken on luma codes; an rgb24 source has none")
     if film_grain and cube.fmt.layout == "rgb24":
         raise ValueError("encode_gop: film grain is measured and synthesised in the delivered Y'CbCr domain; an rgb24 source has none")
     source_fmt = cube.fmt
@@ -228,7 +276,13 @@ def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float 
     configure_fit(mp_, opt, cube, steps, lmbda, slab_frames, densify_grad_threshold)
     opt.loss_domain = loss_domain
     opt.distortion = distortion
-    pc, trainer = new_fit(cube, mp_, opt, pipe, anchors, device, init=init, init_cell=init_cell, init_mix=init_mix)
+    if weighted:
+        pc, trainer = new_fit(cube, mp_, opt, pipe, anchors, device, init=init, init_cell=init_cell, init_mix=init_mix, weighting=weighting,
+                              weight_strength=weight_strength, weight_cell=weight_cell, roi=roi, weight_file=weight_file,
+                              roi_base_hw=(display[1], display[0]) if frame_size is not None else None)
+        weighting_log, weight_maps = trainer.weighting, trainer.weight_maps.cpu()
+    else:
+        pc, trainer = new_fit(cube, mp_, opt, pipe, anchors, device, init=init, init_cell=init_cell, init_mix=init_mix)
     log["init"] = init
     if init == "detail":
         log["init_cell"], log["init_mix"] = int(init_cell), float(init_mix)
@@ -261,6 +315,17 @@ def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float 
     gc.collect()
     torch.cuda.empty_cache()
     log["hash_format"], log["verify_decode_fps"] = fmt.name, res["fps"]
+    if weighted:
+        if fit_frames is None:
+            from .frames_in import open_video
+            _, fit_frames = open_video(video, video_size[0], video_size[1], video_format)
+            if frame_range is not None:
+                fit_frames = fit_frames[int(frame_range[0]):int(frame_range[1])]
+        psnr_y, wpsnr_y = coded_wpsnr(parse_bitstream(blob), fit_frames, source_fmt, weight_maps, weighting_log["cell"], device)
+        log["weighting"] = dict(weighting_log, psnr_y=psnr_y, wpsnr_y=wpsnr_y)
+        del fit_frames
+        gc.collect()
+        torch.cuda.empty_cache()
     if frame_size is not None:
         from .bitstream import with_display
         from .frames_in import open_video

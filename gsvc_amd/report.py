@@ -20,7 +20,7 @@ from .ortho_gaussian_renderer import render_frames
 
 @torch.no_grad()
 def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_fn=None, eight_bit: bool = False, delivered=None,
-             code_metrics: bool = False, source_u8=None, msssim: str = "torch") -> dict:
+             code_metrics: bool = False, source_u8=None, msssim: str = "torch", weight_maps=None, weight_cell=None) -> dict:
     """Mean L1 / PSNR / SSIM / MS-SSIM (MS-SSIM only for frames at least 160 pixels high and large enough for 5 scales) of the
     rendered two-view frames, clamped to [0, 1], against ``dataset[i].image``; ``fps`` counts the whole loop's wall time,
     metrics excluded.  ``eight_bit=True``: the metrics are taken on what the decoder delivers — the frames quantised to 8 bits
@@ -33,7 +33,11 @@ def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_
     ``[frames, frame_bytes]``, tensor or array, in the order of ``frame_ids``: for example a file's own bytes from ``open_video``), else
     ``frames_to_u8(gt, fmt)``: ``psnr_y``, ``psnr_u``, ``psnr_v``, ``psnr_avg``, ``psnr_611`` (``yuv420p``) and ``msssim_y`` (frames with both sides above
     160 pixels), each the mean over the frames.  ``msssim="fused"``: the ``msssim`` entry comes from ``metrics.ms_ssim_fused`` instead of
-    the tensor expressions."""
+    the tensor expressions.  ``weight_maps`` (``[T, Hc, Wc]`` for the dataset's frames at ``weight_cell``, gsvc_amd/wdist.py; needs
+    ``code_metrics=True`` and a Y'CbCr ``delivered``): adds ``wpsnr_y``, the mean over the frames of ``wdist.weighted_psnr_y`` under each
+    frame's own map, on the same codes as ``psnr_y``."""
+    if weight_maps is not None and (not code_metrics or delivered is None or delivered.layout == "rgb24" or weight_cell is None):
+        raise ValueError("evaluate: weight_maps needs code_metrics=True, a Y'CbCr delivered= format and weight_cell")
     if eight_bit and delivered is not None:
         raise ValueError("evaluate: eight_bit=True and delivered= both say what is delivered; give one")
     if code_metrics and delivered is None:
@@ -86,12 +90,14 @@ def evaluate(pc, dataset, pipe, bg_color, frame_ids=None, batch: int = 8, lpips_
     if delivered is not None:
         out["delivered"] = delivered.name
     if code_metrics and rendered:
-        out.update(_code_metrics_means(rendered, gts, source_u8, delivered, batch))
+        weights = None if weight_maps is None else (weight_maps[ids], int(weight_cell))
+        out.update(_code_metrics_means(rendered, gts, source_u8, delivered, batch, weights))
     return out
 
 
-def _code_metrics_means(rendered, gts, source_u8, fmt, batch):
-    """Means over the frames of ``metrics.code_metrics`` between the rendered frames' codes and the source's (see ``evaluate``)."""
+def _code_metrics_means(rendered, gts, source_u8, fmt, batch, weights=None):
+    """Means over the frames of ``metrics.code_metrics`` between the rendered frames' codes and the source's (see ``evaluate``);
+    ``weights = (maps [frames, Hc, Wc], cell)``: also of the weighted luma PSNR."""
     from .frames_out import frame_bytes, frames_to_u8
     from .metrics import code_metrics
     H, W = (int(v) for v in rendered[0].shape[1:])
@@ -110,6 +116,10 @@ def _code_metrics_means(rendered, gts, source_u8, fmt, batch):
         for k, v in code_metrics(dec, ref, H, W, fmt).items():
             if k not in ("peak", "sse"):
                 sums[k] = sums.get(k, 0.0) + float(v.sum())
+        if weights is not None:
+            from .wdist import block_sse, weighted_psnr_y
+            per, _ = weighted_psnr_y(block_sse(dec, ref, H, W, fmt, weights[1]), weights[0][i:i + step], fmt.depth, H, W)
+            sums["wpsnr_y"] = sums.get("wpsnr_y", 0.0) + float(per.sum())
     return {k: v / len(rendered) for k, v in sums.items()}
 
 

@@ -150,9 +150,16 @@ def _mean_over_selected(values, r):
 
 
 class Trainer:
-    def __init__(self, gaussians, dataset, opt, pipe, model_params, seed: int = 0, batched: bool = True, prefetch: bool = True):
-        # what the step's image terms are and where they are taken: refuses a loss domain or a structural term this dataset cannot have
-        self._distortion = StepDistortion(opt, dataset)
+    def __init__(self, gaussians, dataset, opt, pipe, model_params, seed: int = 0, batched: bool = True, prefetch: bool = True,
+                 weight_maps=None, weight_cell=None):
+        # what the step's image terms are and where they are taken: refuses a loss domain or a structural term this dataset cannot have.
+        # weight_maps [T, Hc, Wc] (gsvc_amd/wdist.py) weight them per cell; they live on the model's device, each frame of a step takes
+        # its own
+        if weight_maps is not None and torch.is_tensor(weight_maps):
+            weight_maps = weight_maps.to(gaussians._anchor.device)
+        self._distortion = StepDistortion(opt, dataset, weight_maps=weight_maps, weight_cell=weight_cell)
+        self.weight_maps, self.weight_cell = self._distortion.weight_maps, self._distortion.weight_cell
+        self.weighting = None                  # what a log says of the maps (fit_setup.new_fit sets it)
         self.loss_domain, self.loss_matrix, self.distortion = self._distortion.domain, self._distortion.matrix, self._distortion.name
         self.batched = batched
         # prefetch: the next step's frame pair is drawn, its visibility test run and every data-dependent index list of its
@@ -466,11 +473,11 @@ class Trainer:
         gt1 = dist.target(self.dataset, st.frame1, st.frame_idx, dev)
         gt2 = dist.target(self.dataset, st.frame2, st.frame_idx + 1, dev)
         if self.batched:
-            terms1, st.image1 = dist(r1f.rendered_image, r1b.rendered_image, gt1)
-            terms2, st.image2 = dist(r2f.rendered_image, r2b.rendered_image, gt2)
+            terms1, st.image1 = dist(r1f.rendered_image, r1b.rendered_image, gt1, frame_index=st.frame_idx)
+            terms2, st.image2 = dist(r2f.rendered_image, r2b.rendered_image, gt2, frame_index=st.frame_idx + 1)
         else:
-            terms1, st.image1 = dist(st.image1, None, gt1)
-            terms2, st.image2 = dist(st.image2, None, gt2)
+            terms1, st.image1 = dist(st.image1, None, gt1, frame_index=st.frame_idx)
+            terms2, st.image2 = dist(st.image2, None, gt2, frame_index=st.frame_idx + 1)
         # the loss is a weighted sum of scalar terms: they are collected and combined with one stack + dot (instead of
         # one tiny kernel per +, *, and their backward nodes)
         st.terms = dist.image_terms(terms1, terms2)

@@ -390,6 +390,30 @@ int gsvc_ssim_l1_pair_backward(const float *img_f, const float *img_b, const flo
                                const float *grads, const float *dm_dmu1, const float *dm_de11, const float *dm_de12,
                                float *dL_dimg_f, float *dL_dimg_b, void *stream);
 
+/* Spatially weighted distortion (csrc/wdist.hip; no counterpart in the reference).  weights: float32 [Hc, Wc], Hc = ceil(H / cell),
+ * Wc = ceil(W / cell), cell 4, 8 or 16, finite and >= 0; pixel (y, x) of every channel has the weight w[y / cell][x / cell].
+ * forward: window, padding, moments and map of gsvc_ssim_l1_forward, on x = img1 or, with img1b, on the two-view frame
+ * 0.5 * (img1 + flip_W(img1b)), which avg_out (required then, optional otherwise) receives.  sums[0] = sum w ssim, sums[1] = sum w |x - img2|;
+ * the three partial maps (all or none) are written already multiplied by the pixel's weight.  workspace: gsvc_wssim_workspace_floats(C, H, W)
+ * floats (2 per 32 x 32 tile; -1 for a bad shape): every workgroup stores its own row and a second kernel adds the rows in a fixed order in
+ * double, so the sums are the same bits in every run; nothing needs zeroing.
+ * backward: dL_dimg1 = grads[0] / (C H W) * (the blurred weighted maps combined with x and img2, as gsvc_ssim_l1_backward)
+ * + ((grads[1] / (C H W)) * w) * sign(x - img2); with img1b both views receive half of it, dL_dimg1b flipped (required then, NULL otherwise). */
+int64_t gsvc_wssim_workspace_floats(int32_t C, int32_t H, int32_t W);
+int gsvc_wssim_l1_forward(const float *img1, const float *img1b, const float *img2, const float *weights, int32_t C, int32_t H, int32_t W,
+                          int32_t cell, float *sums, float *workspace, float *dm_dmu1, float *dm_de11, float *dm_de12, float *avg_out,
+                          void *stream);
+int gsvc_wssim_l1_backward(const float *img1, const float *img1b, const float *img2, const float *weights, int32_t C, int32_t H, int32_t W,
+                           int32_t cell, const float *grads, const float *dm_dmu1, const float *dm_de11, const float *dm_de12,
+                           float *dL_dimg1, float *dL_dimg1b, void *stream);
+
+/* out[f, cy, cx] (int64 [n, Hc, Wc], 8-byte aligned) = the sum of squared differences of the luma codes of frames a[f], b[f] over cell
+ * (cy, cx); yuv420p / yuv444p frames of 8 .. 16 bits, both buffers `stride` bytes apart (deep formats: even bases and stride); cell 4, 8
+ * or 16, partial cells at the right and bottom edges sum their own pixels.  Exact (every sum < 2^40); one launch; the sum over a frame's
+ * cells is gsvc_frames_sse's luma entry. */
+int gsvc_frames_block_sse(const uint8_t *a, const uint8_t *b, int64_t stride, int32_t n, int32_t H, int32_t W, int32_t layout, int32_t depth,
+                          int32_t cell, int64_t *out, void *stream);
+
 /* STE_binary forward (reference utils/encodings.py:375-392: y = x >= 0 ? +1 : -1) and count[0] = number of +1 entries
  * (the hash-bit term of the loss, pipeline/train.py:456, needs it); n < 2^24. */
 int gsvc_ste_binary_count(const float *x, int64_t n, float *y, float *count, void *stream);

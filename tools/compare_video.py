@@ -6,6 +6,7 @@ kernels of csrc/metrics.hip, so it needs the GPU).  Prints one JSON line.
     python tools/compare_video.py ref.y4m dec.y4m [--json out.json]
     python tools/compare_video.py ref.yuv dec.yuv --size 1920x1080 --format yuv420p10le
     python tools/compare_video.py a.y4m b.y4m --hash      (also each file's per-frame picture hashes, ``metrics.picture_hash``, and whether they agree)
+    python tools/compare_video.py ref.y4m dec.y4m --weights w.npy --weight-cell 8      (also wPSNR-Y under the maps of w.npy, gsvc_amd/wdist.py)
 """
 import argparse
 import json
@@ -31,6 +32,27 @@ def _hashes(path, W, H, fmt, chunk):
     return out
 
 
+def _wpsnr(ref, dec, W, H, fmt, chunk, weights_path, cell):
+    """wPSNR-Y of two video files under the weight maps of a .npy ([Hc, Wc] or [frames, Hc, Wc]): {"wpsnr_y": per frame, "wpsnr_y_seq"}."""
+    import numpy as np
+    import torch
+
+    from gsvc_amd.frames_in import open_video
+    from gsvc_amd.wdist import block_sse, load_weights, weighted_psnr_y
+    ha, fa = open_video(ref, W, H, fmt)
+    hb, fb = open_video(dec, int(ha["W"]), int(ha["H"]), ha["fmt"])
+    if fa.shape != fb.shape:
+        raise SystemExit(f"--weights: the files differ in frames or size ({tuple(fa.shape)} and {tuple(fb.shape)})")
+    h, w, f = int(ha["H"]), int(ha["W"]), ha["fmt"]
+    maps = load_weights(weights_path, int(fa.shape[0]), h, w, cell)
+    sse = []
+    for i in range(0, int(fa.shape[0]), chunk):
+        a, b = (torch.from_numpy(np.ascontiguousarray(x[i:i + chunk])).cuda() for x in (fa, fb))
+        sse.append(block_sse(a, b, h, w, f, cell).cpu())
+    per, pooled = weighted_psnr_y(torch.cat(sse), maps, f.depth, h, w)
+    return {"wpsnr_y": [float(v) for v in per], "wpsnr_y_seq": pooled, "weight_cell": cell}
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("ref")
@@ -41,6 +63,9 @@ def main(argv=None):
     ap.add_argument("--no-per-frame", action="store_true", help="leave the per-frame lists out of the line")
     ap.add_argument("--hash", action="store_true",
                     help="also print the per-frame, per-plane picture hashes of both files (what a bitstream file's PHSH section holds) and whether they agree")
+    ap.add_argument("--weights", default=None, metavar="FILE.npy",
+                    help="also print wPSNR-Y under these weight maps ([Hc, Wc] or [frames, Hc, Wc]; normalised per frame; YUV files only)")
+    ap.add_argument("--weight-cell", type=int, choices=(4, 8, 16), default=8, metavar="N", help="the cell of --weights in pixels (default 8)")
     ap.add_argument("--json", default=None)
     args = ap.parse_args(argv)
     from gsvc_amd.frames_out import FrameFormat
@@ -57,6 +82,10 @@ def main(argv=None):
         ha, hb = _hashes(args.ref, W, H, fmt, max(1, args.chunk)), _hashes(args.dec, W, H, fmt, max(1, args.chunk))
         same = [a == b for a, b in zip(ha, hb)]
         res["picture_hash"] = {"ref": ha, "dec": hb, "equal": same, "all_equal": all(same)}
+    if args.weights:
+        wp = _wpsnr(args.ref, args.dec, W, H, fmt, max(1, args.chunk), args.weights, args.weight_cell)
+        res["wpsnr_y_seq"], res["weight_cell"] = wp["wpsnr_y_seq"], wp["weight_cell"]
+        res["per_frame"]["wpsnr_y"] = wp["wpsnr_y"]
     if args.no_per_frame:
         res.pop("per_frame")
     line = json.dumps(res)

@@ -55,6 +55,7 @@ def _frame_format(text):
 
 def parse_args(argv=None):
     from gsvc_amd.tfilter import parse_sigma          # (the one reader of an {auto,SIGMA} option; needs neither torch nor the library)
+    from gsvc_amd.wdist import parse_roi              # (X,Y,W,H:WEIGHT)
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--height", type=int, default=1080)
@@ -111,7 +112,23 @@ def parse_args(argv=None):
                     help="with a Y'CbCr --video: fit its motion-compensated temporally filtered frames (gsvc_amd/tfilter.py; 'auto' estimates "
                          "the noise, a number gives its sigma in codes).  Every metric is still reported against the UNFILTERED file")
     ap.add_argument("--denoise-gain", type=float, default=None, metavar="X", help="with --denoise: scale the filter's strength (default 1.0)")
+    ap.add_argument("--weighting", choices=("activity",), default=None,
+                    help="weight the distortion per cell by the clip's activity (gsvc_amd/wdist.py); rgb loss domain and --distortion ssim only")
+    ap.add_argument("--weight-strength", type=float, default=None, metavar="S",
+                    help="with --weighting activity: > 0 moves weight to flat cells, < 0 to detail (default 0.5: a starting value, not measured)")
+    ap.add_argument("--weight-cell", type=int, choices=(4, 8, 16), default=None, help="the cell of the weight maps in pixels (default 8)")
+    ap.add_argument("--roi", action="append", type=parse_roi, default=None, metavar="X,Y,W,H:WEIGHT",
+                    help="a rectangle in pixels with this weight over a base of 1 (repeatable; later ones override earlier ones)")
+    ap.add_argument("--weight-map", default=None, metavar="FILE.npy",
+                    help="weights [Hc, Wc] or [frames, Hc, Wc] at --weight-cell; multiplies with the other sources")
     args = ap.parse_args(argv)
+    args.weighted = args.weighting is not None or bool(args.roi) or args.weight_map is not None
+    if args.weight_strength is not None and args.weighting is None:
+        ap.error("--weight-strength needs --weighting activity")
+    if args.weight_cell is not None and not args.weighted:
+        ap.error("--weight-cell needs --weighting, --roi or --weight-map")
+    if args.weighted and (args.loss_domain != "rgb" or args.distortion != "ssim"):
+        ap.error("weighted distortion needs --loss-domain rgb and --distortion ssim")
     if args.denoise is not None and not args.video:
         ap.error("--denoise needs --video (a Y'CbCr file)")
     if args.denoise is None and args.denoise_gain is not None:
@@ -194,7 +211,12 @@ def main(argv=None):
     init = {"init": args.init}
     if args.init == "detail":
         init.update(init_cell=8 if args.init_cell is None else args.init_cell, init_mix=0.25 if args.init_mix is None else args.init_mix)
-    pc, trainer = new_fit(cube, mp_, opt, pipe, args.anchors, dev, **init)
+    weighting = {}
+    if args.weighted:
+        weighting = dict(weighting=args.weighting, weight_strength=0.5 if args.weight_strength is None else args.weight_strength,
+                         weight_cell=args.weight_cell, roi=args.roi, weight_file=args.weight_map)
+    pc, trainer = new_fit(cube, mp_, opt, pipe, args.anchors, dev, **init, **weighting)
+    weight_maps, weight_cell = (trainer.weight_maps.cpu(), trainer.weight_cell) if args.weighted else (None, None)
     bg = trainer.background
     log = {"config": {"H": H, "W": W, "frames": T, "steps": N, "anchors_init": args.anchors, **init,
                       "anchors_initial": int(pc._anchor.shape[0]), "lmbda": args.lmbda,
@@ -208,6 +230,8 @@ def main(argv=None):
                         "range": cube.fmt.range, "chroma": cube.chroma, "resident": cube.resident, "optical_lambda": opt.optical_lambda}
     if denoise_log is not None:
         log["denoise"] = dict(denoise_log, metrics_against="the unfiltered source")
+    if args.weighted:
+        log["weighting"] = dict(trainer.weighting)
     eval_ids = [int(round(i)) for i in np.linspace(0, T - 1, args.eval_frames)]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -358,7 +382,8 @@ def main(argv=None):
         if args.code_metrics:
             from gsvc_amd.frames_out import FrameFormat
             cfmt = _frame_format(args.decoded_format) if args.decoded_format else FrameFormat("yuv420p")
-            both = evaluate(dec_q, cube, pipe, bg, frame_ids=eval_ids, delivered=cfmt, code_metrics=True)
+            both = evaluate(dec_q, cube, pipe, bg, frame_ids=eval_ids, delivered=cfmt, code_metrics=True, weight_maps=weight_maps,
+                            weight_cell=weight_cell)
             log["decoded_code_metrics"] = dict({k: v for k, v in both.items() if k not in ev or k == "delivered"}, format=cfmt.name)
         if args.write_decoded:
             from gsvc_amd.frames_out import open_sink, write_video

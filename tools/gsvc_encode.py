@@ -47,6 +47,7 @@ def _frame_format(text):
 def parse_args(argv=None):
     from gsvc_amd.resample import parse_size          # (likewise for a WxH option)
     from gsvc_amd.tfilter import parse_sigma          # (the one reader of an {auto,SIGMA} option; needs neither torch nor the library)
+    from gsvc_amd.wdist import parse_roi              # (X,Y,W,H:WEIGHT)
     ap = argparse.ArgumentParser()
     ap.add_argument("video", help="8-bit or 10 / 12 / 16-bit video file: .y4m, or raw .yuv / .rgb with --video-size")
     ap.add_argument("-o", "--output", required=True, metavar="PATH", help="the bitstream file to write (.gsvc)")
@@ -88,7 +89,24 @@ def parse_args(argv=None):
     ap.add_argument("--coded-size", type=parse_size, default=None, metavar="WxH",
                     help="fit the source resampled to this size (Lanczos-3 on the codes, a ratio of at most 4 per side) and let the decoder "
                          "resample back to the source's size (section DISP); YUV sources only, not with --flow-dir or --film-grain")
+    ap.add_argument("--weighting", choices=("activity",), default=None,
+                    help="weight the fit's distortion per cell by the clip's activity (gsvc_amd/wdist.py; per GOP with --gop-frames); rgb loss "
+                         "domain and --distortion ssim only, YUV sources only")
+    ap.add_argument("--weight-strength", type=float, default=None, metavar="S",
+                    help="with --weighting activity: > 0 moves weight to flat cells, < 0 to detail (default 0.5: a starting value, not measured)")
+    ap.add_argument("--weight-cell", type=int, choices=(4, 8, 16), default=None, help="the cell of the weight maps in pixels (default 8)")
+    ap.add_argument("--roi", action="append", type=parse_roi, default=None, metavar="X,Y,W,H:WEIGHT",
+                    help="a rectangle in the source's pixels with this weight over a base of 1 (repeatable; later ones override earlier ones)")
+    ap.add_argument("--weight-map", default=None, metavar="FILE.npy",
+                    help="weights [Hc, Wc] or [frames, Hc, Wc] at --weight-cell of the frames the fit sees; multiplies with the other sources")
     args = ap.parse_args(argv)
+    weighted = args.weighting is not None or args.roi or args.weight_map is not None
+    if args.weight_strength is not None and args.weighting is None:
+        ap.error("--weight-strength needs --weighting activity")
+    if args.weight_cell is not None and not weighted:
+        ap.error("--weight-cell needs --weighting, --roi or --weight-map")
+    if weighted and (args.loss_domain != "rgb" or args.distortion != "ssim"):
+        ap.error("weighted distortion needs --loss-domain rgb and --distortion ssim")
     if args.coded_size is not None and (args.flow_dir is not None or args.film_grain):
         ap.error("--coded-size does not go with --flow-dir (those flows are at the source's size) or --film-grain")
     if args.denoise is None and args.denoise_gain is not None:
@@ -124,6 +142,9 @@ def main(argv=None):
         fit.update(denoise=args.denoise, denoise_gain=1.0 if args.denoise_gain is None else args.denoise_gain)
     if args.coded_size is not None:
         fit.update(coded_size=args.coded_size)
+    if args.weighting is not None or args.roi or args.weight_map is not None:
+        fit.update(weighting=args.weighting, weight_strength=0.5 if args.weight_strength is None else args.weight_strength,
+                   weight_cell=args.weight_cell, roi=args.roi, weight_file=args.weight_map)
     if args.gop_frames is None:
         blob, log = encode_gop(args.video, dev, **fit)
         with open(args.output, "wb") as f:
@@ -155,7 +176,8 @@ def main(argv=None):
         gops.append({"first": first, "frames": count, "bytes": len(blob), "bpp": 8.0 * len(blob) / (H * W * count),
                      "fit_seconds": one["fit_seconds"], "cut": int(cut), "anchors_initial": one["anchors_initial"], "anchors_coded": one["anchors_coded"],
                      "sections": one["sections"], **({"grain": one["grain"]} if "grain" in one else {}),
-                     **({"denoise": one["denoise"]} if "denoise" in one else {}), **({"display": one["display"]} if "display" in one else {})})
+                     **({"denoise": one["denoise"]} if "denoise" in one else {}), **({"display": one["display"]} if "display" in one else {}),
+                     **({"weighting": one["weighting"]} if "weighting" in one else {})})
     fps = header.get("fps") or (30, 1)
     write_sequence(args.output, blobs, cW, cH, fps, flags)
     log = {"output": args.output, "W": cW, "H": cH, **({"display": {"W": W, "H": H, "filter": "lanczos3"}} if args.coded_size else {}), "frames": T, "steps": args.steps, "fit_seconds": fit_seconds,
