@@ -390,6 +390,7 @@ __global__ void __launch_bounds__(256) k_ans_model_many(AnsJobs t)
 
 using namespace gsvc;
 
+#include <atomic>
 #include <cmath>
 #include <mutex>
 
@@ -398,6 +399,7 @@ using namespace gsvc;
 // checksum (gsvc_ans_table_checksum) and the decoder compares it with its own before decoding.
 static uint32_t g_phi_host[PHI_STEPS + 1];
 static uint32_t g_phi_crc = 0;
+static std::atomic<bool> g_phi_uploaded{false};
 static int ensure_phi_table()
 {
     static std::once_flag once;
@@ -417,8 +419,26 @@ static int ensure_phi_table()
             set_error("ans: uploading the Phi table failed");
             rc = GSVC_E_LAUNCH;
         }
+        g_phi_uploaded.store(rc == GSVC_OK, std::memory_order_release);
     });
     return rc;
+}
+
+// What the coding entry points call.  The upload above is a synchronous copy, which a capturing stream must not see (it ends the
+// capture with an error): until the table is on the device, a call on a capturing stream is refused before anything is done.
+// gsvc_ans_table_checksum(), or any eager coding call, uploads it.
+static int ensure_phi_table_for(hipStream_t s)
+{
+    if (!g_phi_uploaded.load(std::memory_order_acquire)) {
+        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+        const hipError_t e = hipStreamIsCapturing(s, &st);
+        if (e != hipSuccess || st != hipStreamCaptureStatusNone) {
+            set_error("ans: the Phi table is not on the device yet and %s: call gsvc_ans_table_checksum() once before the capture",
+                      e != hipSuccess ? "the stream's capture state cannot be read (another stream may be capturing)" : "the stream is capturing");
+            return GSVC_E_UNSUPPORTED;
+        }
+    }
+    return ensure_phi_table();
 }
 
 extern "C" uint32_t gsvc_ans_table_checksum(void)
@@ -443,7 +463,7 @@ extern "C" int gsvc_ans_encode(const int32_t *symbols, const float *mu, const fl
                  "ans_encode: symbol range [%d, %d] does not fit 20-bit frequencies", min_symbol, max_symbol);
     if (n == 0) return GSVC_OK;
     GSVC_REQUIRE(symbols && mu && sigma && scratch && seg_bytes && seg_offsets && out && error_flag, "ans_encode: NULL pointer");
-    if (int rc = ensure_phi_table()) return rc;
+    if (int rc = ensure_phi_table_for((hipStream_t)stream)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int64_t n_seg = gsvc_ans_segments(n, seg_len);
     {
@@ -474,7 +494,7 @@ extern "C" int gsvc_ans_decode(const uint8_t *bytes, const uint64_t *seg_offsets
     if (n == 0) return GSVC_OK;
     GSVC_REQUIRE(bytes && seg_offsets && mu && sigma && symbols && error_flag && scratch, "ans_decode: NULL pointer");
     GSVC_REQUIRE((reinterpret_cast<uintptr_t>(scratch) & 15) == 0, "ans_decode: scratch must be 16-byte aligned");
-    if (int rc = ensure_phi_table()) return rc;
+    if (int rc = ensure_phi_table_for((hipStream_t)stream)) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int64_t n_seg = gsvc_ans_segments(n, seg_len);
     {
@@ -491,7 +511,7 @@ extern "C" int gsvc_ans_decode(const uint8_t *bytes, const uint64_t *seg_offsets
 extern "C" int gsvc_ans_decode_many(const gsvc_ans_decode_job *jobs, int32_t n_jobs, void *stream)
 {
     GSVC_REQUIRE(jobs && n_jobs >= 0, "ans_decode_many: bad arguments");
-    if (int rc = ensure_phi_table()) return rc;
+    if (int rc = ensure_phi_table_for((hipStream_t)stream)) return rc;
     hipStream_t s = (hipStream_t)stream;
     for (int j0 = 0; j0 < n_jobs;) {
         AnsJobs t;

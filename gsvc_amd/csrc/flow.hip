@@ -454,8 +454,8 @@ extern "C" int gsvc_flow_estimate(const float *luma0, const float *luma1, int64_
     int cur = 0;
     {
         const int h = L.h[L.levels - 1], w = L.w[L.levels - 1];
-        if (hipMemsetAsync(ws + L.field[0], 0, (size_t)n * 2 * h * w * sizeof(float), s) != hipSuccess) {
-            set_error("flow_estimate: hipMemsetAsync failed");
+        if (gsvc::zero_words_async(ws + L.field[0], (size_t)n * 2 * h * w * sizeof(float), s) != hipSuccess) {
+            set_error("flow_estimate: zeroing failed");
             return GSVC_E_LAUNCH;
         }
     }

@@ -253,8 +253,9 @@ inline int frames_sums_setup(const char *who, const FrameBufs &bufs, int32_t n, 
     const bool deep = depth > 8, rgb = layout == GSVC_FRAMES_RGB24;
     if (deep) GSVC_FRAMES_TRY(frames_check_even(who, bufs));
     GSVC_REQUIRE((reinterpret_cast<uintptr_t>(out) & (uintptr_t)(out_elem - 1)) == 0, "%s: out is not %d-byte aligned", who, out_elem);
-    if (hipMemsetAsync(out, 0, (size_t)n * (size_t)out_per_frame * (size_t)out_elem, s) != hipSuccess) {
-        set_error("%s: hipMemsetAsync failed", who);
+    GSVC_REQUIRE(out_elem % 4 == 0, "%s: sums of %d bytes", who, out_elem);
+    if (zero_words_async(out, (size_t)n * (size_t)out_per_frame * (size_t)out_elem, s) != hipSuccess) {
+        set_error("%s: zeroing failed", who);
         return GSVC_E_LAUNCH;
     }
     const int64_t px = (int64_t)H * W, chroma = layout == GSVC_FRAMES_YUV420P ? px / 4 : px;

@@ -918,8 +918,8 @@ extern "C" int gsvc_q_rows_backward(const float *g_feat, const float *g_scaling,
     if (D == 0) return GSVC_OK;
     GSVC_REQUIRE(grad_adj3 && (!raw || (adj_feat && adj_scaling && adj_offsets)), "q_rows_backward: NULL pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (ctx_row && hipMemsetAsync(grad_adj3, 0, sizeof(float) * 3 * (size_t)D, s) != hipSuccess) {
-        gsvc::set_error("q_rows_backward: hipMemsetAsync failed");
+    if (ctx_row && gsvc::zero_words_async(grad_adj3, sizeof(float) * 3 * (size_t)D, s) != hipSuccess) {
+        gsvc::set_error("q_rows_backward: zeroing failed");
         return GSVC_E_LAUNCH;
     }
     if (rows == 0) return GSVC_OK;

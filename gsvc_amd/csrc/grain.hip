@@ -339,8 +339,8 @@ extern "C" int gsvc_grain_stats(const uint8_t *src, int64_t src_stride, const ui
     GSVC_REQUIRE(max_residual >= 0 && max_residual <= 255, "grain_stats: max_residual must be 0 .. 255 (got %d)", (int)max_residual);
     GSVC_REQUIRE((reinterpret_cast<uintptr_t>(out) & 7) == 0, "grain_stats: out is not 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(out, 0, GS_ROWS * sizeof(uint64_t), s) != hipSuccess) {
-        set_error("grain_stats: hipMemsetAsync failed");
+    if (gsvc::zero_words_async(out, GS_ROWS * sizeof(uint64_t), s) != hipSuccess) {
+        set_error("grain_stats: zeroing failed");
         return GSVC_E_LAUNCH;
     }
     const bool sub = layout == GSVC_FRAMES_YUV420P;

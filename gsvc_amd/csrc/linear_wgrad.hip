@@ -575,8 +575,8 @@ extern "C" int gsvc_linear_wgrad(const float *G, const float *X, float *dW, floa
     GSVC_REQUIRE(dW, "linear_wgrad: NULL pointer");
     hipStream_t s = (hipStream_t)stream;
     if (M == 0) {
-        (void)hipMemsetAsync(dW, 0, sizeof(float) * (size_t)N * K, s);
-        if (db) (void)hipMemsetAsync(db, 0, sizeof(float) * (size_t)N, s);
+        (void)gsvc::zero_words_async(dW, sizeof(float) * (size_t)N * K, s);
+        if (db) (void)gsvc::zero_words_async(db, sizeof(float) * (size_t)N, s);
         return GSVC_OK;
     }
     return wgrad_launch(G, X, dW, db, db != nullptr, M, N, K, workspace, workspace_floats, s, "linear_wgrad", nullptr);

@@ -318,8 +318,8 @@ extern "C" int gsvc_optical_forward(const float *world1, const uint8_t *mask1, c
     GSVC_REQUIRE(table && sums && partial && (n1 == 0 || (world1 && mask1 && vis1 && partner)) && (n2 == 0 || (world2 && mask2 && vis2)) && flow,
                  "optical_forward: NULL pointer");
     hipStream_t s = (hipStream_t)stream;
-    (void)hipMemsetAsync(table, 0, sizeof(int32_t) * (size_t)anchors * K, s);
-    (void)hipMemsetAsync(sums, 0, 2 * sizeof(float), s);      // stays (0, 0) when render 1 is empty
+    (void)gsvc::zero_words_async(table, sizeof(int32_t) * (size_t)anchors * K, s);
+    (void)gsvc::zero_words_async(sums, 2 * sizeof(float), s);      // stays (0, 0) when render 1 is empty
     if (n2) {
         ProfScope _p("k_optical_mark", s);
         hipLaunchKernelGGL(k_optical_mark, dim3((unsigned)((n2 + 255) / 256)), dim3(256), 0, s, mask2, vis2, n2, K, table);
@@ -339,8 +339,8 @@ extern "C" int gsvc_optical_backward(const int32_t *partner, int64_t n1, int64_t
 {
     GSVC_REQUIRE(sums && grad_out && (n1 == 0 || (partner && grad_world1)) && (n2 == 0 || grad_world2), "optical_backward: NULL pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (n1) (void)hipMemsetAsync(grad_world1, 0, sizeof(float) * 3 * (size_t)n1, s);
-    if (n2) (void)hipMemsetAsync(grad_world2, 0, sizeof(float) * 3 * (size_t)n2, s);
+    if (n1) (void)gsvc::zero_words_async(grad_world1, sizeof(float) * 3 * (size_t)n1, s);
+    if (n2) (void)gsvc::zero_words_async(grad_world2, sizeof(float) * 3 * (size_t)n2, s);
     if (n1) {
         ProfScope _p("k_optical_bwd", s);
         hipLaunchKernelGGL(k_optical_bwd, dim3((unsigned)((n1 + 255) / 256)), dim3(256), 0, s, partner, n1, sums, grad_out, grad_world1,
@@ -443,8 +443,8 @@ extern "C" int gsvc_optical_many_forward(const float *world, const uint8_t *mask
     GSVC_REQUIRE(table && partner && sums && partial && loss && flow && (ob.goff[R] == 0 || (world && mask && vis)),
                  "optical_many_forward: NULL pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(table, 0, sizeof(int32_t) * (size_t)R * anchors, s) != hipSuccess) {
-        set_error("optical_many_forward: hipMemsetAsync failed");
+    if (gsvc::zero_words_async(table, sizeof(int32_t) * (size_t)R * anchors, s) != hipSuccess) {
+        set_error("optical_many_forward: zeroing failed");
         return GSVC_E_LAUNCH;
     }
     const int64_t rows = ob.goff[R] / K;

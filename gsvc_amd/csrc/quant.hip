@@ -350,8 +350,8 @@ extern "C" int gsvc_ste_binary_count(const float *x, int64_t n, float *y, float 
     GSVC_REQUIRE(n >= 0 && n < (1ll << 24), "ste_binary_count: the count must stay exact in float32 (n < 2^24)");
     GSVC_REQUIRE(count, "ste_binary_count: NULL pointer");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(count, 0, sizeof(float), s) != hipSuccess) {
-        gsvc::set_error("ste_binary_count: hipMemsetAsync failed");
+    if (gsvc::zero_words_async(count, sizeof(float), s) != hipSuccess) {
+        gsvc::set_error("ste_binary_count: zeroing failed");
         return GSVC_E_LAUNCH;
     }
     if (n == 0) return GSVC_OK;
@@ -386,8 +386,8 @@ extern "C" int gsvc_ste_binary_count_many(const float *const *x, float *const *y
     int blocks = 0;
     GSVC_REQUIRE(ste_fill(x, nullptr, y, n, tables, t, blocks) && counts, "ste_binary_count_many: 1..8 tables of fewer than 2^24 entries");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(counts, 0, sizeof(float) * tables, s) != hipSuccess) {
-        gsvc::set_error("ste_binary_count_many: hipMemsetAsync failed");
+    if (gsvc::zero_words_async(counts, sizeof(float) * tables, s) != hipSuccess) {
+        gsvc::set_error("ste_binary_count_many: zeroing failed");
         return GSVC_E_LAUNCH;
     }
     if (blocks == 0) return GSVC_OK;

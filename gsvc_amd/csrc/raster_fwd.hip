@@ -1511,8 +1511,8 @@ static int raster_forward_impl(const char *ex_fn, const gsvc_raster_settings *se
     auto *n_contrib = (int32_t *)((char *)image_state + L.off_n_contrib);
 
     // counters + tile_offsets + tile_count + tile_extra are contiguous at the head of the blob
-    if (hipMemsetAsync(bin, 0, L.off_big_list, s) != hipSuccess) {
-        set_error("raster_forward: hipMemsetAsync failed");
+    if (zero_words_async(bin, L.off_big_list, s) != hipSuccess) {
+        set_error("raster_forward: zeroing failed");
         return GSVC_E_LAUNCH;
     }
     if (P > 0) {

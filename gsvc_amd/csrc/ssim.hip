@@ -205,8 +205,8 @@ static int ssim_forward_impl(const float *img1, const float *img1b, float *avg_o
     GSVC_REQUIRE((dm_dmu1 && dm_de11 && dm_de12) || (!dm_dmu1 && !dm_de11 && !dm_de12),
                  "ssim_l1_forward: pass all three partial maps or none");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(workspace, 0, 2 * SS_SLOTS * sizeof(float), s) != hipSuccess) {
-        set_error("ssim_l1_forward: hipMemsetAsync failed");
+    if (gsvc::zero_words_async(workspace, 2 * SS_SLOTS * sizeof(float), s) != hipSuccess) {
+        set_error("ssim_l1_forward: zeroing failed");
         return GSVC_E_LAUNCH;
     }
     static const SsimWindow win = make_loss_window();

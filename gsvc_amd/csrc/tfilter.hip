@@ -299,8 +299,8 @@ extern "C" int gsvc_noise_sums(const uint8_t *frames, int64_t stride, int32_t n,
     GSVC_FRAMES_TRY(tfilter_check_frames(who, bufs, n, GSVC_FRAMES_MAX_BATCH, H, W, layout, depth));
     GSVC_REQUIRE((reinterpret_cast<uintptr_t>(out) & 7) == 0, "noise_sums: out is not 8-byte aligned");
     hipStream_t s = (hipStream_t)stream;
-    if (hipMemsetAsync(out, 0, (size_t)n * 3 * sizeof(uint64_t), s) != hipSuccess) {
-        set_error("noise_sums: hipMemsetAsync failed");
+    if (gsvc::zero_words_async(out, (size_t)n * 3 * sizeof(uint64_t), s) != hipSuccess) {
+        set_error("noise_sums: zeroing failed");
         return GSVC_E_LAUNCH;
     }
     const bool sub = layout == GSVC_FRAMES_YUV420P;

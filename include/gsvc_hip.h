@@ -37,7 +37,16 @@
  *   - plain pointers and sizes only; every pointer is DEVICE memory unless its name ends in _host;
  *   - the caller owns every buffer (outputs, scratch blobs); nothing is allocated or freed inside, nothing
  *     synchronises the device, so every call may be captured into a hipGraph;
- *   - every call is enqueued on `stream` (a hipStream_t passed as void*);
+ *   - every call is enqueued on `stream` (a hipStream_t passed as void*): every kernel and helper kernel of it (buffers an entry
+ *     zeroes are zeroed by a kernel, not by hipMemsetAsync: csrc/common.h, zero_words_async);
+ *   - before a capture, make one eager call through each entry family the graph will hold: a process's first call through a family
+ *     may set kernel attributes, and the entropy coder's first use uploads its Phi table with a synchronous copy (see
+ *     gsvc_ans_table_checksum);
+ *   - what is tested of this: tests/test_abi_contract_gpu.py captures and replays one case per entry family of the fitting step and
+ *     the decoder, the rasterizer's forward and backward have their own graph test.  NOT established: capture of
+ *     gsvc_generate_all_forward / _backward (the inference forward included), whose case stopped the device and was withdrawn, and
+ *     of the front-end analysis entries (flow, detail, scene, tfilter, frames_from_*, frames_sse, msssim, grain_stats, block_sse,
+ *     knn), which have no case;
  *   - return value: 0 = ok, negative = GSVC_E_*; gsvc_last_error() gives the message of the calling
  *     thread's last failure;
  *   - float = IEEE binary32, row-major, contiguous.
@@ -556,7 +565,11 @@ int gsvc_knn3_mean_dist2(const float *points_by_cell, const int32_t *cell_start,
 /* number of segments / bytes of encode scratch for n symbols */
 int64_t gsvc_ans_segments(int64_t n, int32_t seg_len);
 /* checksum of the fixed-point Phi table encoder and decoder build their frequencies from: a stream records it, a decoder
- * whose own table differs (another platform's erfc rounded an entry the other way) must refuse the stream */
+ * whose own table differs (another platform's erfc rounded an entry the other way) must refuse the stream.
+ * The first call of a process to this or to gsvc_ans_encode / _decode / _decode_many builds the table and uploads it with a
+ * synchronous copy (nothing after that).  That copy must not meet a capturing stream: call gsvc_ans_table_checksum() once before
+ * capturing a coder call.  Until the table is on the device, gsvc_ans_encode / _decode / _decode_many on a stream that is capturing
+ * return GSVC_E_UNSUPPORTED without doing anything (the capture itself goes on). */
 uint32_t gsvc_ans_table_checksum(void);
 int64_t gsvc_ans_scratch_bytes(int64_t n, int32_t seg_len);
 

@@ -38,6 +38,44 @@ def test_library_exports_every_declared_symbol(hip_lib):
     assert hip_lib.lib().gsvc_version().startswith(b"gsvc_hip")
 
 
+def test_every_entry_point_has_a_stream_contract_case_or_a_stated_reason(hip_lib):
+    """tests/_abi_contract_cases.py against the header and the binding's signature table: an entry point that takes a stream is the
+    `entries` of exactly one case of tests/test_abi_contract_gpu.py, or one of the rasterizer's forward / backward entries (which keep
+    their own graph test), or stands in WITHDRAWN (a case that was taken out again, with what happened), or in NOT_COVERED with a reason — a capped table that may hold front-end analysis entries only; an
+    entry point without a stream stands in NO_STREAM.  A new entry point cannot land without its case."""
+    from tests import _abi_contract_cases as A
+    streamed = A.streamed_entries()
+    declared = A.header_entries()
+    assert sorted(declared) == hip_lib.declared_symbols()
+    for name, at in streamed.items():       # the header's `void *stream` is a void pointer of the binding, the last but for one entry
+        args = hip_lib._SIGNATURES[name][1]
+        assert args[at] is C.c_void_p and (at == len(args) - 1 or name == "gsvc_generate_all_backward"), name
+    owners = {}
+    for case in A.CASES:
+        assert case.entries, case
+        for name in case.entries:
+            owners.setdefault(name, []).append(case.name)
+        assert set(case.also) <= set(streamed) and not set(case.also) & set(case.entries), case
+    twice = {n: o for n, o in owners.items() if len(o) > 1}
+    assert not twice, twice
+    assert len({case.name for case in A.CASES}) == len(A.CASES)
+    tables = [set(owners), set(A.NOT_COVERED), set(A.RASTER_GRAPH_TEST), set(A.WITHDRAWN), set(A.NO_STREAM)]
+    for i, a in enumerate(tables):
+        for b in tables[i + 1:]:
+            assert not a & b, sorted(a & b)
+    covered_or_excused = tables[0] | tables[1] | tables[2] | tables[3]
+    orphans = sorted(set(streamed) - covered_or_excused)
+    assert not orphans, f"entry points with a stream argument and no contract case: {orphans}"
+    assert covered_or_excused <= set(streamed), sorted(covered_or_excused - set(streamed))
+    assert set(A.NO_STREAM) == set(declared) - set(streamed), sorted(set(A.NO_STREAM) ^ (set(declared) - set(streamed)))
+    assert all(also in owners for case in A.CASES for also in case.also)
+    assert len(A.NOT_COVERED) <= A.NOT_COVERED_CAP and set(A.NOT_COVERED) <= A.FRONT_END, sorted(set(A.NOT_COVERED) - A.FRONT_END)
+    assert all(isinstance(r, str) and r for r in list(A.NOT_COVERED.values()) + list(A.WITHDRAWN.values()) + list(A.NO_STREAM.values()))
+    assert all(n.startswith("gsvc_raster_") for n in A.RASTER_GRAPH_TEST)
+    # WITHDRAWN is no second NOT_COVERED: it holds the two entries of the one case that was taken out, and nothing can be added to it
+    assert set(A.WITHDRAWN) == {"gsvc_generate_all_forward", "gsvc_generate_all_backward"}
+
+
 def test_host_side_validation_without_gpu(hip_lib):
     L = hip_lib.lib()
     s = hip_lib.RasterSettingsC()
