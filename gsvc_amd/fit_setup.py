@@ -5,6 +5,21 @@ fitted, stream-encoded and verified into the bytes of one bitstream file (a whol
 The reference's schedule (pipeline/train.py:325-583: 10 k full precision / 5 k quantised / 20 k entropy-constrained / 5 k
 straight-through; statistics from 500, densification 1 500 .. 25 000 every 100, paused 1 000 iterations at the first phase change) is
 scaled to ``steps`` iterations with the same proportions.
+
+``encode_gop`` takes one ``encode_options.EncodeOptions`` and runs these stages in this order, each a function below; the measures decode
+through ``decoded_batches`` and open the file again through ``source_range``, and ``release`` returns a stage's device memory before the next:
+
+    stage              what it does                                                                   the log keys it writes
+    prepare_source     denoise, coded_size: the prefilter at source size, then the resampler          "denoise" (stands behind "steps")
+    source_cube        the VideoFileCube of those frames, or of the file's own
+    fit_gop            flow, schedule, new_fit, the steps, conduct_stream_encoding -> the file image  "W" "H" "frames" "steps" "init" ("init_cell" "init_mix")
+                                                                                                      "anchors_initial" "loss_domain" "loss_matrix" "distortion"
+                                                                                                      "fit_seconds" "anchors_coded"
+    verify_decode      the decoder's own path on the image; its hashes become the section PHSH        "hash_format" "verify_decode_fps"
+    measure_weighting  a weighted fit: one more decode against the frames the fit saw                 "weighting"
+    measure_display    coded_size: the section DISP, one more decode at display size                  "display"
+    measure_grain      film_grain: one more decode against the source, the section GRAN               "grain"
+    encode_gop         the section sizes of the final image                                           "sections"
 """
 from __future__ import annotations
 
@@ -67,232 +82,180 @@ def new_fit(cube, mp_, opt, pipe, anchors: int, device, init: str = "uniform", i
     pc.update_anchor_bound(cube.x_min, cube.y_min, cube.z_min)
     pc.training_setup(opt)
     gdist.broadcast_parameters(pc)
-    if maps is None:
-        trainer = Trainer(pc, cube, opt, pipe, mp_, seed=0)
-    else:
-        trainer = Trainer(pc, cube, opt, pipe, mp_, seed=0, weight_maps=maps, weight_cell=weighting_info["cell"])
+    trainer = Trainer(pc, cube, opt, pipe, mp_, seed=0, weight_maps=maps, weight_cell=weighting_info and weighting_info["cell"])
     trainer.weighting = weighting_info
     return pc, trainer
 
 
-def grain_statistics(bs, source_frames, H: int, W: int, fmt, device, batch: int = 8, flat_threshold=None, max_residual=None):
-    """The film-grain statistics of a file image against its source: ``bs`` (a parsed ``Bitstream``) is decoded into ``fmt``, the SOURCE's
-    own format, batch by batch, each batch's ``grain.grain_stats`` against the source's codes (``source_frames``: the host array
-    ``[T, frame_bytes]`` of ``frames_in.open_video``, uploaded a batch at a time) is taken on the device, and the batches are summed on
-    the host as Python ints -> nested lists ``[3][16][6]``.  ``flat_threshold``, ``max_residual``: the two rejection thresholds of
-    ``grain.grain_stats`` (None: its defaults, which are starting values)."""
+def decoded_batches(bs, fmt, device, batch: int = 8, out_size=None):
+    """Decode ``bs`` (a parsed ``Bitstream``) into ``fmt`` on the device, render batch by render batch (``render_frames_u8`` with
+    ``to_host=False``; at ``out_size = (H, W)`` when given) -> a generator of ``(first_frame, rows)``, ``rows`` uint8 ``[n, frame_bytes]``
+    on the device.  ``batch`` is the render batch: a frame's bits depend on whether it was rendered in a batch of one."""
     from .frames_out import render_frames_u8
+    pc, cams, pipe, bg = bs.build_model(device)
+    frames = render_frames_u8(cams, pc, pipe, bg, fmt=fmt, batch=int(batch), to_host=False, out_size=out_size)
+    try:
+        for first in range(0, len(cams), int(batch)):
+            with torch.no_grad():          # (around the render alone: a generator must not leave the mode on for its caller)
+                rows = torch.stack([next(frames) for _ in range(min(int(batch), len(cams) - first))])
+            yield first, rows
+    finally:
+        with torch.no_grad():          # (the render loop restores the mode it started in when it ends: it ends here, not when collected)
+            frames.close()
+
+
+def decoded_against(bs, source_frames, fmt, device, what: str, batch: int = 8, out_size=None, has: str = "the source has"):
+    """``decoded_batches`` paired with the source's codes -> a generator of ``(rows, source rows)``: ``source_frames`` is the host array
+    ``[T, frame_bytes]`` of ``frames_in.open_video``, uploaded a batch at a time.  A ``ValueError`` at the end when the file decodes to
+    another number of frames than ``source_frames`` has."""
+    got, T = 0, int(source_frames.shape[0])
+    for first, rows in decoded_batches(bs, fmt, device, batch, out_size):
+        got = first + int(rows.shape[0])
+        yield rows, torch.from_numpy(np.ascontiguousarray(source_frames[first:got])).to(rows.device)
+    if got != T:
+        raise ValueError(f"{what}: the file decodes to {got} frames, {has} {T}")
+
+
+def grain_statistics(bs, source_frames, H: int, W: int, fmt, device, batch: int = 8, flat_threshold=None, max_residual=None):
+    """The film-grain statistics of a file image against its source: ``bs`` is decoded into ``fmt``, the SOURCE's own format, each
+    batch's ``grain.grain_stats`` against the source's codes is taken on the device, and the batches are summed on the host as Python
+    ints -> nested lists ``[3][16][6]``.  ``flat_threshold``, ``max_residual``: the two rejection thresholds of ``grain.grain_stats``
+    (None: its defaults, which are starting values)."""
     from .grain import BINS, DEFAULT_FLAT_THRESHOLD, DEFAULT_MAX_RESIDUAL, grain_stats
     flat = DEFAULT_FLAT_THRESHOLD if flat_threshold is None else int(flat_threshold)
     worst = DEFAULT_MAX_RESIDUAL if max_residual is None else int(max_residual)
-    total = [[[0] * 6 for _ in range(BINS)] for _ in range(3)]
-    pc, cams, pipe, bg = bs.build_model(device)
-    at = [0]
-
-    def take(rows):
-        n = int(rows.shape[0])
-        src = torch.from_numpy(np.ascontiguousarray(source_frames[at[0]:at[0] + n])).to(rows.device)
-        part = grain_stats(src, rows, H, W, fmt, flat_threshold=flat, max_residual=worst).cpu().tolist()
-        for p in range(3):
-            for b in range(BINS):
-                for j in range(6):
-                    total[p][b][j] += int(part[p][b][j])
-        at[0] += n
-
-    with torch.no_grad():
-        for _ in render_frames_u8(cams, pc, pipe, bg, fmt=fmt, batch=int(batch), to_host=False, on_device_batch=take):
-            pass
-    if at[0] != int(source_frames.shape[0]):
-        raise ValueError(f"grain_statistics: the file decodes to {at[0]} frames, the source has {int(source_frames.shape[0])}")
-    return total
+    parts = [grain_stats(src, rows, H, W, fmt, flat_threshold=flat, max_residual=worst).cpu().tolist()
+             for rows, src in decoded_against(bs, source_frames, fmt, device, "grain_statistics", batch)]
+    return [[[sum(part[p][b][j] for part in parts) for j in range(6)] for b in range(BINS)] for p in range(3)]
 
 
 def display_psnr(bs, source_frames, fmt, device, batch: int = 8):
-    """What a reduced-resolution file delivers against its source: ``bs`` (a parsed ``Bitstream`` with a DISP section) is decoded into
-    ``fmt``, the SOURCE's own format, at display size, batch by batch, and each batch's ``metrics.plane_sse`` against the source's codes
-    (``source_frames``: the host array ``[T, frame_bytes]`` at display size, uploaded a batch at a time) is summed over all frames ->
-    ``(psnr_y, psnr_611)``, the latter ``(6 Y + U + V) / 8`` of the three plane PSNRs."""
-    from .frames_out import render_frames_u8
+    """What a reduced-resolution file delivers against its source: ``bs`` (with a DISP section) is decoded into ``fmt``, the SOURCE's own
+    format, at display size, and each batch's ``metrics.plane_sse`` against the source's codes (``source_frames`` at display size) is
+    summed over all frames -> ``(psnr_y, psnr_611)``, the latter ``(6 Y + U + V) / 8`` of the three plane PSNRs."""
     from .metrics import plane_samples, plane_sse, psnr_of_sse
     W, H = bs.display_size
-    cW, cH = bs.coded_size
-    pc, cams, pipe, bg = bs.build_model(device)
     total = torch.zeros(3, dtype=torch.int64, device=device)
-    got, rows = 0, []
-    with torch.no_grad():
-        for row in render_frames_u8(cams, pc, pipe, bg, fmt=fmt, batch=int(batch), to_host=False,
-                                    out_size=None if (W, H) == (cW, cH) else (H, W)):
-            rows.append(row)
-            if len(rows) == int(batch) or got + len(rows) == len(cams):
-                src = torch.from_numpy(np.ascontiguousarray(source_frames[got:got + len(rows)])).to(row.device)
-                total += plane_sse(torch.stack(rows), src, H, W, fmt).sum(dim=0)
-                got += len(rows)
-                rows = []
-    if got != int(source_frames.shape[0]):
-        raise ValueError(f"display_psnr: the file decodes to {got} frames, the source has {int(source_frames.shape[0])}")
-    peak = float((1 << fmt.depth) - 1)
-    samples = torch.tensor(plane_samples(H, W, fmt), dtype=torch.float64, device=total.device) * got
-    p = [float(v) for v in psnr_of_sse(total, samples, peak).tolist()]
+    out_size = None if (W, H) == tuple(bs.coded_size) else (H, W)
+    for rows, src in decoded_against(bs, source_frames, fmt, device, "display_psnr", batch, out_size):
+        total += plane_sse(rows, src, H, W, fmt).sum(dim=0)
+    samples = torch.tensor(plane_samples(H, W, fmt), dtype=torch.float64, device=total.device) * int(source_frames.shape[0])
+    p = [float(v) for v in psnr_of_sse(total, samples, float((1 << fmt.depth) - 1)).tolist()]
     return p[0], (6.0 * p[0] + p[1] + p[2]) / 8.0
 
 
 def coded_wpsnr(bs, fit_frames, fmt, weight_maps, cell: int, device, batch: int = 8):
-    """What a weighted fit bought, on the delivered codes: ``bs`` (a parsed ``Bitstream``) is decoded into ``fmt``, the format of the frames
-    the fit was given, at the size it was fitted at, batch by batch, and each batch's ``wdist.block_sse`` against those frames
-    (``fit_frames``: the host array ``[T, frame_bytes]``, uploaded a batch at a time) is kept -> ``(psnr_y, wpsnr_y)`` pooled over the
-    frames: the plain luma PSNR and ``wdist.weighted_psnr_y`` under ``weight_maps`` ``[T, Hc, Wc]``."""
-    from .frames_out import render_frames_u8
+    """What a weighted fit bought, on the delivered codes: ``bs`` is decoded into ``fmt``, the format of the frames the fit was given, at
+    the size it was fitted at, and each batch's ``wdist.block_sse`` against those frames (``fit_frames``) is kept -> ``(psnr_y, wpsnr_y)``
+    pooled over the frames: the plain luma PSNR and ``wdist.weighted_psnr_y`` under ``weight_maps`` ``[T, Hc, Wc]``."""
     from .wdist import block_sse, weighted_psnr_y
     W, H = bs.coded_size
-    pc, cams, pipe, bg = bs.build_model(device)
-    blocks, rows, got = [], [], 0
-    with torch.no_grad():
-        for row in render_frames_u8(cams, pc, pipe, bg, fmt=fmt, batch=int(batch), to_host=False):
-            rows.append(row)
-            if len(rows) == int(batch) or got + len(rows) == len(cams):
-                src = torch.from_numpy(np.ascontiguousarray(fit_frames[got:got + len(rows)])).to(row.device)
-                blocks.append(block_sse(torch.stack(rows), src, H, W, fmt, cell).cpu())
-                got += len(rows)
-                rows = []
-    if got != int(fit_frames.shape[0]):
-        raise ValueError(f"coded_wpsnr: the file decodes to {got} frames, the fit saw {int(fit_frames.shape[0])}")
-    sse = torch.cat(blocks)
+    sse = torch.cat([block_sse(rows, src, H, W, fmt, cell).cpu()
+                     for rows, src in decoded_against(bs, fit_frames, fmt, device, "coded_wpsnr", batch, has="the fit saw")])
     _, plain = weighted_psnr_y(sse, torch.ones(sse.shape, dtype=torch.float64), fmt.depth, H, W)
     _, weighted = weighted_psnr_y(sse, weight_maps, fmt.depth, H, W)
     return plain, weighted
 
 
-def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float = 0.004, anchors: int = 100_000, slab_frames: float = 16.0,
-               densify_grad_threshold=None, estimate_flow: bool = False, flow_dir=None, video_size=(None, None), video_format=None,
-               hash_format=None, loss_domain: str = "rgb", init: str = "uniform", init_cell: int = 8, init_mix: float = 0.25,
-               distortion: str = "ssim", film_grain: bool = False, grain_gain: float = 1.0, grain_seed=None,
-               grain_flat_threshold=None, grain_max_residual=None, denoise=None, denoise_gain: float = 1.0, coded_size=None,
-               weighting=None, weight_strength: float = 0.5, weight_cell=None, roi=None, weight_file=None):
-    """One group of pictures of a video file -> ``(the bytes of a complete GSVC file, log)``: what tools/gsvc_encode.py does with a whole
-    clip, for the frames ``frame_range = (first, stop)`` of it (None: all).  VideoFileCube (optionally with the flow estimated from the
-    frames) -> the fit -> ``conduct_stream_encoding`` with 8-bit MLPs -> the file image; that image is then decoded into a null sink by
-    the function, batch size and format the decoder will use (``decode_video``), which yields the picture hashes it is given as its PHSH
-    section.  The trainer, the cube and the model are released before this returns.  ``loss_domain``: where the fit takes its
-    distortion (``OptimizationParams.loss_domain``; the bitstream and the decoder are the same for every domain); ``distortion``: its
-    structural term, "ssim" or "ms_ssim" (``OptimizationParams.distortion``).  ``film_grain``: after the verification decode the file
-    image is decoded once more, into the SOURCE's own format, and the flat-block statistics of the source's codes against it
-    (``grain_statistics``) are fitted to film-grain parameters (``grain.fit_grain`` with ``grain_gain``; ``grain_seed`` None: a seed
-    derived from the file image; ``grain_flat_threshold``, ``grain_max_residual`` None: the defaults of ``grain.grain_stats``), which the
-    file carries as its GRAN section; the picture hashes stay those of the ungrained
-    pictures, and an ``rgb24`` source is a ``ValueError`` before the fit starts.  The log then has "grain": {"seed", "scale", "kx", "ky",
-    "source", "blocks", "gain"}.  ``denoise``: None (the default: the source as it is), "auto" or a noise sigma in codes: the frames of
-    ``frame_range`` are first put through the motion-compensated temporal prefilter (``tfilter.denoise_frames`` with ``denoise_gain``; one
-    GOP, so nothing is filtered across its ends) and the fit is given the filtered frames; an ``rgb24`` source is a ``ValueError``.  The log
-    then has "denoise": {"sigma", "q", "source", "gain", "psnr_y"}.  With ``film_grain`` as well the grain statistics stay measured
-    against the ORIGINAL source (``video`` is reopened for them), so the grain the prefilter removed is what the decoder puts back.
-    ``coded_size=(Wc, Hc)`` (None: the source's size): reduced-resolution coding (gsvc_amd/resample.py).  The frames of ``frame_range``
-    — with ``denoise`` the filtered ones, filtered at source size — are resampled on the device, in chunks of 16, to ``Wc x Hc`` in the
-    source's own format, and the fit is given the resampled frames (``estimate_flow`` estimates on them); HEAD carries the coded size,
-    the section DISP the source's size and the filter, PHSH the hashes of the coded-size pictures.  The file image is then decoded
-    once more, into the source's format at display size, and compared with the ORIGINAL source's codes (``metrics.plane_sse`` over all
-    frames): "W" / "H" of the log are the coded size and the log has "display": {"W", "H", "filter": "lanczos3", "psnr_y", "psnr_611":
-    (6 Y + U + V) / 8 of the plane PSNRs}.  A ``ValueError`` before anything is fitted: ``flow_dir`` (those flows are at source size) or
-    ``film_grain`` with ``coded_size``, an ``rgb24`` source, a ratio above 4, an odd size for 4:2:0.  ``init``,
-    ``init_cell``, ``init_mix``: where the fit's first anchors come from (``new_fit``; anchors are coded wherever they are).  ``log``:
-    {"W", "H", "frames", "steps", "init", ("init_cell", "init_mix": with init="detail" only), "anchors_initial": the anchors after the
-    voxel merge of ``create_from_points``, "loss_domain", "loss_matrix", "distortion", "anchors_coded", "fit_seconds", "hash_format",
-    "verify_decode_fps", "sections"}.  ``weighting="activity"`` (with ``weight_strength``), ``roi=[(x, y, w, h, weight), ...]`` in the
-    SOURCE's pixels, ``weight_file`` (a ``.npy``), all at cells of ``weight_cell`` pixels (None: 8): spatially weighted distortion
-    (``new_fit``, gsvc_amd/wdist.py).  The maps are built on the frames the fit sees — of this ``frame_range`` alone, filtered and at
-    coded size where those are asked for, rectangles scaled to it — and only shape the fit: the file's sections are what they were.  The
-    file image is then decoded once more, into the format and size of those frames, and the log has "weighting": {"sources", "cell",
-    ("strength", "clamp": activity), ("roi": the scaled rectangles), "min", "max", "psnr_y", "wpsnr_y": ``coded_wpsnr``}; an ``rgb24``
-    source is a ``ValueError`` before the fit starts.  Without these arguments the log has no such entry."""
+def release():
+    """Return what a finished stage held to the device: unreachable objects are collected and the allocator's cache is emptied."""
     import gc
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
+def source_range(video, frame_range, options):
+    """The frames ``frame_range = (first, stop)`` (None: all) of the video file as it is -> ``(header, host array [T, frame_bytes])`` of
+    ``frames_in.open_video`` (memory-mapped: a stage that needs them opens the file again).  ``ValueError``: no non-empty range inside it."""
+    from .frames_in import open_video
+    hdr, source = open_video(video, options.video_size[0], options.video_size[1], options.video_format)
+    if frame_range is None:
+        return hdr, source
+    try:
+        first, stop = (int(v) for v in frame_range)
+    except (TypeError, ValueError):
+        raise ValueError(f"encode_gop: frame_range must be (first, stop) (got {frame_range!r})") from None
+    if not 0 <= first < stop <= int(source.shape[0]):          # (what VideoFileCube refuses, before anything is filtered)
+        raise ValueError(f"encode_gop: frame_range ({first}, {stop}) is not a non-empty range inside the {int(source.shape[0])} "
+                         f"frames of {video}")
+    return hdr, source[first:stop]
+
+
+def prepare_source(video, device, frame_range, options):
+    """``denoise`` and ``coded_size`` -> ``(frames, coded_size, display_size, denoise_log)``.  The frames of ``frame_range`` are put through
+    the motion-compensated temporal prefilter at the source's size (``tfilter.denoise_range`` with ``denoise_gain``; one range, so
+    nothing is filtered across its ends), then resampled on the device to the coded size in the source's own format
+    (``resample.resample_range``): ``frames`` is the host array the fit is to be given, ``coded_size`` and ``display_size`` its and the
+    source's ``(W, H)``.  Each is None where its option is off; with both off the file is not opened.  A ``ValueError`` before anything is
+    filtered: an ``rgb24`` source, and what ``resample.check_sizes`` refuses (a ratio above 4, an odd size for 4:2:0).
+    Log entry: "denoise": {"sigma", "q", "source", "gain", "psnr_y"}, handed on as ``denoise_log``."""
+    frames, denoise_log, size = None, None, options.frame_size
+    if options.denoise is None and size is None:
+        return None, None, None, None
+    hdr, source = source_range(video, frame_range, options)
+    H, W, fmt = int(hdr["H"]), int(hdr["W"]), hdr["fmt"]
+    if fmt.layout == "rgb24":
+        raise ValueError("encode_gop: the temporal prefilter and the resampler work on Y'CbCr codes; an rgb24 source has none")
+    if size is not None:
+        from .resample import check_sizes, resample_range
+        check_sizes(H, W, size[1], size[0], fmt, "encode_gop: coded_size")
+    if options.denoise is not None:
+        from .tfilter import denoise_range
+        frames, denoise_log = denoise_range(source, H, W, fmt, device, sigma=options.denoise, gain=float(options.denoise_gain))
+    if size is not None:
+        frames = resample_range(source if frames is None else frames, H, W, fmt, size[1], size[0], device)
+    return frames, size, (W, H) if size is not None else None, denoise_log
+
+
+def source_cube(video, device, frame_range, options, frames=None, coded_size=None):
+    """The ``VideoFileCube`` of the fit: the frames of ``frame_range`` of the file, or ``frames`` at ``coded_size`` in their place (what
+    ``prepare_source`` returned).  An ``rgb24`` source with weights or ``film_grain`` is a ``ValueError`` here, before the fit starts."""
+    from .frames_in import VideoFileCube
+    cube = VideoFileCube(video, optical_flow_dir=options.flow_dir, W=options.video_size[0], H=options.video_size[1],
+                         fmt=options.video_format, device=device, frame_range=frame_range, frames=frames, frame_size=coded_size)
+    if options.weighted and cube.fmt.layout == "rgb24":
+        raise ValueError("encode_gop: the weighted PSNR of a weighted fit is taken on luma codes; an rgb24 source has none")
+    if options.film_grain and cube.fmt.layout == "rgb24":
+        raise ValueError("encode_gop: film grain is measured and synthesised in the delivered Y'CbCr domain; an rgb24 source has none")
+    return cube
+
+
+def fit_gop(cube, device, options, display_size=None, denoise_log=None):
+    """The fit and the stream encode -> ``(image, log, weights)``.  The flow of the cube (estimated on its frames, of ``flow_dir``, or
+    none: ``optical_lambda = 0``) -> ``configure_fit`` and ``new_fit`` -> ``steps`` steps -> ``conduct_stream_encoding`` with 8-bit MLPs ->
+    ``bitstream_bytes``: the file image, still without picture hashes.  ``weights``: None, or for a weighted fit (what a log says of the
+    maps, the maps on the host); they are built on the cube's frames, the rectangles of ``roi`` scaled from ``display_size`` to them.
+    Log entries: "W", "H", "frames", "steps", ("denoise": ``denoise_log``), "init", ("init_cell", "init_mix": with init="detail" only),
+    "anchors_initial": the anchors after the voxel merge of ``create_from_points``, "loss_domain", "loss_matrix", "distortion",
+    "fit_seconds", "anchors_coded"."""
     import os
     import tempfile
     import time
 
     from .arguments import cfg_20240919
-    from .bitstream import CubeGeometry, NullSink, bitstream_bytes, decode_video, parse_bitstream, unpack_sections, with_hashes
-    from .frames_in import VideoFileCube
-    from .frames_out import FrameFormat
+    from .bitstream import CubeGeometry, bitstream_bytes
     from .stream_codec import conduct_stream_encoding
+    o, geometry_source = options, cube
     mp_, opt, pipe = cfg_20240919()
-    filtered, denoise_log, frame_size = None, None, None
-    weighted = weighting is not None or bool(roi) or weight_file is not None
-    if coded_size is not None:
-        try:
-            frame_size = tuple(int(v) for v in coded_size)
-        except (TypeError, ValueError):
-            frame_size = ()
-        if len(frame_size) != 2:
-            raise ValueError(f"encode_gop: coded_size must be (W, H) (got {coded_size!r})")
-        if flow_dir is not None:
-            raise ValueError("encode_gop: the flows of flow_dir are at the source's size; with coded_size use estimate_flow")
-        if film_grain:
-            raise ValueError("encode_gop: film_grain with coded_size is not supported (the grain would be measured at one size and "
-                             "synthesised at another)")
-    if denoise is not None or frame_size is not None:
-        from .frames_in import open_video
-        hdr, source = open_video(video, video_size[0], video_size[1], video_format)
-        if hdr["fmt"].layout == "rgb24":
-            raise ValueError("encode_gop: the temporal prefilter and the resampler work on Y'CbCr codes; an rgb24 source has none")
-        if frame_size is not None:
-            from .resample import check_sizes
-            check_sizes(int(hdr["H"]), int(hdr["W"]), frame_size[1], frame_size[0], hdr["fmt"], "encode_gop: coded_size")
-        if frame_range is not None:
-            try:
-                first, stop = (int(v) for v in frame_range)
-            except (TypeError, ValueError):
-                raise ValueError(f"encode_gop: frame_range must be (first, stop) (got {frame_range!r})") from None
-            if not 0 <= first < stop <= int(source.shape[0]):          # (what VideoFileCube refuses, before anything is filtered)
-                raise ValueError(f"encode_gop: frame_range ({first}, {stop}) is not a non-empty range inside the {int(source.shape[0])} "
-                                 f"frames of {video}")
-            source = source[first:stop]
-        if denoise is not None:
-            from .tfilter import denoise_range
-            filtered, denoise_log = denoise_range(source, int(hdr["H"]), int(hdr["W"]), hdr["fmt"], device, sigma=denoise,
-                                                  gain=float(denoise_gain))
-        if frame_size is not None:
-            from .resample import resample_range
-            filtered = resample_range(source if filtered is None else filtered, int(hdr["H"]), int(hdr["W"]), hdr["fmt"], frame_size[1],
-                                      frame_size[0], device)
-            display = (int(hdr["W"]), int(hdr["H"]))
-        del source
-    cube = VideoFileCube(video, optical_flow_dir=flow_dir, W=video_size[0], H=video_size[1], fmt=video_format, device=device,
-                         frame_range=frame_range, frames=filtered, frame_size=frame_size)
-    fit_frames = filtered if weighted else None          # what the fit sees, for the weighted PSNR of the file image
-    del filtered
-    if weighted and cube.fmt.layout == "rgb24":
-        raise ValueError("encode_gop: the weighted PSNR of a weighted fit is taken on luma codes; an rgb24 source has none")
-    if film_grain and cube.fmt.layout == "rgb24":
-        raise ValueError("encode_gop: film grain is measured and synthesised in the delivered Y'CbCr domain; an rgb24 source has none")
-    source_fmt = cube.fmt
-    log = {"W": cube.width, "H": cube.height, "frames": cube.len_z_frames, "steps": int(steps)}
+    log = {"W": cube.width, "H": cube.height, "frames": cube.len_z_frames, "steps": int(o.steps)}
     if denoise_log is not None:
         log["denoise"] = denoise_log
-    geometry_source = cube
-    if estimate_flow:
+    if o.estimate_flow:
         from .flow import EstimatedFlowCube
         cube = EstimatedFlowCube(cube, device=device)
-    elif flow_dir is None:
+    elif o.flow_dir is None:
         opt.optical_lambda = 0.0
-    configure_fit(mp_, opt, cube, steps, lmbda, slab_frames, densify_grad_threshold)
-    opt.loss_domain = loss_domain
-    opt.distortion = distortion
-    if weighted:
-        pc, trainer = new_fit(cube, mp_, opt, pipe, anchors, device, init=init, init_cell=init_cell, init_mix=init_mix, weighting=weighting,
-                              weight_strength=weight_strength, weight_cell=weight_cell, roi=roi, weight_file=weight_file,
-                              roi_base_hw=(display[1], display[0]) if frame_size is not None else None)
-        weighting_log, weight_maps = trainer.weighting, trainer.weight_maps.cpu()
-    else:
-        pc, trainer = new_fit(cube, mp_, opt, pipe, anchors, device, init=init, init_cell=init_cell, init_mix=init_mix)
-    log["init"] = init
-    if init == "detail":
-        log["init_cell"], log["init_mix"] = int(init_cell), float(init_mix)
-    log["anchors_initial"] = int(pc._anchor.shape[0])
-    log["loss_domain"], log["loss_matrix"] = trainer.loss_domain, trainer.loss_matrix
-    log["distortion"] = trainer.distortion
+    configure_fit(mp_, opt, cube, o.steps, o.lmbda, o.slab_frames, o.densify_grad_threshold)
+    opt.loss_domain, opt.distortion = o.loss_domain, o.distortion
+    pc, trainer = new_fit(cube, mp_, opt, pipe, o.anchors, device,
+                          **o.new_fit_keywords(roi_base_hw=display_size and (display_size[1], display_size[0])))
+    weights = (trainer.weighting, trainer.weight_maps.cpu()) if o.weighted else None
+    log.update(o.init_log(), anchors_initial=int(pc._anchor.shape[0]), loss_domain=trainer.loss_domain, loss_matrix=trainer.loss_matrix,
+               distortion=trainer.distortion)
     bg = trainer.background
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for it in range(1, int(steps) + 1):
+    for it in range(1, int(o.steps) + 1):
         trainer.step(it)
     torch.cuda.synchronize()
     log["fit_seconds"] = time.perf_counter() - t0
@@ -303,58 +266,89 @@ def encode_gop(video, device, frame_range=None, steps: int = 2000, lmbda: float 
         pack = conduct_stream_encoding(pc, mlp_file=mlp_file)          # (quantises the MLPs of pc in place: the shipped form)
         with open(mlp_file, "rb") as f:
             mlp_bytes = f.read()
-    blob = bitstream_bytes(pc, pack, CubeGeometry.of(geometry_source, mp_, pipe, bg.tolist()), mlp_bytes)
     log["anchors_coded"] = int(pack.n)
-    # the decoder's own path on the file image: the hashes are those of the pictures IT produces
-    del trainer, cube, geometry_source, pc, pack
-    gc.collect()
-    fmt = hash_format or FrameFormat("yuv420p")
-    res = decode_video(parse_bitstream(blob), NullSink(), fmt=fmt, verify=True, device=device)
-    blob = with_hashes(blob, fmt, res["hashes"])
-    del res["hashes"]
-    gc.collect()
-    torch.cuda.empty_cache()
-    log["hash_format"], log["verify_decode_fps"] = fmt.name, res["fps"]
-    if weighted:
-        if fit_frames is None:
-            from .frames_in import open_video
-            _, fit_frames = open_video(video, video_size[0], video_size[1], video_format)
-            if frame_range is not None:
-                fit_frames = fit_frames[int(frame_range[0]):int(frame_range[1])]
-        psnr_y, wpsnr_y = coded_wpsnr(parse_bitstream(blob), fit_frames, source_fmt, weight_maps, weighting_log["cell"], device)
-        log["weighting"] = dict(weighting_log, psnr_y=psnr_y, wpsnr_y=wpsnr_y)
-        del fit_frames
-        gc.collect()
-        torch.cuda.empty_cache()
-    if frame_size is not None:
-        from .bitstream import with_display
-        from .frames_in import open_video
-        blob = with_display(blob, display)
-        _, source = open_video(video, video_size[0], video_size[1], video_format)
-        if frame_range is not None:
-            source = source[int(frame_range[0]):int(frame_range[1])]
-        psnr_y, psnr_611 = display_psnr(parse_bitstream(blob), source, source_fmt, device)
-        log["display"] = {"W": display[0], "H": display[1], "filter": "lanczos3", "psnr_y": psnr_y, "psnr_611": psnr_611}
-        del source
-        gc.collect()
-        torch.cuda.empty_cache()
-    if film_grain:
-        import hashlib
+    return bitstream_bytes(pc, pack, CubeGeometry.of(geometry_source, mp_, pipe, bg.tolist()), mlp_bytes), log, weights
 
-        from .bitstream import with_grain
-        from .frames_in import open_video
-        from .grain import blocks_used, fit_grain
-        _, source = open_video(video, video_size[0], video_size[1], video_format)
-        if frame_range is not None:
-            source = source[int(frame_range[0]):int(frame_range[1])]
-        stats = grain_statistics(parse_bitstream(blob), source, log["H"], log["W"], source_fmt, device, flat_threshold=grain_flat_threshold,
-                                 max_residual=grain_max_residual)
-        seed = int.from_bytes(hashlib.sha256(blob).digest()[:8], "little") if grain_seed is None else int(grain_seed)
-        params = fit_grain(stats, seed, gain=float(grain_gain), source=source_fmt)
-        blob = with_grain(blob, params)
-        log["grain"] = dict(params.summary(), blocks=blocks_used(stats), gain=float(grain_gain))
-        del source
-        gc.collect()
-        torch.cuda.empty_cache()
-    log["sections"] = {t.decode("ascii"): len(p) for t, p in unpack_sections(blob)}
-    return blob, log
+
+def verify_decode(image, device, options):
+    """The decoder's own path on the file image -> ``(the image with the section PHSH, log entries)``: it is decoded into a null sink by
+    the function, batch size and format the decoder will use (``decode_video``), and the hashes are those of the pictures IT produces.
+    Log entries: "hash_format", "verify_decode_fps"."""
+    from .bitstream import NullSink, decode_video, parse_bitstream, with_hashes
+    from .frames_out import FrameFormat
+    fmt = options.hash_format or FrameFormat("yuv420p")
+    res = decode_video(parse_bitstream(image), NullSink(), fmt=fmt, verify=True, device=device)
+    return with_hashes(image, fmt, res["hashes"]), {"hash_format": fmt.name, "verify_decode_fps": res["fps"]}
+
+
+def measure_weighting(image, device, options, fmt, source, weights, fit_frames=None):
+    """A weighted fit (else nothing happens): the weights only shaped the fit, so the image stays as it is.  It is decoded once more,
+    into the format and size of the frames the fit saw (``fit_frames``; None: those of ``source = (video, frame_range)``).
+    Log entry: "weighting": {"sources", "cell", ("strength", "clamp": activity), ("roi": the scaled rectangles), "min", "max", "psnr_y",
+    "wpsnr_y": ``coded_wpsnr``}."""
+    from .bitstream import parse_bitstream
+    if weights is None:
+        return image, {}
+    if fit_frames is None:
+        fit_frames = source_range(*source, options)[1]
+    psnr_y, wpsnr_y = coded_wpsnr(parse_bitstream(image), fit_frames, fmt, weights[1], weights[0]["cell"], device)
+    return image, {"weighting": dict(weights[0], psnr_y=psnr_y, wpsnr_y=wpsnr_y)}
+
+
+def measure_display(image, device, options, fmt, source, display_size):
+    """``coded_size`` (else nothing happens): the image gets the section DISP (the source's size and the filter) and is decoded once
+    more, into the source's format at display size, against the ORIGINAL source's codes (``display_psnr``).
+    Log entry: "display": {"W", "H", "filter": "lanczos3", "psnr_y", "psnr_611": (6 Y + U + V) / 8 of the plane PSNRs}."""
+    from .bitstream import parse_bitstream, with_display
+    if display_size is None:
+        return image, {}
+    image = with_display(image, display_size)
+    psnr_y, psnr_611 = display_psnr(parse_bitstream(image), source_range(*source, options)[1], fmt, device)
+    return image, {"display": {"W": display_size[0], "H": display_size[1], "filter": "lanczos3", "psnr_y": psnr_y, "psnr_611": psnr_611}}
+
+
+def measure_grain(image, device, options, fmt, source):
+    """``film_grain`` (else nothing happens): the image is decoded once more, into the SOURCE's own format, and the flat-block statistics
+    of the ORIGINAL source's codes against it (``grain_statistics``; with ``denoise`` the grain the prefilter removed is what the decoder
+    puts back) are fitted to film-grain parameters (``grain.fit_grain`` with ``grain_gain``; ``grain_seed`` None: a seed derived from the
+    image as it stands here), which the image then carries as its section GRAN.  The picture hashes stay those of the ungrained pictures.
+    Log entry: "grain": {"seed", "scale", "kx", "ky", "source", "blocks", "gain"}."""
+    import hashlib
+
+    from .bitstream import parse_bitstream, with_grain
+    from .grain import blocks_used, fit_grain
+    if not options.film_grain:
+        return image, {}
+    hdr, frames = source_range(*source, options)
+    stats = grain_statistics(parse_bitstream(image), frames, int(hdr["H"]), int(hdr["W"]), fmt, device,
+                             flat_threshold=options.grain_flat_threshold, max_residual=options.grain_max_residual)
+    seed = int.from_bytes(hashlib.sha256(image).digest()[:8], "little") if options.grain_seed is None else int(options.grain_seed)
+    params = fit_grain(stats, seed, gain=float(options.grain_gain), source=fmt)
+    return with_grain(image, params), {"grain": dict(params.summary(), blocks=blocks_used(stats), gain=float(options.grain_gain))}
+
+
+def encode_gop(video, device, frame_range=None, options=None, **fields):
+    """One group of pictures of a video file -> ``(the bytes of a complete GSVC file, log)``: what tools/gsvc_encode.py does with a whole
+    clip, for the frames ``frame_range = (first, stop)`` of it (None: all).  ``options``: an ``encode_options.EncodeOptions``, which
+    documents every option, or its fields as keywords (both: ``TypeError``).  The stages and the log entries of each are in the
+    docstrings of the functions this calls; the module's docstring has the table."""
+    from .bitstream import unpack_sections
+    from .encode_options import EncodeOptions
+    if options is not None and fields:
+        raise TypeError("encode_gop: give options= or its fields as keywords, not both")
+    o, source = EncodeOptions(**fields) if options is None else options, (video, frame_range)
+    frames, coded_size, display_size, denoise_log = prepare_source(video, device, frame_range, o)
+    cube = source_cube(video, device, frame_range, o, frames, coded_size)
+    frames, fmt = frames if o.weighted else None, cube.fmt          # (a weighted fit keeps what it saw on the host, for its weighted PSNR)
+    image, log, weights = fit_gop(cube, device, o, display_size, denoise_log)
+    del cube
+    for stage, more in ((verify_decode, ()), (measure_weighting, (fmt, source, weights, frames)),
+                        (measure_display, (fmt, source, display_size)), (measure_grain, (fmt, source))):
+        release()
+        image, entry = stage(image, device, o, *more)
+        log.update(entry)
+    release()
+    log["sections"] = {t.decode("ascii"): len(p) for t, p in unpack_sections(image)}
+    return image, log
+
+

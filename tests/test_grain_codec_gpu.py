@@ -126,6 +126,28 @@ def test_grain_is_synthesised_behind_the_hashes_and_is_the_reference(coded):
     assert res_rgb["film_grain"] is False and np.array_equal(rgb_on, _decode(B.parse_bitstream(blob), fmt=FrameFormat("rgb24"), verify=False, film_grain=False)[0])
 
 
+def test_decoded_batches_are_the_render_batches_and_the_pairing_counts_frames(coded):
+    """``fit_setup.decoded_batches`` (what the encoder's three measures decode through) on the first GOP with a batch that does not divide
+    it: the batches start at 0, 3, 6, the last one is the short one, and their rows are the frames of ``render_frames_u8`` at that
+    batch, byte for byte; ``decoded_against`` pairs them with the source's rows and refuses a source of another length at the end."""
+    from gsvc_amd.fit_setup import decoded_against, decoded_batches
+    from gsvc_amd.frames_out import render_frames_u8
+    dev = torch.device("cuda", 0)
+    blob = coded["gops"][0]
+    got = list(decoded_batches(B.parse_bitstream(blob), FMT, dev, batch=3))
+    assert [first for first, _ in got] == [0, 3, 6] and [tuple(rows.shape) for _, rows in got] == [(3, NB), (3, NB), (2, NB)]
+    assert all(rows.dtype == torch.uint8 and rows.device.type == "cuda" for _, rows in got) and torch.is_grad_enabled()
+    pc, cams, pipe, bg = B.parse_bitstream(blob).build_model(dev)
+    with torch.no_grad():
+        want = torch.stack(list(render_frames_u8(cams, pc, pipe, bg, fmt=FMT, batch=3, to_host=False)))
+    assert torch.equal(torch.cat([rows for _, rows in got]), want)
+    source = read_y4m(coded["clip"])[1][:GOP]
+    pairs = list(decoded_against(B.parse_bitstream(blob), source, FMT, dev, "test", batch=3))
+    assert torch.equal(torch.cat([rows for rows, _ in pairs]), want) and np.array_equal(torch.cat([src for _, src in pairs]).cpu().numpy(), source)
+    with pytest.raises(ValueError, match=f"test: the file decodes to {GOP} frames, the source has {GOP - 1}"):
+        list(decoded_against(B.parse_bitstream(blob), source[:GOP - 1], FMT, dev, "test", batch=3))
+
+
 def test_a_frame_range_across_the_cut_has_the_bytes_of_the_full_decode(coded, capsys):
     import gsvc_decode
     whole, res = _decode(coded["file"], strict=True)

@@ -91,13 +91,11 @@ def _trainer(cube, distortion, domain="rgb"):
 
 
 def test_default_distortion_is_ssim():
-    import inspect
-
     from gsvc_amd.arguments import OptimizationParams, cfg_20240919
-    from gsvc_amd.fit_setup import encode_gop
+    from gsvc_amd.encode_options import EncodeOptions
     assert OptimizationParams().distortion == "ssim"
     assert cfg_20240919()[1].distortion == "ssim"
-    assert inspect.signature(encode_gop).parameters["distortion"].default == "ssim"
+    assert EncodeOptions().distortion == "ssim"
 
 
 def test_trainer_refusals():

@@ -130,6 +130,15 @@ def test_encode_at_a_coded_size_and_decode_at_the_display_size(clip, handed):
     again = Collect()
     res = S.decode_sequence(seq, again, fmt=FMT, strict=True)
     assert (res["W"], res["H"], res["resampled"]) == (W, H, True) and np.array_equal(again.array(), shown.array())
+    # what the encoder's display measure decodes through: the render batches of render_frames_u8 at the display size, byte for byte
+    from gsvc_amd.fit_setup import decoded_batches
+    from gsvc_amd.frames_out import render_frames_u8
+    got = list(decoded_batches(B.parse_bitstream(blob), FMT, dev, batch=3, out_size=(H, W)))
+    assert [first for first, _ in got] == [0, 3, 6] and [tuple(rows.shape) for _, rows in got] == [(3, NB), (3, NB), (2, NB)]
+    pc, cams, pipe, bg = B.parse_bitstream(blob).build_model(dev)
+    with torch.no_grad():
+        want = torch.stack(list(render_frames_u8(cams, pc, pipe, bg, fmt=FMT, batch=3, to_host=False, out_size=(H, W))))
+    assert torch.equal(torch.cat([rows for _, rows in got]), want)
 
 
 def test_with_denoise_the_fit_is_handed_the_resampled_filtered_frames(clip, handed):

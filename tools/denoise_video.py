@@ -17,15 +17,6 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def _frame_format(text):
-    """LAYOUT[,MATRIX[,RANGE]] -> FrameFormat; LAYOUT in ffmpeg's spelling (yuv420p, yuv444p10le, ...)."""
-    from gsvc_amd.frames_out import FrameFormat
-    name, *rest = text.split(",")
-    if len(rest) > 2:
-        raise SystemExit(f"a frame format is LAYOUT[,MATRIX[,RANGE]] (got {text!r})")
-    return FrameFormat.from_name(name, **dict(zip(("matrix", "range"), rest)))
-
-
 def parse_args(argv=None):
     from gsvc_amd.tfilter import parse_sigma          # (the one reader of an {auto,SIGMA} option; needs neither torch nor the library)
     ap = argparse.ArgumentParser()
@@ -57,11 +48,13 @@ def main(argv=None):
     args = parse_args(argv)
     import torch
 
+    from gsvc_amd.encode_options import parse_frame_format
+    from gsvc_amd.resample import parse_size
     from gsvc_amd.tfilter import denoise_video
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    vw, vh = (int(v) for v in args.video_size.lower().split("x")) if args.video_size else (None, None)
-    video_fmt = _frame_format(args.video_format) if args.video_format else None
+    vw, vh = parse_size(args.video_size) if args.video_size else (None, None)          # (the namespace keeps the text)
+    video_fmt = parse_frame_format(args.video_format) if args.video_format else None
     ranges = None
     if args.gop_frames is not None:
         from gsvc_amd import scene

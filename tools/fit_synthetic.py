@@ -44,28 +44,16 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def _frame_format(text):
-    """LAYOUT[,MATRIX[,RANGE]] -> FrameFormat; LAYOUT in ffmpeg's spelling (yuv420p, yuv444p10le, rgb24, ...)."""
-    from gsvc_amd.frames_out import FrameFormat
-    name, *rest = text.split(",")
-    if len(rest) > 2:
-        raise SystemExit(f"a frame format is LAYOUT[,MATRIX[,RANGE]] (got {text!r})")
-    return FrameFormat.from_name(name, **dict(zip(("matrix", "range"), rest)))
+from gsvc_amd.encode_options import add_fit_arguments, check_fit_arguments, options_from_args, parse_frame_format as _frame_format  # noqa: E402, I001
 
 
 def parse_args(argv=None):
-    from gsvc_amd.tfilter import parse_sigma          # (the one reader of an {auto,SIGMA} option; needs neither torch nor the library)
-    from gsvc_amd.wdist import parse_roi              # (X,Y,W,H:WEIGHT)
     ap = argparse.ArgumentParser()
-    ap.add_argument("--steps", type=int, default=2000)
+    add_fit_arguments(ap)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--frames", type=int, default=64)
-    ap.add_argument("--anchors", type=int, default=100_000)
-    ap.add_argument("--lmbda", type=float, default=0.004)
-    ap.add_argument("--slab-frames", type=float, default=16.0, help="z-slab of a render in frames (2 x threshold x scale)")
     ap.add_argument("--eval-frames", type=int, default=16)
-    ap.add_argument("--densify-grad-threshold", type=float, default=None, help="default: the reference's 5e-4")
     ap.add_argument("--payload-tol", type=float, default=0.02, help="allowed |coded payload / estimate_final_bits - 1| of the attribute streams")
     ap.add_argument("--json", default=None)
     ap.add_argument("--dump-coder-inputs", default=None, help="npz of what the first slabs hand to the entropy coder (symbols, mu, sigma)")
@@ -83,60 +71,15 @@ def parse_args(argv=None):
                     help="write the shipped-form model (8-bit MLPs, the streams coded under them) as ONE bitstream file (.gsvc, gsvc_amd/bitstream.py): "
                          "log['bitstream_bytes'] beside log['total_bytes'], the size of the directory of streams")
     ap.add_argument("--video", default=None, metavar="PATH",
-                    help="fit this 8-bit or 10 / 12 / 16-bit video file (.y4m, or raw .yuv / .rgb with --video-size) instead of the synthetic frames")
-    ap.add_argument("--video-size", default=None, metavar="WxH", help="frame size of a raw --video file")
-    ap.add_argument("--video-format", default=None, metavar="LAYOUT[,MATRIX[,RANGE]]",
-                    help="e.g. yuv420p,bt601,full or yuv420p10le (default: yuv420p,bt709,limited; rgb24 for .rgb; a .y4m file's own layout, "
-                         "depth and range win)")
-    ap.add_argument("--flow-dir", default=None, metavar="DIR", help="optical-flow files of --video, one per frame pair (none: optical_lambda = 0)")
-    ap.add_argument("--estimate-flow", action="store_true",
-                    help="estimate the optical flow from the frames themselves (gsvc_amd.flow.EstimatedFlowCube): a --video keeps optical_lambda "
-                         "without a --flow-dir, the synthetic video's analytic flow is replaced")
+                    help="fit this 8-bit or 10 / 12 / 16-bit video file (.y4m, or raw .yuv / .rgb with --video-size) instead of the synthetic frames; "
+                         "without --flow-dir or --estimate-flow its optical_lambda is 0, with --estimate-flow the synthetic video's analytic flow is replaced")
     ap.add_argument("--optical-lambda", type=float, default=None, help="weight of the flow-guided loss (default: the configuration's)")
     ap.add_argument("--video-resident", choices=("float", "u8"), default="float",
                     help="keep the video on the device as float32 pictures, or as the file's bytes (converted one frame per fetch)")
-    ap.add_argument("--film-grain", action="store_true",
-                    help="with a Y'CbCr --video: measure the grain the fit removed against the file's codes and fit film-grain parameters "
-                         "(gsvc_amd/grain.py): log['grain'], and the GRAN section of --write-bitstream")
-    ap.add_argument("--distortion", choices=("ssim", "ms_ssim"), default="ssim",
-                    help="the structural term of the distortion: single-scale SSIM, or MS-SSIM (rgb domain, sides above 160 pixels)")
-    ap.add_argument("--loss-domain", choices=("rgb", "yuv420", "yuv444"), default="rgb",
-                    help="where the fit takes its distortion: float RGB, or Y'CbCr planes (gsvc_amd/yuv_loss.py): those of a Y'CbCr --video "
-                         "file's sample codes, else the transform of the RGB pictures")
-    ap.add_argument("--init", choices=("uniform", "detail"), default="uniform",
-                    help="where the first anchors are drawn: uniformly in the cube, or where the luma has detail (gsvc_amd/detail.py)")
-    ap.add_argument("--init-cell", type=int, choices=(4, 8, 16), default=None, help="with --init detail: the cell of the detail map in pixels (default 8)")
-    ap.add_argument("--init-mix", type=float, default=None, metavar="X",
-                    help="with --init detail: the share of the points that is still drawn uniformly, 0 .. 1 (default 0.25)")
-    ap.add_argument("--denoise", type=parse_sigma, default=None, metavar="{auto,SIGMA}",
-                    help="with a Y'CbCr --video: fit its motion-compensated temporally filtered frames (gsvc_amd/tfilter.py; 'auto' estimates "
-                         "the noise, a number gives its sigma in codes).  Every metric is still reported against the UNFILTERED file")
-    ap.add_argument("--denoise-gain", type=float, default=None, metavar="X", help="with --denoise: scale the filter's strength (default 1.0)")
-    ap.add_argument("--weighting", choices=("activity",), default=None,
-                    help="weight the distortion per cell by the clip's activity (gsvc_amd/wdist.py); rgb loss domain and --distortion ssim only")
-    ap.add_argument("--weight-strength", type=float, default=None, metavar="S",
-                    help="with --weighting activity: > 0 moves weight to flat cells, < 0 to detail (default 0.5: a starting value, not measured)")
-    ap.add_argument("--weight-cell", type=int, choices=(4, 8, 16), default=None, help="the cell of the weight maps in pixels (default 8)")
-    ap.add_argument("--roi", action="append", type=parse_roi, default=None, metavar="X,Y,W,H:WEIGHT",
-                    help="a rectangle in pixels with this weight over a base of 1 (repeatable; later ones override earlier ones)")
-    ap.add_argument("--weight-map", default=None, metavar="FILE.npy",
-                    help="weights [Hc, Wc] or [frames, Hc, Wc] at --weight-cell; multiplies with the other sources")
     args = ap.parse_args(argv)
-    args.weighted = args.weighting is not None or bool(args.roi) or args.weight_map is not None
-    if args.weight_strength is not None and args.weighting is None:
-        ap.error("--weight-strength needs --weighting activity")
-    if args.weight_cell is not None and not args.weighted:
-        ap.error("--weight-cell needs --weighting, --roi or --weight-map")
-    if args.weighted and (args.loss_domain != "rgb" or args.distortion != "ssim"):
-        ap.error("weighted distortion needs --loss-domain rgb and --distortion ssim")
+    check_fit_arguments(ap, args)
     if args.denoise is not None and not args.video:
         ap.error("--denoise needs --video (a Y'CbCr file)")
-    if args.denoise is None and args.denoise_gain is not None:
-        ap.error("--denoise-gain needs --denoise")
-    if args.init != "detail" and (args.init_cell is not None or args.init_mix is not None):
-        ap.error("--init-cell and --init-mix need --init detail")
-    if args.init_mix is not None and not 0.0 <= args.init_mix <= 1.0:
-        ap.error("--init-mix must lie in 0 .. 1")
     if args.film_grain and not args.video:
         ap.error("--film-grain needs --video (a Y'CbCr file)")
     return args
@@ -162,23 +105,15 @@ def main(argv=None):
     rank, world, _ = gdist.init_from_env(os.environ.get("GSVC_DIST_BACKEND") or None)
     H, W, T, N = args.height, args.width, args.frames, args.steps
     mp_, opt, pipe = cfg_20240919()
+    opts = options_from_args(args)
     denoise_log = None
     if args.video:
+        from gsvc_amd.fit_setup import prepare_source
         from gsvc_amd.frames_in import VideoFileCube
         from gsvc_amd.frames_out import FrameFormat
-        vw, vh = (int(v) for v in args.video_size.lower().split("x")) if args.video_size else (None, None)
-        vfmt = _frame_format(args.video_format) if args.video_format else None
-        filtered = None
-        if args.denoise is not None:
-            # the fit sees the filtered frames only; the file as it is becomes the cube again once the fit is over (below)
-            from gsvc_amd.frames_in import open_video
-            from gsvc_amd.tfilter import denoise_range
-            hdr, source = open_video(args.video, vw, vh, vfmt)
-            if hdr["fmt"].layout == "rgb24":
-                raise ValueError("--denoise: the temporal prefilter works on Y'CbCr codes; an rgb24 --video has none")
-            filtered, denoise_log = denoise_range(source, int(hdr["H"]), int(hdr["W"]), hdr["fmt"], dev, sigma=args.denoise,
-                                                  gain=1.0 if args.denoise_gain is None else args.denoise_gain)
-            del source
+        (vw, vh), vfmt = opts.video_size, opts.video_format
+        # --denoise: the fit sees the filtered frames only; the file as it is becomes the cube again once the fit is over (below)
+        filtered, _, _, denoise_log = prepare_source(args.video, dev, None, opts)
         cube = VideoFileCube(args.video, optical_flow_dir=args.flow_dir, W=vw, H=vh, fmt=vfmt, device=dev, resident=args.video_resident,
                              frames=filtered)
         del filtered
@@ -208,14 +143,8 @@ def main(argv=None):
     configure_fit(mp_, opt, cube, N, args.lmbda, args.slab_frames, args.densify_grad_threshold)
     opt.loss_domain = args.loss_domain
     opt.distortion = args.distortion
-    init = {"init": args.init}
-    if args.init == "detail":
-        init.update(init_cell=8 if args.init_cell is None else args.init_cell, init_mix=0.25 if args.init_mix is None else args.init_mix)
-    weighting = {}
-    if args.weighted:
-        weighting = dict(weighting=args.weighting, weight_strength=0.5 if args.weight_strength is None else args.weight_strength,
-                         weight_cell=args.weight_cell, roi=args.roi, weight_file=args.weight_map)
-    pc, trainer = new_fit(cube, mp_, opt, pipe, args.anchors, dev, **init, **weighting)
+    init = opts.init_log()
+    pc, trainer = new_fit(cube, mp_, opt, pipe, args.anchors, dev, **opts.new_fit_keywords())
     weight_maps, weight_cell = (trainer.weight_maps.cpu(), trainer.weight_cell) if args.weighted else (None, None)
     bg = trainer.background
     log = {"config": {"H": H, "W": W, "frames": T, "steps": N, "anchors_init": args.anchors, **init,

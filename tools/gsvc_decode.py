@@ -49,6 +49,7 @@ def parse_args(argv=None):
 def main(argv=None):
     args = parse_args(argv)
     from gsvc_amd.bitstream import BitstreamError, delivered_size
+    from gsvc_amd.encode_options import parse_frame_format
     from gsvc_amd.frames_out import FrameFormat, open_sink
     from gsvc_amd.sequence import decode_sequence, open_sequence
     frames = None
@@ -66,10 +67,7 @@ def main(argv=None):
         return 2
     fmt, ext = None, os.path.splitext(args.output)[1].lower()
     if args.format:
-        name, *rest = args.format.split(",")
-        if len(rest) > 2:
-            raise SystemExit(f"a frame format is LAYOUT[,MATRIX[,RANGE]] (got {args.format!r})")
-        fmt = FrameFormat.from_name(name, **dict(zip(("matrix", "range"), rest)))
+        fmt = parse_frame_format(args.format)
     elif hash_format is not None:
         takes = {".y4m": ("yuv420p", "yuv444p"), ".yuv": ("yuv420p", "yuv444p"), ".rgb": ("rgb24",)}.get(ext, ("rgb24",))
         if hash_format.layout in takes:

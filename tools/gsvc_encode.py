@@ -35,88 +35,32 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def _frame_format(text):
-    """LAYOUT[,MATRIX[,RANGE]] -> FrameFormat; LAYOUT in ffmpeg's spelling (yuv420p, yuv444p10le, rgb24, ...)."""
-    from gsvc_amd.frames_out import FrameFormat
-    name, *rest = text.split(",")
-    if len(rest) > 2:
-        raise SystemExit(f"a frame format is LAYOUT[,MATRIX[,RANGE]] (got {text!r})")
-    return FrameFormat.from_name(name, **dict(zip(("matrix", "range"), rest)))
-
-
 def parse_args(argv=None):
-    from gsvc_amd.resample import parse_size          # (likewise for a WxH option)
-    from gsvc_amd.tfilter import parse_sigma          # (the one reader of an {auto,SIGMA} option; needs neither torch nor the library)
-    from gsvc_amd.wdist import parse_roi              # (X,Y,W,H:WEIGHT)
+    from gsvc_amd.encode_options import add_fit_arguments, check_fit_arguments          # (needs neither torch nor the library)
+    from gsvc_amd.resample import parse_size
     ap = argparse.ArgumentParser()
     ap.add_argument("video", help="8-bit or 10 / 12 / 16-bit video file: .y4m, or raw .yuv / .rgb with --video-size")
     ap.add_argument("-o", "--output", required=True, metavar="PATH", help="the bitstream file to write (.gsvc)")
-    ap.add_argument("--steps", type=int, default=2000)
-    ap.add_argument("--lmbda", type=float, default=0.004)
-    ap.add_argument("--anchors", type=int, default=100_000)
-    ap.add_argument("--slab-frames", type=float, default=16.0, help="z-slab of a render in frames (2 x threshold x scale)")
-    ap.add_argument("--densify-grad-threshold", type=float, default=None, help="default: the reference's 5e-4")
-    ap.add_argument("--estimate-flow", action="store_true", help="estimate the optical flow from the frames (gsvc_amd.flow.EstimatedFlowCube)")
-    ap.add_argument("--flow-dir", default=None, metavar="DIR", help="optical-flow files, one per frame pair")
-    ap.add_argument("--video-size", default=None, metavar="WxH", help="frame size of a raw video file")
-    ap.add_argument("--video-format", default=None, metavar="LAYOUT[,MATRIX[,RANGE]]", help="e.g. yuv420p,bt601,full or yuv420p10le")
+    add_fit_arguments(ap)
     ap.add_argument("--hash-format", default="yuv420p", metavar="LAYOUT[,MATRIX[,RANGE]]",
                     help="the frame format whose picture hashes the file carries: what the decoder verifies when it decodes to it")
-    ap.add_argument("--loss-domain", choices=("rgb", "yuv420", "yuv444"), default="rgb",
-                    help="where the fit takes its distortion: float RGB, or the Y'CbCr planes of the file (gsvc_amd/yuv_loss.py)")
-    ap.add_argument("--distortion", choices=("ssim", "ms_ssim"), default="ssim",
-                    help="the structural term of the fit's distortion: single-scale SSIM, or MS-SSIM as the metrics report it (rgb "
-                         "domain, sides above 160 pixels)")
     ap.add_argument("--gop-frames", type=int, default=None, metavar="N",
                     help="cut the clip into groups of pictures of at most N frames and write a sequence file (GSVS)")
     ap.add_argument("--scene-cuts", action="store_true", help="with --gop-frames: also start a GOP where the luma histogram changes")
     ap.add_argument("--cut-threshold", type=float, default=None, metavar="X",
                     help="histogram distance in [0, 1] above which a frame starts a scene (default 0.5: a starting value, not measured)")
     ap.add_argument("--min-gop", type=int, default=None, metavar="M", help="the shortest GOP (default 4); --gop-frames must be at least 2 M")
-    ap.add_argument("--init", choices=("uniform", "detail"), default="uniform",
-                    help="where the first anchors are drawn: uniformly in the cube, or where the luma has detail (gsvc_amd/detail.py)")
-    ap.add_argument("--init-cell", type=int, choices=(4, 8, 16), default=None, help="with --init detail: the cell of the detail map in pixels (default 8)")
-    ap.add_argument("--init-mix", type=float, default=None, metavar="X",
-                    help="with --init detail: the share of the points that is still drawn uniformly, 0 .. 1 (default 0.25)")
-    ap.add_argument("--film-grain", action="store_true",
-                    help="measure the grain the fit removed and ship its parameters (section GRAN); YUV sources only (gsvc_amd/grain.py)")
     ap.add_argument("--film-grain-gain", type=float, default=None, metavar="X", help="with --film-grain: scale the fitted strengths (default 1.0)")
     ap.add_argument("--film-grain-seed", type=int, default=None, metavar="N", help="with --film-grain: the 64-bit seed (default: derived from the file)")
-    ap.add_argument("--denoise", type=parse_sigma, default=None, metavar="{auto,SIGMA}",
-                    help="fit a motion-compensated temporally filtered source (gsvc_amd/tfilter.py): 'auto' estimates the noise per GOP, "
-                         "a number gives its sigma in codes; YUV sources only.  --film-grain still measures against the original source")
-    ap.add_argument("--denoise-gain", type=float, default=None, metavar="X", help="with --denoise: scale the filter's strength (default 1.0)")
     ap.add_argument("--coded-size", type=parse_size, default=None, metavar="WxH",
                     help="fit the source resampled to this size (Lanczos-3 on the codes, a ratio of at most 4 per side) and let the decoder "
                          "resample back to the source's size (section DISP); YUV sources only, not with --flow-dir or --film-grain")
-    ap.add_argument("--weighting", choices=("activity",), default=None,
-                    help="weight the fit's distortion per cell by the clip's activity (gsvc_amd/wdist.py; per GOP with --gop-frames); rgb loss "
-                         "domain and --distortion ssim only, YUV sources only")
-    ap.add_argument("--weight-strength", type=float, default=None, metavar="S",
-                    help="with --weighting activity: > 0 moves weight to flat cells, < 0 to detail (default 0.5: a starting value, not measured)")
-    ap.add_argument("--weight-cell", type=int, choices=(4, 8, 16), default=None, help="the cell of the weight maps in pixels (default 8)")
-    ap.add_argument("--roi", action="append", type=parse_roi, default=None, metavar="X,Y,W,H:WEIGHT",
-                    help="a rectangle in the source's pixels with this weight over a base of 1 (repeatable; later ones override earlier ones)")
-    ap.add_argument("--weight-map", default=None, metavar="FILE.npy",
-                    help="weights [Hc, Wc] or [frames, Hc, Wc] at --weight-cell of the frames the fit sees; multiplies with the other sources")
     args = ap.parse_args(argv)
-    weighted = args.weighting is not None or args.roi or args.weight_map is not None
-    if args.weight_strength is not None and args.weighting is None:
-        ap.error("--weight-strength needs --weighting activity")
-    if args.weight_cell is not None and not weighted:
-        ap.error("--weight-cell needs --weighting, --roi or --weight-map")
-    if weighted and (args.loss_domain != "rgb" or args.distortion != "ssim"):
-        ap.error("weighted distortion needs --loss-domain rgb and --distortion ssim")
+    check_fit_arguments(ap, args)
     if args.coded_size is not None and (args.flow_dir is not None or args.film_grain):
         ap.error("--coded-size does not go with --flow-dir (those flows are at the source's size) or --film-grain")
-    if args.denoise is None and args.denoise_gain is not None:
-        ap.error("--denoise-gain needs --denoise")
     if not args.film_grain and (args.film_grain_gain is not None or args.film_grain_seed is not None):
         ap.error("--film-grain-gain and --film-grain-seed need --film-grain")
-    if args.init != "detail" and (args.init_cell is not None or args.init_mix is not None):
-        ap.error("--init-cell and --init-mix need --init detail")
-    if args.init_mix is not None and not 0.0 <= args.init_mix <= 1.0:
-        ap.error("--init-mix must lie in 0 .. 1")
     if args.gop_frames is None and (args.scene_cuts or args.cut_threshold is not None or args.min_gop is not None):
         ap.error("--scene-cuts, --cut-threshold and --min-gop need --gop-frames")
     return args
@@ -126,27 +70,13 @@ def main(argv=None):
     args = parse_args(argv)
     import torch
 
+    from gsvc_amd.encode_options import options_from_args
     from gsvc_amd.fit_setup import encode_gop
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
-    vw, vh = (int(v) for v in args.video_size.lower().split("x")) if args.video_size else (None, None)
-    video_fmt = _frame_format(args.video_format) if args.video_format else None
-    fit = dict(steps=args.steps, lmbda=args.lmbda, anchors=args.anchors, slab_frames=args.slab_frames,
-               densify_grad_threshold=args.densify_grad_threshold, estimate_flow=args.estimate_flow, flow_dir=args.flow_dir,
-               video_size=(vw, vh), video_format=video_fmt, hash_format=_frame_format(args.hash_format), loss_domain=args.loss_domain,
-               distortion=args.distortion, init=args.init, init_cell=8 if args.init_cell is None else args.init_cell,
-               init_mix=0.25 if args.init_mix is None else args.init_mix)
-    if args.film_grain:
-        fit.update(film_grain=True, grain_gain=1.0 if args.film_grain_gain is None else args.film_grain_gain, grain_seed=args.film_grain_seed)
-    if args.denoise is not None:
-        fit.update(denoise=args.denoise, denoise_gain=1.0 if args.denoise_gain is None else args.denoise_gain)
-    if args.coded_size is not None:
-        fit.update(coded_size=args.coded_size)
-    if args.weighting is not None or args.roi or args.weight_map is not None:
-        fit.update(weighting=args.weighting, weight_strength=0.5 if args.weight_strength is None else args.weight_strength,
-                   weight_cell=args.weight_cell, roi=args.roi, weight_file=args.weight_map)
+    opts = options_from_args(args)
     if args.gop_frames is None:
-        blob, log = encode_gop(args.video, dev, **fit)
+        blob, log = encode_gop(args.video, dev, options=opts)
         with open(args.output, "wb") as f:
             f.write(blob)
         log = dict({"output": args.output}, **log)
@@ -159,7 +89,7 @@ def main(argv=None):
     from gsvc_amd import scene
     from gsvc_amd.frames_in import open_video
     from gsvc_amd.sequence import write_sequence
-    header, frames = open_video(args.video, vw, vh, video_fmt)
+    header, frames = open_video(args.video, *opts.video_size, opts.video_format)
     H, W, T = int(header["H"]), int(header["W"]), int(frames.shape[0])
     min_gop = scene.DEFAULT_MIN_GOP if args.min_gop is None else args.min_gop
     threshold = scene.DEFAULT_CUT_THRESHOLD if args.cut_threshold is None else args.cut_threshold
@@ -170,20 +100,18 @@ def main(argv=None):
     flags = scene.gop_cut_flags(plan, cuts)
     blobs, gops, fit_seconds = [], [], 0.0
     for (first, count), cut in zip(plan, flags):
-        blob, one = encode_gop(args.video, dev, frame_range=(first, first + count), **fit)          # (everything of the GOP's fit is released inside)
+        blob, one = encode_gop(args.video, dev, frame_range=(first, first + count), options=opts)          # (everything of the GOP's fit is released inside)
         blobs.append(blob)
         fit_seconds += one["fit_seconds"]
         gops.append({"first": first, "frames": count, "bytes": len(blob), "bpp": 8.0 * len(blob) / (H * W * count),
                      "fit_seconds": one["fit_seconds"], "cut": int(cut), "anchors_initial": one["anchors_initial"], "anchors_coded": one["anchors_coded"],
-                     "sections": one["sections"], **({"grain": one["grain"]} if "grain" in one else {}),
-                     **({"denoise": one["denoise"]} if "denoise" in one else {}), **({"display": one["display"]} if "display" in one else {}),
-                     **({"weighting": one["weighting"]} if "weighting" in one else {})})
+                     "sections": one["sections"], **{k: one[k] for k in ("grain", "denoise", "display", "weighting") if k in one}})
     fps = header.get("fps") or (30, 1)
     write_sequence(args.output, blobs, cW, cH, fps, flags)
     log = {"output": args.output, "W": cW, "H": cH, **({"display": {"W": W, "H": H, "filter": "lanczos3"}} if args.coded_size else {}), "frames": T, "steps": args.steps, "fit_seconds": fit_seconds,
            "loss_domain": one["loss_domain"], "loss_matrix": one["loss_matrix"], "distortion": one["distortion"],
            **{k: one[k] for k in ("init", "init_cell", "init_mix") if k in one},
-           "hash_format": _frame_format(args.hash_format).name, "gop_frames": args.gop_frames, "min_gop": min_gop,
+           "hash_format": opts.hash_format.name, "gop_frames": args.gop_frames, "min_gop": min_gop,
            "scene_cuts": cuts if args.scene_cuts else None, "cut_threshold": threshold if args.scene_cuts else None, "gops": gops}
     log["total_bytes"] = int(os.path.getsize(args.output))
     log["bpp"] = 8.0 * log["total_bytes"] / (H * W * T)
@@ -193,3 +121,5 @@ def main(argv=None):
 
 if __name__ == "__main__":
     main()
+
+

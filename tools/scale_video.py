@@ -15,15 +15,6 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def _frame_format(text):
-    """LAYOUT[,MATRIX[,RANGE]] -> FrameFormat; LAYOUT in ffmpeg's spelling (yuv420p, yuv444p10le, ...)."""
-    from gsvc_amd.frames_out import FrameFormat
-    name, *rest = text.split(",")
-    if len(rest) > 2:
-        raise SystemExit(f"a frame format is LAYOUT[,MATRIX[,RANGE]] (got {text!r})")
-    return FrameFormat.from_name(name, **dict(zip(("matrix", "range"), rest)))
-
-
 def parse_args(argv=None):
     from gsvc_amd.resample import parse_size          # (the one reader of a WxH option; needs neither torch nor the library)
     ap = argparse.ArgumentParser()
@@ -42,11 +33,12 @@ def main(argv=None):
     args = parse_args(argv)
     import torch
 
+    from gsvc_amd.encode_options import parse_frame_format
     from gsvc_amd.resample import resample_video
     dev = torch.device("cuda", 0)
     torch.cuda.set_device(dev)
     vw, vh = args.video_size or (None, None)
-    video_fmt = _frame_format(args.video_format) if args.video_format else None
+    video_fmt = parse_frame_format(args.video_format) if args.video_format else None
     log = resample_video(args.video, args.output, args.size, W=vw, H=vh, fmt=video_fmt, device=dev)
     log = dict({"output": args.output}, **log)
     print(json.dumps(log))
